@@ -1,13 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark: Flow.combine_with(mode=3) at 2160 x 3840 float32 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one synthetic batch of flow-field pairs that is already resident
 in HBM: one launch of the fused compose kernel (ofl_compose3_dev, with the reference's zero-flow
 predicates evaluated in the same launch).  Steps rotate over `--sets` distinct input/output sets so
-that consecutive steps cannot be served from the 256 MiB Infinity Cache.  With N > 1 every rank owns
+that consecutive steps cannot be served from the 256 MiB Infinity Cache.  A plain run sets up, warms up,
+times exactly K steps and prints the headline; `--full` adds everything else the line can carry (other
+sampling patterns, the other BASELINE configs, strong scaling, the CPU baseline, the check of the fused
+predicates).  `--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy.  With N > 1 every rank owns
 one GPU and its own pairs (independent units, "weak" scaling, no data-path collective); the only
 exchange is the one-off RCCL broadcast of the shared first flow field before the timed region.
 Started WITHOUT a launcher (`python bench.py --gpus N`, WORLD_SIZE unset) the process becomes the launcher
@@ -29,6 +32,9 @@ H, W = 2160, 3840
 BYTES_PER_PX = 27            # 2 x (8 + 1) read + (8 + 1) written
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8 TB/s HBM3E peak
 TRAFFIC_FILES = ("profiles/r04_compose3_traffic.json", "profiles/r03_compose3_traffic.json", "profiles/r02_compose3_traffic.json", "profiles/r01_compose3_traffic.json")
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: whole outputs up to this size, else DUMP_SAMPLE_PX seeded pixels
+DUMP_SAMPLE_PX = 1 << 21
+DUMP_SEED = 20240611
 
 
 PATTERN = "scale"
@@ -116,13 +122,44 @@ def parse_args():
     ap.add_argument("--pattern", default="scale", choices=["scale", "shift", "rot"],
                     help="sampling pattern of the gather (default: the BASELINE config)")
     ap.add_argument("--angle", type=float, default=-30.0, help="rotation angle of f1 (default: the BASELINE config, -30 deg)")
-    ap.add_argument("--min-timed-ms", type=float, default=100.0,
-                    help="the K timed steps are repeated (each repeat bracketed like the first) until this much GPU time has been "
-                         "timed; the line reports the MEDIAN repeat.  --steps / --warmup stay what the driver passes")
+    ap.add_argument("--min-timed-ms", type=float, default=0.0,
+                    help="repeat the K timed steps (each repeat bracketed like the first) until this much GPU time has been "
+                         "timed and report the MEDIAN repeat (default 0: the K steps are timed once)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: the shift / rot patterns, the other BASELINE "
+                         "configs, the strong-scaling entries, the CPU baseline and the fused zero-flow predicates "
+                         "(the --no-* options narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the vecs and masks of the last step's pairs as DIR/vecs.npy and "
+                         "DIR/mask.npy (float32; a fixed, seeded pixel sample when the whole output exceeds 64 MiB)")
     ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configs (\"configs\": N = 1 only)")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling entries (\"strong\": config 4 / 5 over N ranks)")
     ap.add_argument("--configs-budget-s", type=float, default=75.0)
     return ap.parse_args()
+
+
+def dump_outputs(dirname, out, batch, h, w):
+    """What the caller of the timed path receives from the last step: the composed vectors and valid masks of its `batch`
+    pairs, as DIR/vecs.npy [batch][.., 2] and DIR/mask.npy [batch][..] (0 / 1), both float32.  Whole fields up to
+    DUMP_MAX_BYTES in all; above that the same seeded sample of DUMP_SAMPLE_PX / batch pixel indices (sorted, raster order)
+    from every field."""
+    from oflibnumpy_amd import _native as nat
+    lib = nat.load()
+    n = h * w
+    idx = None
+    if batch * n * 12 > DUMP_MAX_BYTES:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=max(1, DUMP_SAMPLE_PX // batch)))
+    vecs, mask = [], []
+    v = np.empty((n, 2), np.float32)
+    m = np.empty(n, np.uint8)
+    for j in range(batch):
+        nat.check(lib.ofl_download(v.ctypes.data, out.vecs.ptr + j * n * 8, n * 8, None))
+        nat.check(lib.ofl_download(m.ctypes.data, out.mask.ptr + j * n, n, None))
+        vecs.append(v.reshape(h, w, 2).copy() if idx is None else v[idx])
+        mask.append(m.reshape(h, w).astype(np.float32) if idx is None else m[idx].astype(np.float32))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "vecs.npy"), np.stack(vecs))
+    np.save(os.path.join(dirname, "mask.npy"), np.stack(mask))
 
 
 def main():
@@ -252,7 +289,8 @@ def main():
             print("rank {}: RCCL broadcast {}".format(rank, rccl_note), file=sys.stderr)
         if rccl_bad and rccl_note == "ok":
             rccl_note = "ok here, failed on another rank"
-    stat_rows = max(64, args.warmup + 65 * args.steps)            # flag words of every timed launch (<= 64 repeats of the K steps)
+    # flag words of every timed launch (<= 64 repeats of the K steps with --min-timed-ms)
+    stat_rows = max(64, args.warmup + (65 if args.min_timed_ms > 0 else 1) * args.steps)
     stats = None if args.no_stats else dev.DeviceBuffer.zeros(32 * B * stat_rows)
 
     ev0, ev1 = ctypes.c_void_p(), ctypes.c_void_p()
@@ -292,9 +330,9 @@ def main():
     if stats is not None:
         nat.check(lib.ofl_memset(stats.ptr, 0, stats.nbytes, None))
 
-    # The driver's --steps 20 is 6.5 ms of GPU time: too short for its own busy-sampling and at the mercy of one hiccup.  The
-    # K-step region is therefore repeated -- every repeat is EXACTLY K timed steps between barrier + synchronisation, after W
-    # warm-up steps before the first -- until >= --min-timed-ms have been timed, and the line reports the median repeat.
+    # EXACTLY K timed steps between barrier + synchronisation, after W warm-up steps.  With --min-timed-ms the K-step region is
+    # repeated (the same K steps, no further warm-up) until that much GPU time has been timed, and the line reports the
+    # median repeat.
     repeats = []
     first = 0
     while True:
@@ -311,10 +349,12 @@ def main():
     order = sorted(range(len(repeats)), key=lambda i: repeats[i][0])
     elapsed, kernel_ms = repeats[order[len(order) // 2]]
     total = first
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sets[(total - 1) % len(sets)][3], B, h, w)     # the last timed step's outputs
 
     # the predicates computed inside the timed launches: none of these synthetic flows is zero, so the
     # reference would not have taken an early exit on any step
-    if stats is not None:
+    if args.full and stats is not None:
         words = stats.to_host((min(total, stat_rows) * B, 8), np.uint32)
         assert words[:, [0, 1, 4, 5, 6, 7]].all(), "unexpected zero-flow predicate"
 
@@ -322,7 +362,7 @@ def main():
     # rotated by 30 degrees), "shift" = a 3.3-px translation as the sampling field
     algo_bytes = BYTES_PER_PX * h * w * B
     secondary = {}
-    if world == 1 and not args.no_secondary and PATTERN == "scale":
+    if args.full and world == 1 and not args.no_secondary and PATTERN == "scale":
         rot_sets = [(fb, fa, sign, out) for fa, fb, sign, out in sets]
         tr = of.Flow.from_transforms([['translation', 3.3, -2.7]], [h, w], ref)
         shift_sets = []
@@ -343,11 +383,11 @@ def main():
     log = lambda msg: print("[bench] " + msg, file=sys.stderr, flush=True)
     configs, strong = None, None
     sys.path.insert(0, os.path.join(ROOT, "tools"))
-    if world == 1 and not args.no_configs and (h, w) == (H, W) and PATTERN == "scale":
+    if args.full and world == 1 and not args.no_configs and (h, w) == (H, W) and PATTERN == "scale":
         # BASELINE configs 2 - 5 and the Delaunay-path cases on this GPU, rotating sets as the headline (tools/bench_ops.py)
         import bench_ops
         configs = bench_ops.collect(iters=12, budget_s=args.configs_budget_s, log=log)
-    if not args.no_strong and (h, w) == (H, W) and PATTERN == "scale":
+    if args.full and not args.no_strong and (h, w) == (H, W) and PATTERN == "scale":
         import bench_strong
         strong = bench_strong.run(of, dist, rank, world, comm_ok=(rccl_note == "ok" and rccl_bad == 0), log=log if rank == 0 else (lambda m: None))
     if rank == 0:
@@ -398,7 +438,7 @@ def main():
             line["configs"] = configs
         if strong is not None:
             line["strong"] = strong
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(h, w, ref)
         print(json.dumps(line), flush=True)
     if dist is not None:
