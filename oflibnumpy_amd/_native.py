@@ -134,7 +134,8 @@ def load():
                 got = lib.ofl_abi_version()
                 if got != ABI_VERSION:
                     # a stale build (the .so files are git-ignored and travel with the snapshot; OFL_LIB may point at an old
-                    # experiments build): same symbol names, shifted arguments -- refuse rather than call it
+                    # experiments build -- the product plus the OFL_DL_NEAR2_MIN test hook): same symbol names, shifted
+                    # arguments -- refuse rather than call it
                     raise ImportError("{} has ABI version {}, these bindings need {}: rebuild it with "
                                       "`python -m oflibnumpy_amd.build_native --force --experiments`".format(LIB_PATH, got, ABI_VERSION))
                 _lib = lib

@@ -4,9 +4,10 @@ hipcc cross-compiles without a GPU, so this also runs in the build container.  T
 git-ignored but travels to the GPU box with the repository snapshot.
 
 Two libraries come out of the same sources:
-  libofl_hip.so      the product: no environment knobs, no ablation probes, only the default kernels;
-  libofl_hip_exp.so  the EXPERIMENTS build (-DOFL_EXPERIMENTS): the A/B kernel variants, ablation probes and OFL_* tuning /
-                     test knobs.  Loaded only when OFL_LIB points at it (tools/, and the tests of the non-default routes).
+  libofl_hip.so      the product: reads no environment variable;
+  libofl_hip_exp.so  the EXPERIMENTS build (-DOFL_EXPERIMENTS): differs from the product only in reading OFL_DL_NEAR2_MIN, the
+                     test hook that sends small fields through the second per-thread star pass.  Loaded only when OFL_LIB
+                     points at it (test_near2_route_on_the_experiments_build).
 """
 import os
 import shutil

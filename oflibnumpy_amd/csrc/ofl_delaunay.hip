@@ -25,10 +25,6 @@
 // Everything is a pure function of the inputs (buckets are sorted by point index, far points are compacted in
 // index order, triangle ids derive from point indices), so row bands concatenate to the full result bit for bit.
 #include "ofl_scatter_dev.h"
-#ifdef OFL_EXPERIMENTS
-__device__ unsigned long long dl_dbg_counters[8];      // development counters of the geometry core (experiments build, OFL_DL_DEBUG prints them)
-#define DL_DBG(i, v) atomicAdd(&dl_dbg_counters[i], (unsigned long long)(v))
-#endif
 #include "ofl_delaunay_core.h"
 #include <algorithm>
 #include <limits>
@@ -44,10 +40,7 @@ namespace {
 
 constexpr int      kRings    = 6;        // bucket rings of the per-thread star pass
 constexpr int      kOpenRings = 2;       // ... of which a cell still unbounded after this many is handed on at once
-#ifndef OFL_NEAR_CAP
-#define OFL_NEAR_CAP 10
-#endif
-constexpr int      kNearCap  = OFL_NEAR_CAP;       // polygon capacity of the per-thread pass (float32 cell in LDS)
+constexpr int      kNearCap  = 10;       // polygon capacity of the per-thread pass (float32 cell in LDS)
 constexpr int      kSlots    = 16;       // neighbour slots per point
 constexpr int      kNear2Rings = 6;      // coarse rings of the second per-thread pass ...
 constexpr unsigned kNear2MinPoints = 32768;   // unfinished points below which the second per-thread pass is skipped
@@ -83,7 +76,7 @@ struct DlHead {                           // device header of the exact path (25
     Grid     grid, grid1;                    // fine buckets (all kept points), coarse buckets (unfinished points)
     unsigned kept, n_far, n_left, pool_used, err;    // err bit 0: far polygon overflow, bit 1: pool overflow, bit 2: big list overflow, bit 3: triangle-id space
     unsigned long long big_n;
-    unsigned n_todo;                                 // points the mesh-fan pass left to the clip pass (counted in debug runs only)
+    unsigned n_todo;                                 // points the mesh-fan pass left to the clip pass
     unsigned n_fan;                                  // points the mesh-cell pass left to the fan pass
     double   far_t2;                                 // squared distance beyond which a cell vertex counts as "far" (well outside the data)
     unsigned n_big;                                  // sorted entries that live in buckets of more than kDedupeSmall entries
@@ -94,7 +87,6 @@ struct DlHead {                           // device header of the exact path (25
     unsigned n_raster;                               // sites the site-wise raster looks at (stars of 1 .. kSlots neighbours outside the clean tiles)
     unsigned n_heavy;                                // buckets of more than kHeavy entries (dense clusters): they get grids of their own
     unsigned sub_used;                               // words of DlWs::sub_start handed out to those grids
-    unsigned dbg[8];                                 // experiments build: counters of the left-over pass (sites, chunks swept, steps, clips, seed/near/coarse clips)
 };
 static_assert(sizeof(DlHead) <= 256, "DlHead");
 static_assert(offsetof(DlHead, slab_stamp) == ofl_sc::kSlabStampAt, "ofl_scatter_dev.h: kSlabStampAt");
@@ -244,7 +236,7 @@ __host__ __device__ inline unsigned slab_stamp_of(int H, int W, int row0, int ro
 }
 
 __global__ __launch_bounds__(256)
-void dl_params_kernel(DlHead *head, unsigned long long bcap, double bucket_scale, int H, int W, int slab, int row0, int rows,
+void dl_params_kernel(DlHead *head, unsigned long long bcap, int H, int W, int slab, int row0, int rows,
                       const unsigned long long *__restrict__ partial, unsigned n_partial)
 {
     {   // the bounding box and the number of kept points from dl_bbox_kernel's records
@@ -286,7 +278,7 @@ void dl_params_kernel(DlHead *head, unsigned long long bcap, double bucket_scale
         const double bw = x1 - x0, bh = y1 - y0;
         // every point on one spot or on one axis-parallel line: nothing to triangulate (Qhull: "initial simplex is flat")
         if (n >= 3 && (!(okey_inv(head->kx1) > okey_inv(head->kx0)) || !(okey_inv(head->ky1) > okey_inv(head->ky0)))) atomicOr(&head->err, kErrDegenerate);
-        double s = bucket_scale * sqrt(fmax(bw * bh, 1e-300) / (double)n);             // ~bucket_scale^2 points per bucket
+        double s = sqrt(fmax(bw * bh, 1e-300) / (double)n);             // ~1 point per bucket
         s = fmax(s, (bw + bh) / (double)n);
         if (!(s > 0.0) || !isfinite(s)) s = 1.0;
         for (int it = 0; it < 64; ++it) {
@@ -869,11 +861,11 @@ void dl_star_fan_kernel(const float *__restrict__ flow, int sign, const uint8_t 
 // schedules for BASELINE config 5, whose source rows scatter over hundreds of buckets: one wave per 8 x 8 bucket tile -- half
 // empty waves, 24 -> 46 ms -- and a list compacted in bucket order -- no change: the pass is bound by the divergent clip
 // code of its 64 lanes, not by where the candidates come from.)
-#ifndef OFL_NEAR_WAVES
-#define OFL_NEAR_WAVES 5      // measured (product flags, same box): 4 waves per SIMD (116 VGPRs, cells of 12) config 5 22.88 ms, 5 waves (96 VGPRs + 9 spilled,
-#endif                        // cells of 10: 7 680 B of LDS per wave) 21.86 ms, 6 waves (80 + 18 spilled, cells of 8) 22.69 ms; cells of 10 at 4 waves: 22.90 ms
+// waves per SIMD of the per-thread pass, measured (product flags, same box): 4 waves per SIMD (116 VGPRs, cells of 12) config 5 22.88 ms, 5 waves (96 VGPRs + 9 spilled,
+// cells of 10: 7 680 B of LDS per wave) 21.86 ms, 6 waves (80 + 18 spilled, cells of 8) 22.69 ms; cells of 10 at 4 waves: 22.90 ms
+constexpr int kNearWaves = 5;
 template <bool HEAVY>       // false: every site of the list; true (a second launch, at once over when no bucket is heavy): the sites the first one marked kDegHeavy
-__global__ __launch_bounds__(64, HEAVY ? 1 : OFL_NEAR_WAVES)
+__global__ __launch_bounds__(64, HEAVY ? 1 : kNearWaves)
 void dl_star_near_kernel(const float *__restrict__ flow, int sign, const uint8_t *__restrict__ pmask, const unsigned char *__restrict__ dup, int H, int W,
                          const DlHead *__restrict__ head, const unsigned *__restrict__ todo,
                          const unsigned *__restrict__ bstart,
@@ -1184,7 +1176,6 @@ struct FarLds {
     unsigned run_lo[64];       // candidate runs of the current step (ranges of a sorted list) ...
     int    run_pre[65];        // ... and the exclusive prefix of their lengths
     int    n, a, ncut, nstart, status;
-    int    napply;             // cooperative clips applied to this cell so far (counted for the experiments build's debug line)
     // Candidate rejection: a site can only cut a vertex v if it is closer than 2 |v| to the cell's site.  Vertices well
     // outside the data (|v|^2 > t2: the box vertices of an unbounded cell, the circumcentres of sliver triangles along a
     // straight border) would make that radius useless, so they are listed and tested one by one; reach2 covers the rest.
@@ -1351,7 +1342,7 @@ __device__ void far_apply(FarLds<CAP, NT> &L, const P2 &C, int ctag, int ptag, R
             L.vx[m + 1] = v2.x; L.vy[m + 1] = v2.y; L.tag[m + 1] = tb;
         }
     }
-    if (t == 0) { L.n = n2; ++L.napply; }
+    if (t == 0) L.n = n2;
     __syncthreads();
     far_refresh(L);
 }
@@ -1711,18 +1702,13 @@ __device__ void far_point(FarLds<CAP, NT> &L, unsigned &s_off, unsigned li, unsi
     if (t == 0) {
         Poly P{ L.vx, L.vy, L.tag, 1, CAP, 0 };
         poly_init(P);
-        L.n = P.n; L.status = 0; L.t2 = head->far_t2; L.napply = 0;
+        L.n = P.n; L.status = 0; L.t2 = head->far_t2;
     }
     __syncthreads();
     far_refresh(L);
     far_seeds(L, p, pp, nbr, pos, rel);
     far_near_rows(L, p, pp, g, bstart, sorted, sorted_xy, rel);
     far_coarse_annulus(L, p, pp, -1, kMidRings, g1, b1start, sorted1_pt, sorted1_xy, rel);
-#ifdef OFL_EXPERIMENTS
-    __syncthreads();
-    const int dbg_before = L.napply;
-    unsigned dbg_chunks = 0;
-#endif
     // (Round 4 measured five more forms of this pass, each bit-identical in its results, none faster -- profiles/HISTORY.md: the
     // chunks nearest first with the box test repeated before every chunk (+ 2 .. 7 %); a chunk's 256 candidates in one round trip
     // under one vote (+ 15 .. 20 %); 5 and 6 waves per SIMD instead of 4 (no change); the sites in another order (no change);
@@ -1777,9 +1763,6 @@ __device__ void far_point(FarLds<CAP, NT> &L, unsigned &s_off, unsigned li, unsi
         for (int w = 0; w < NT / 64; ++w) { const unsigned c = (unsigned)__popcll(L.hit[w]); if (w < (t >> 6)) before += c; total += c; }
         if (keep) L.clist[before + (unsigned)__popcll(bal & ((1ull << (t & 63)) - 1ull))] = ck;
         __syncthreads();
-#ifdef OFL_EXPERIMENTS
-        dbg_chunks += total;
-#endif
         constexpr int kVote = NT == 64 ? 1 : 4;            // steps under one vote (a wave's own vote is cheap)
         constexpr int kPer = 256 / NT;                     // steps of NT candidates per chunk of 256
         for (unsigned k0 = 0; k0 < total * kPer; k0 += kVote) {
@@ -1799,25 +1782,14 @@ __device__ void far_point(FarLds<CAP, NT> &L, unsigned &s_off, unsigned li, unsi
         }
     }
     __syncthreads();
-#ifdef OFL_EXPERIMENTS
-    if (t == 0 && NT == 64) {
-        atomicAdd(&head->dbg[0], 1u); atomicAdd(&head->dbg[1], dbg_chunks); atomicAdd(&head->dbg[2], (unsigned)dbg_before);
-        atomicAdd(&head->dbg[3], (unsigned)(L.napply - dbg_before)); atomicAdd(&head->dbg[4], (unsigned)L.n);
-        atomicMax(&head->dbg[5], dbg_chunks); if (dbg_chunks > 12) atomicAdd(&head->dbg[6], 1u); atomicMax(&head->dbg[7], (unsigned)L.napply);
-    }
-#endif
     if (CAP < kFarCap && L.status) return;               // overflow of the small capacity: far_deg stays kDegLeft for the next pass
     far_store(L, rank, head, far_deg, far_off, pool, pool_cap, &s_off);
 }
 
-#ifndef OFL_FAR_WAVES
-#define OFL_FAR_WAVES 4
-#endif
-#ifndef OFL_FAR_CAP
-#define OFL_FAR_CAP 384
-#endif
+constexpr int kFarWaves = 4;        // waves per SIMD of the single-wave form
+constexpr int kFarSmallCap = 384;   // its cell capacity
 template <int CAP, int NT>          // first single waves with a small cell capacity, then -- for the few fans that overflowed it -- workgroups with the large one
-__global__ __launch_bounds__(NT, NT == 64 ? OFL_FAR_WAVES : 1)
+__global__ __launch_bounds__(NT, NT == 64 ? kFarWaves : 1)
 void dl_star_far_kernel(const float *__restrict__ flow, int sign, int H, int W, DlHead *head,
                         const unsigned *__restrict__ bstart, const unsigned *__restrict__ sorted, const P2 *__restrict__ sorted_xy,
                         const unsigned *__restrict__ b1start, const unsigned *__restrict__ sorted1_pt, const P2 *__restrict__ sorted1_xy,
@@ -2506,8 +2478,7 @@ int exact_stars(const float *flow, int sign_pp, const uint8_t *pmask, int H, int
     const dim3 bgrid((W + 31) / 32, std::max(1, std::min((H + 7) / 8, 4096 / ((W + 31) / 32) + 1)));
     unsigned long long *partial = (unsigned long long *)ws.pool;        // (the neighbour pool is free until the cooperative passes; 8 n + 65 536 words)
     hipLaunchKernelGGL(dl_bbox_kernel, bgrid, dim3(256), 0, s, flow, sign_pp, pmask, H, W, partial);
-    static const double bucket_scale = OFL_KNOB_DOUBLE("OFL_DL_BUCKET", 1.0);      // development knob (experiments build only)
-    hipLaunchKernelGGL(dl_params_kernel, dim3(1), dim3(256), 0, s, ws.head, (unsigned long long)ws.bcap, bucket_scale, H, W, slab ? 1 : 0, row0, rows,
+    hipLaunchKernelGGL(dl_params_kernel, dim3(1), dim3(256), 0, s, ws.head, (unsigned long long)ws.bcap, H, W, slab ? 1 : 0, row0, rows,
                        (const unsigned long long *)partial, bgrid.x * bgrid.y);
     OFL_HIP(hipMemsetAsync(ws.dup, 0, n, s));
     hipLaunchKernelGGL(dl_count_kernel, dim3(nblk), dim3(256), 0, s, flow, sign_pp, pmask, H, W, (const DlHead *)ws.head, ws.bstart, ws.dup,
@@ -2580,7 +2551,6 @@ int exact_finish(const float *flow, int sign_pp, int H, int W, int row0, int row
     const size_t n = (size_t)H * W;
     const unsigned nblk = (unsigned)((n + 255) / 256);
     const unsigned fblk = (unsigned)((n + kScanChunk - 1) / kScanChunk);
-    static const bool debug = OFL_KNOB_SET("OFL_DL_DEBUG");                      // development aid (experiments build only)
     // unfinished points in index order
     OFL_HIP(hipMemsetAsync(ws.cstate, 0, 2 * ws.cstride * 4, s));
     OFL_HIP(hipMemsetAsync(ws.cstate + 4 * ws.cstride, 0, ws.cstride * 4, s));
@@ -2622,7 +2592,7 @@ int exact_finish(const float *flow, int sign_pp, int H, int W, int row0, int row
         hipLaunchKernelGGL(dl_list_xy_kernel<2>, dim3(rblk), dim3(256), 0, s, flow, sign_pp, W,
                            (const DlHead *)ws.head, (const unsigned *)ws.left_idx, (const unsigned *)ws.far_idx, ws.left_xy, ws.left_pt);
         hipLaunchKernelGGL(dl_left_box_kernel, dim3(rblk), dim3(256), 0, s, (const DlHead *)ws.head, W, (const unsigned *)ws.left_pt, (const P2 *)ws.left_xy, ws.left_box);
-        hipLaunchKernelGGL((dl_star_far_kernel<OFL_FAR_CAP, 64>), dim3(walk), dim3(64), 0, s, flow, sign_pp, H, W, ws.head,
+        hipLaunchKernelGGL((dl_star_far_kernel<kFarSmallCap, 64>), dim3(walk), dim3(64), 0, s, flow, sign_pp, H, W, ws.head,
                            (const unsigned *)ws.bstart, (const unsigned *)ws.sorted, (const P2 *)ws.sorted_xy, (const unsigned *)ws.b1start,
                            (const unsigned *)ws.sorted1_pt, (const P2 *)ws.sorted1_xy, (const unsigned *)ws.far_idx, (const unsigned *)ws.left_idx,
                            (const unsigned *)ws.left_pt, (const P2 *)ws.left_xy, (const double *)ws.left_box, (const unsigned *)ws.nbr,
@@ -2646,26 +2616,11 @@ int exact_finish(const float *flow, int sign_pp, int H, int W, int row0, int row
     hipLaunchKernelGGL(dl_raster_big_kernel, dim3((unsigned)rt().n_cu * 4), dim3(256), 0, s, flow, sign_pp, H, W, ws, (unsigned)far_base);
     far_base_out = (unsigned)far_base;
     OFL_HIP(hipGetLastError());
-    if (info_host || debug) {
+    if (info_host) {
         DlHead h;
         OFL_HIP(hipMemcpyAsync(&h, ws.head, sizeof(h), hipMemcpyDeviceToHost, s));
         OFL_HIP(hipStreamSynchronize(s));
-        if (info_host) { info_host[0] = h.kept; info_host[1] = h.n_far; info_host[2] = h.n_left; }
-        if (debug) fprintf(stderr, "[ofl exact] kept %u, fan pass %u, clip pass %u, unfinished %u, left over %u\n", h.kept, h.n_fan, h.n_todo, h.n_far, h.n_left);
-#ifdef OFL_EXPERIMENTS
-        if (debug) {
-            unsigned long long c[8], z[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-            (void)hipMemcpyFromSymbol(c, HIP_SYMBOL(dl_dbg_counters), sizeof(c));
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(dl_dbg_counters), z, sizeof(z));
-            fprintf(stderr, "[ofl exact] heavy buckets %u (grid words %u): heavy runs %llu, candidates scanned in them %llu, cells given up %llu, heavy buckets without a grid %llu, grid rows walked %llu; ordinary runs: %llu candidates, %llu clip tests\n",
-                    h.n_heavy, h.sub_used, c[0], c[1], c[2], c[3], c[5], c[6], c[7]);
-        }
-#endif
-        if (debug && h.dbg[0]) fprintf(stderr, "[ofl exact] left-over pass: %u sites, per site %.1f chunks swept, %.1f clips before the sweep, %.1f clips in it, %.1f edges\n",
-                                       h.dbg[0], (double)h.dbg[1] / h.dbg[0], (double)h.dbg[2] / h.dbg[0], (double)h.dbg[3] / h.dbg[0], (double)h.dbg[4] / h.dbg[0]);
-        if (debug && h.dbg[0]) fprintf(stderr, "[ofl exact] left-over pass: most chunks swept by one site %u (of %u), sites with more than 12: %u, most clips of one site %u\n",
-                                       h.dbg[5], (h.n_left + 255) / 256, h.dbg[6], h.dbg[7]);
-        if (!info_host) return OFL_OK;
+        info_host[0] = h.kept; info_host[1] = h.n_far; info_host[2] = h.n_left;
         if (h.err) {
             // a capacity or degeneracy error leaves SOME stars rasterised: blank the owner map, so that the result is what
             // include/ofl.h promises for an error -- all zero, all invalid -- rather than a partial warp

@@ -25,10 +25,6 @@
 #define DL_HD inline
 #endif
 
-#ifndef DL_DBG
-#define DL_DBG(i, v)
-#endif
-
 namespace ofl_dl {
 
 struct P2 { double x, y; };
@@ -305,7 +301,6 @@ template <class PolyX, class PosFn>
 DL_HD int apply_range(PolyX &P, int p, const P2 &pp, unsigned lo, unsigned hi, const unsigned *sorted, const P2 *sorted_xy, PosFn pos, double &reach2)
 {
     auto rel = [&](int t) { const P2 q = pos(t); return P2{ q.x - pp.x, q.y - pp.y }; };
-    DL_DBG(1, hi - lo);
     for (unsigned j0 = lo; j0 < hi; j0 += 4) {
         int c4[4];
         P2  q4[4];                                           // four candidates' indices, then their positions, in flight together
@@ -343,12 +338,10 @@ int apply_heavy_run(PolyX &P, int p, const P2 &pp, int row, int x0, int x1, cons
                     const unsigned *sorted, const P2 *sorted_xy, PosFn pos, double &reach2, const SubGrids &sub, unsigned *budget)
 {
     const bool give_up = budget != nullptr;
-    DL_DBG(0, 1);
     for (int bx = x0; bx <= x1; ++bx) {
         const size_t b = (size_t)row * g.gx + bx;
         const unsigned lo = bstart[b], hi = bstart[b + 1];
         const int h = hi - lo > kHeavy ? find_heavy(sub, (unsigned)b) : -1;
-        if (hi - lo > kHeavy && h < 0) DL_DBG(3, 1);
         if (h < 0) { if (apply_range(P, p, pp, lo, hi, sorted, sorted_xy, pos, reach2) < 0) return -1; continue; }
         const SubGrid sg = sub.info[h];
         const Grid &q = sg.g;
@@ -362,7 +355,6 @@ int apply_heavy_run(PolyX &P, int p, const P2 &pp, int row, int x0, int x1, cons
         const int rmax = ax > ay ? ax : ay;
         for (int r = 0; r <= rmax; ++r) {
             for (int yy = sy - r; yy <= sy + r; ++yy) {
-                DL_DBG(5, 1);
                 if (yy < 0 || yy >= q.gy) continue;
                 const bool full = yy == sy - r || yy == sy + r;
                 for (int part = 0; part < (full ? 1 : 2); ++part) {
@@ -384,7 +376,7 @@ int apply_heavy_run(PolyX &P, int p, const P2 &pp, int row, int x0, int x1, cons
             // and a rim cell does not close within the rings anyway.  A cell that has looked at more than kHeavyBudget sites
             // of heavy buckets (an interior site of a cluster needs a few hundred) is given up (1: the caller hands it on
             // unfinished, with the edges found so far as seeds): the cooperative passes scan clusters 64 sites at a time.
-            if (give_up && *budget > kHeavyBudget) { DL_DBG(2, 1); return 1; }
+            if (give_up && *budget > kHeavyBudget) return 1;
         }
     }
     return 0;
@@ -398,10 +390,8 @@ int apply_heavy_run(PolyX &P, int p, const P2 &pp, int row, int x0, int x1, cons
 // HEAVY = false (the passes every field runs): a run that may hold a heavy bucket is not touched -- 2 is returned and the caller
 // leaves the star to the HEAVY instantiation (a launch of its own, only for such sites): the few hundred lines of the heavy search,
 // a call that is not inlined and a polygon whose address escapes cost the ordinary clip pass half its speed when they sat in it.
+constexpr int kRingW = 4;          // candidates apply_ring has in flight together
 template <bool HEAVY = false, class PolyX, class PosFn>
-#ifndef OFL_RING_W
-#define OFL_RING_W 4
-#endif
 DL_HD int apply_ring(PolyX &P, int p, const P2 &pp, int bx, int by, int r, const Grid &g,
                      const unsigned *bstart, const unsigned *sorted, PosFn pos, double &reach2,
                      const P2 *sorted_xy = nullptr,          // positions in `sorted` order (one contiguous read per run) or null
@@ -446,35 +436,34 @@ DL_HD int apply_ring(PolyX &P, int p, const P2 &pp, int bx, int by, int r, const
         }
         unsigned nlo = 0, nhi = 0;
         if (seg + 1 < nseg) bounds(seg + 1, nlo, nhi);
-        DL_DBG(6, hi - lo);
-        for (unsigned j = lo; j < hi; j += OFL_RING_W) {
+        for (unsigned j = lo; j < hi; j += kRingW) {
             // a few candidates at a time: their indices, then their positions, are in flight together
-            int c[OFL_RING_W];
-            P2  q[OFL_RING_W];
+            int c[kRingW];
+            P2  q[kRingW];
             if (sorted_xy) {
                 // With the positions stored in list order both loads depend on the list position alone: asked for unconditionally, at a
                 // clamped position, ALL of them leave before the first is looked at.  (A load inside a branch is waited for where it
                 // stands, and left alone the compiler sinks each candidate's loads to its use behind the previous candidate's clip:
                 // a batch of four candidates was five round trips, not one.  The empty asm pins the raw values here.)
-                int ck[OFL_RING_W];
+                int ck[kRingW];
 #ifdef __HIPCC__
 #pragma unroll
 #endif
-                for (int k = 0; k < OFL_RING_W; ++k) {
+                for (int k = 0; k < kRingW; ++k) {
                     const unsigned jj = j + k < hi ? j + k : hi - 1;
                     ck[k] = (int)sorted[jj];
                     q[k] = sorted_xy[jj];
                 }
 #ifdef __HIP_DEVICE_COMPILE__
 #pragma unroll
-                for (int k = 0; k < OFL_RING_W; ++k) asm volatile("" : "+v"(ck[k]), "+v"(q[k].x), "+v"(q[k].y));
+                for (int k = 0; k < kRingW; ++k) asm volatile("" : "+v"(ck[k]), "+v"(q[k].x), "+v"(q[k].y));
 #endif
 #ifdef __HIPCC__
 #pragma unroll
 #endif
-                for (int k = 0; k < OFL_RING_W; ++k) c[k] = j + k < hi ? ck[k] : -1;
+                for (int k = 0; k < kRingW; ++k) c[k] = j + k < hi ? ck[k] : -1;
             } else {
-                for (int k = 0; k < OFL_RING_W; ++k) {
+                for (int k = 0; k < kRingW; ++k) {
                     c[k] = j + k < hi ? (int)sorted[j + k] : -1;
                     q[k] = c[k] >= 0 ? pos(c[k]) : pp;
                 }
@@ -482,12 +471,11 @@ DL_HD int apply_ring(PolyX &P, int p, const P2 &pp, int bx, int by, int r, const
 #ifdef __HIPCC__
 #pragma unroll
 #endif
-            for (int k = 0; k < OFL_RING_W; ++k) {
+            for (int k = 0; k < kRingW; ++k) {
                 if (c[k] < 0 || c[k] == p) continue;
                 const P2 C = { q[k].x - pp.x, q[k].y - pp.y };
                 const double d2 = C.x * C.x + C.y * C.y;
                 if (d2 == 0.0 || d2 >= reach2) continue;      // a duplicate of p (same cell), or too far to matter
-                DL_DBG(7, 1);
                 const int rc = poly_clip(P, C, c[k], p, rel);
                 if (rc < 0) return -1;
                 if (rc > 0) reach2 = 4.0 * poly_rmax2(P);

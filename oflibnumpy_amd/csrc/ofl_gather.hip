@@ -80,13 +80,7 @@ __device__ __forceinline__ uint32_t c3_spread16(uint32_t x)
 // x = 2*lx and x = 64 + 2*lx of its tile row, so that every stream instruction of a wave covers
 // contiguous memory (32 lanes x 16 B = 512 B of vectors, 32 lanes x 2 B = 64 B of mask per row):
 // no half-filled 64-byte requests on either the read or the write side.
-#ifndef OFL_C3_LANES_X
-#define OFL_C3_LANES_X 32            // lanes along x per tile row (16 / 32 / 64): tile = 4*LX px x 256/LX rows
-#endif
-#ifndef OFL_C3_NT
-#define OFL_C3_NT 3                  // experiment knob: 1 = non-temporal stores, 2 = non-temporal stream loads
-#endif
-constexpr int kC3LanesX = OFL_C3_LANES_X;
+constexpr int kC3LanesX = 32;      // lanes along x per tile row: tile = 4*LX px x 256/LX rows
 constexpr int kC3TileW = 4 * kC3LanesX, kC3TileH = 256 / kC3LanesX, kC3Px = 4;
 
 struct C3Pos {            // what must stay live while the gather is in flight
@@ -167,17 +161,7 @@ struct C3Args {
     int sign, H, W, tiles_x, tiles_per_field, ntiles;
     float th;
     int mwpr;              // BITS kernels: 32-bit words per row of the packed mask planes ma / mb / mout (bit x & 31 of word x >> 5); else 0
-    int swz_group;         // default kernel: tile rows one XCD owns per group (<= 1: natural order); one-shot variant: workgroups per XCD-swizzle group
-    int xpose_rows;        // transposed-gather kernel: source rows a streamed 128-px segment may cross on the direct path
-#ifdef OFL_EXPERIMENTS
-    int ablate;            // OFL_C3_ABLATE (experiments build only): 1 = skip the gather, 2 = skip the stores, ...
-#endif
 };
-#ifdef OFL_EXPERIMENTS
-#define OFL_ABLATE(a, bit) (((a).ablate & (bit)) != 0)
-#else
-#define OFL_ABLATE(a, bit) false
-#endif
 
 struct C3Stream {          // one lane's share of a tile row of the streamed field fb/mb
     float4   v[2];
@@ -188,48 +172,37 @@ struct C3Stat {            // running maxima for the zero-flow predicates of one
     float amax_m, bmax, bmax_m;
 };
 
-// LX = lanes along x per tile row: tile = 4*LX px wide, 256/LX rows high; lane (lx, ly) owns the pixel
-// pairs at x = 2*lx and x = 2*LX + 2*lx.
-template <int LX>
+// lane (lx, ly) owns the pixel pairs at x = 2*lx and x = 2*kC3LanesX + 2*lx of tile row ly
 __device__ __forceinline__ void c3_tile_coords(const C3Args &a, int tile, int &b, int &y, int (&xg)[2])
 {
     b = tile / a.tiles_per_field;
     const int t  = tile - b * a.tiles_per_field;
     const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
-    y = ty * (256 / LX) + (threadIdx.x / LX);
-    xg[0] = tx * (4 * LX) + 2 * (threadIdx.x % LX);
-    xg[1] = xg[0] + 2 * LX;
+    y = ty * kC3TileH + (threadIdx.x / kC3LanesX);
+    xg[0] = tx * kC3TileW + 2 * (threadIdx.x % kC3LanesX);
+    xg[1] = xg[0] + 2 * kC3LanesX;
 }
 
-template <int LX, bool BITS = false>
+template <bool BITS = false>
 __device__ __forceinline__ C3Stream c3_load_stream(const C3Args &a, int tile)
 {
     int b, y, xg[2];
-    c3_tile_coords<LX>(a, tile, b, y, xg);
+    c3_tile_coords(a, tile, b, y, xg);
     const size_t base = (size_t)b * a.H * a.W + (size_t)y * a.W;
     C3Stream s;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
         s.v[g] = make_float4(0.f, 0.f, 0.f, 0.f);
         s.m[g] = 0;
-        if (BITS) {
-            if (y < a.H && xg[g] < a.W) {
-                const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(a.fb + 2 * (base + xg[g])));
-                s.v[g] = make_float4(t.x, t.y, t.z, t.w);
+        if (y < a.H && xg[g] < a.W) {
+            const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(a.fb + 2 * (base + xg[g])));
+            s.v[g] = make_float4(t.x, t.y, t.z, t.w);
+            if (BITS) {
                 // the pair's two bits (xg is even: both in one word; the 16 lanes of a word read the same address)
                 const uint32_t w = reinterpret_cast<const uint32_t *>(a.mb)[((size_t)b * a.H + y) * a.mwpr + (xg[g] >> 5)] >> (xg[g] & 31);
                 s.m[g] = (w & 1u) | ((w & 2u) << 7);
-            }
-            continue;
-        }
-        if (y < a.H && xg[g] < a.W) {
-            if (OFL_C3_NT & 2) {
-                const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(a.fb + 2 * (base + xg[g])));
-                s.v[g] = make_float4(t.x, t.y, t.z, t.w);
-                s.m[g] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(a.mb + base + xg[g]));
             } else {
-                s.v[g] = *reinterpret_cast<const float4 *>(a.fb + 2 * (base + xg[g]));
-                s.m[g] = *reinterpret_cast<const uint16_t *>(a.mb + base + xg[g]);
+                s.m[g] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(a.mb + base + xg[g]));
             }
         }
     }
@@ -295,28 +268,20 @@ __device__ __forceinline__ void c3_finish(const C3Args &a, size_t row, const int
     }
     // Mask bytes leave as DWORDS when the row length allows aligned ones: the lane pairs (2k, 2k + 1) own four consecutive
     // pixels, the even lane stores both lanes' bytes (sub-dword stores cost as much per instruction as 16-byte ones)
-    const bool quad = (a.W & 3) == 0 && !OFL_ABLATE(a, 64);
+    const bool quad = (a.W & 3) == 0;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
         const int jj = 2 * g;
         const uint32_t mine = ((ok[jj] && bm[jj]) ? 1u : 0u) | ((ok[jj + 1] && bm[jj + 1]) ? 0x100u : 0u);
         const uint32_t other = (uint32_t)__shfl_xor((int)mine, 1);
-        if (act[g] && !(OFL_ABLATE(a, 2) && su[2 * g] != 12345.0f)) {
+        if (act[g]) {
             const int j = 2 * g;
-            const float4 o4 = make_float4(__fadd_rn(bu[j], su[j]), __fadd_rn(bv[j], sv[j]),
-                                          __fadd_rn(bu[j + 1], su[j + 1]), __fadd_rn(bv[j + 1], sv[j + 1]));
-            const uint16_t mo = (uint16_t)mine;
-            if (OFL_C3_NT & 1) {
-                const v4f t = { o4.x, o4.y, o4.z, o4.w };
-                __builtin_nontemporal_store(t, reinterpret_cast<v4f *>(a.out + 2 * (row + xg[g])));
-                if (quad) {
-                    if ((threadIdx.x & 1) == 0) __builtin_nontemporal_store(mine | (other << 16), reinterpret_cast<uint32_t *>(a.mout + row + xg[g]));
-                } else {
-                    __builtin_nontemporal_store(mo, reinterpret_cast<uint16_t *>(a.mout + row + xg[g]));
-                }
+            const v4f t = { __fadd_rn(bu[j], su[j]), __fadd_rn(bv[j], sv[j]), __fadd_rn(bu[j + 1], su[j + 1]), __fadd_rn(bv[j + 1], sv[j + 1]) };
+            __builtin_nontemporal_store(t, reinterpret_cast<v4f *>(a.out + 2 * (row + xg[g])));
+            if (quad) {
+                if ((threadIdx.x & 1) == 0) __builtin_nontemporal_store(mine | (other << 16), reinterpret_cast<uint32_t *>(a.mout + row + xg[g]));
             } else {
-                *reinterpret_cast<float4 *>(a.out + 2 * (row + xg[g])) = o4;
-                *reinterpret_cast<uint16_t *>(a.mout + row + xg[g]) = mo;
+                __builtin_nontemporal_store((uint16_t)mine, reinterpret_cast<uint16_t *>(a.mout + row + xg[g]));
             }
             if (STATS) {
                 const float a0 = fmaxf(fabsf(bu[j]), fabsf(bv[j])), a1 = fmaxf(fabsf(bu[j + 1]), fabsf(bv[j + 1]));
@@ -332,7 +297,7 @@ template <int QUANT, bool STATS, bool BITS = false>
 __device__ __forceinline__ void c3_tile(const C3Args &a, int tile, const C3Stream &in, C3Stat &st)
 {
     int b, y, xg[2];
-    c3_tile_coords<kC3LanesX>(a, tile, b, y, xg);
+    c3_tile_coords(a, tile, b, y, xg);
     const int H = a.H, W = a.W, sign = a.sign;
     const size_t field = (size_t)b * H * W;
     const float   *fa = a.fa + field * 2;
@@ -357,7 +322,6 @@ __device__ __forceinline__ void c3_tile(const C3Args &a, int tile, const C3Strea
         outside = outside && (out_j || !act[j >> 1]);
     }
     if (H < 2) inside = false;
-    if (OFL_ABLATE(a, 1)) outside = true;
 
     float su[kC3Px], sv[kC3Px];
     bool  ok[kC3Px];
@@ -378,13 +342,12 @@ __device__ __forceinline__ void c3_tile(const C3Args &a, int tile, const C3Strea
         for (int g = 0; g < 2; ++g)
             share = share && (!act[g] || (tp[2 * g].iy == tp[2 * g + 1].iy && (unsigned)(tp[2 * g + 1].ix - tp[2 * g].ix) <= 2u &&
                                           tp[2 * g].ix + 3 < W));
-        share = __all(share) && !OFL_ABLATE(a, 32);
+        share = __all(share);
 #pragma unroll
         for (int j = 0; j < kC3Px; ++j) {
             const size_t s0 = act[j >> 1] ? (size_t)tp[j].iy * W + tp[j].ix : 0;
             p0[j] = *reinterpret_cast<const Pair2 *>(fa + 2 * s0);
             p1[j] = *reinterpret_cast<const Pair2 *>(fa + 2 * (s0 + W));
-            if (OFL_ABLATE(a, 16)) { m0[j] = 0x0101u; m1[j] = 0x0101u; continue; }       // TA-cost probe: no mask gathers
             if (BITS) {
                 // bits 0 / 1 = taps ix / ix + 1 (bits 2, 3 serve the pair's other pixel when it shares the load)
                 if (share && (j & 1)) {
@@ -457,131 +420,8 @@ __device__ __forceinline__ void c3_tile(const C3Args &a, int tile, const C3Strea
     c3_finish<STATS, BITS>(a, row, xg, act, bu, bv, bm, su, sv, ok, st);
 }
 
-#ifndef OFL_C3_ONESHOT_WAVES
-#define OFL_C3_ONESHOT_WAVES 6       // waves per SIMD the register allocator is asked to leave room for
-#endif
-
-#ifdef OFL_EXPERIMENTS   // ---- non-default compose variants (OFL_C3_VARIANT = 0 / 2): measured, kept for A/B runs only
-// Persistent form: gridDim.x workgroups (a multiple of 8, sized to the chip's residency) walk the tile
-// list with stride gridDim.x.  The stream loads of the NEXT tile are issued before the gathers of the
-// current one are consumed, which takes the fb round trip out of every tile's dependency chain
-// (load fb -> addresses -> gather -> store), and the launch pays one ramp-up / tail instead of one per
-// resident-set of workgroups.  At every step the workgroups of one XCD (blockIdx % 8) own a contiguous
-// run of tiles, so neighbouring tiles share gather halos in that XCD's L2.
-#ifndef OFL_C3_PREFETCH
-#define OFL_C3_PREFETCH 1            // tiles of stream data kept in flight ahead of the one being gathered (1 or 2)
-#endif
-
-template <int QUANT, bool STATS>
-__global__ __launch_bounds__(256)
-void compose3_kernel(const C3Args a)
-{
-    const int nb  = gridDim.x;
-    const int per = nb >> 3;
-    const int lane_tile = ((nb & 7) == 0 && a.swz_group != 0) ? (blockIdx.x & 7) * per + (blockIdx.x >> 3) : blockIdx.x;
-    int tile = lane_tile;
-    if (tile >= a.ntiles) return;
-    C3Stat st = { 0.0f, 0.0f, 0.0f };
-    int cur_b = tile / a.tiles_per_field;
-    C3Stream in = c3_load_stream<kC3LanesX>(a, tile);
-#if OFL_C3_PREFETCH == 2
-    C3Stream in2;
-    if (tile + nb < a.ntiles) in2 = c3_load_stream<kC3LanesX>(a, tile + nb);
-#endif
-    while (true) {
-        const int next = tile + nb;
-        const bool more = next < a.ntiles;
-        C3Stream nxt;
-#if OFL_C3_PREFETCH == 2
-        if (next + nb < a.ntiles) nxt = c3_load_stream<kC3LanesX>(a, next + nb);   // two tiles ahead
-#else
-        if (more) nxt = c3_load_stream<kC3LanesX>(a, next);          // prefetch: in flight during this tile's gather
-#endif
-        c3_tile<QUANT, STATS>(a, tile, in, st);
-        if (!more) break;
-        if (STATS) {
-            const int nb_ = next / a.tiles_per_field;
-            if (nb_ != cur_b) {
-                c3_flush_stats(a, cur_b, st);
-                st.amax_m = st.bmax = st.bmax_m = 0.0f;
-                cur_b = nb_;
-            }
-        }
-#if OFL_C3_PREFETCH == 2
-        in = in2;
-        in2 = nxt;
-#else
-        in = nxt;
-#endif
-        tile = next;
-    }
-    if (STATS) c3_flush_stats(a, cur_b, st);
-}
-
-// One workgroup per tile (no persistence, no prefetch): the hardware dispatcher keeps every wave slot
-// filled and the active tiles form a window that sweeps memory in order.
-template <int QUANT, bool STATS>
-__global__ __launch_bounds__(256, OFL_C3_ONESHOT_WAVES)
-void compose3_oneshot_kernel(const C3Args a)
-{
-    // XCD-aware tile order inside groups of a.swz_group workgroups: the 8 XCDs sweep ONE window of memory
-    // together, each owning a contiguous eighth of it (neighbouring tiles share gather halos in one L2)
-    int tile = blockIdx.x;
-    if (a.swz_group > 0) {
-        const int g = blockIdx.x / a.swz_group, r = blockIdx.x - g * a.swz_group;
-        const int size = min(a.swz_group, (int)gridDim.x - g * a.swz_group);
-        tile = g * a.swz_group + xcd_swizzle(r, size);
-    }
-    if (tile >= a.ntiles) return;
-    C3Stat st = { 0.0f, 0.0f, 0.0f };
-    const C3Stream in = c3_load_stream<kC3LanesX>(a, tile);
-    c3_tile<QUANT, STATS>(a, tile, in, st);
-    if (STATS) c3_flush_stats(a, tile / a.tiles_per_field, st);
-}
-#endif  // OFL_EXPERIMENTS
-
-#ifdef OFL_EXPERIMENTS   // ---- LDS-staged compose variant (OFL_C3_VARIANT = 1)
-// ------------------------------------------------------------------------------------ K2, LDS-staged form
-// The direct form above fetches 36 B per output pixel through the texture path (two unaligned 16-byte
-// gathers + two 2-byte mask gathers) and its row-strip tiles lose L1 locality when the sampling grid is
-// rotated.  Here a workgroup owns a compact 32 x 32 output tile, finds the bounding box of its sample
-// positions (wave shuffles + 4 LDS atomics per wave), stages that source rectangle ONCE with coalesced,
-// aligned 16-byte row loads into LDS as {u, v, mask, -} quads, and reads the taps with ds_read_b128.
-// Texture-path bytes per pixel drop to 9 (stream) + ~9 x (source px per output px), independent of the
-// rotation of the sampling grid.  Tiles whose footprint does not fit the LDS budget use the direct path.
-#ifndef OFL_LDS_LX
-#define OFL_LDS_LX 8
-#endif
-#ifndef OFL_LDS_CAP
-#define OFL_LDS_CAP 2400
-#endif
-constexpr int kLdsLX  = OFL_LDS_LX;   // 8 lanes x 4 px = 32 px wide, 32 rows (16 -> 64 x 16)
-constexpr int kLdsCap = OFL_LDS_CAP;  // staged source pixels per workgroup (16 B each; 2400 = 37.5 KB -> 4 workgroups / CU)
-
-// Wave-wide min / max on the VALU with DPP row shifts and row broadcasts (gfx9 reduction idiom): four
-// row_shr steps leave each 16-lane row's result in its last lane, row_bcast:15 / row_bcast:31 carry it
-// across rows; lane 63 ends up with the wave's result.  No LDS traffic, no dependent ds_bpermute chain.
-template <bool IS_MIN>
-__device__ __forceinline__ int wave_minmax(int v)
-{
-#define OFL_DPP_STEP(CTRL, ROWMASK)                                                        \
-    {                                                                                      \
-        const int t = __builtin_amdgcn_update_dpp(v, v, CTRL, ROWMASK, 0xf, false);        \
-        v = IS_MIN ? min(v, t) : max(v, t);                                                \
-    }
-    OFL_DPP_STEP(0x111, 0xf)    // row_shr:1
-    OFL_DPP_STEP(0x112, 0xf)    // row_shr:2
-    OFL_DPP_STEP(0x114, 0xf)    // row_shr:4
-    OFL_DPP_STEP(0x118, 0xf)    // row_shr:8
-    OFL_DPP_STEP(0x142, 0xa)    // row_bcast:15 into rows 1 and 3
-    OFL_DPP_STEP(0x143, 0xc)    // row_bcast:31 into rows 2 and 3
-#undef OFL_DPP_STEP
-    return __builtin_amdgcn_readlane(v, 63);
-}
-#endif  // OFL_EXPERIMENTS
-
 // ---------------------------------------------------------------------------------------------------------
-// K2, transposed-gather form (variant 3).  The streaming layout (a wave = 2 rows x 128 px) is what the stream loads
+// K2, transposed-gather form.  The streaming layout (a wave = 2 rows x 128 px) is what the stream loads
 // and stores want, but when the sampling grid is ROTATED each gather instruction of such a wave touches 60+ cache
 // lines (one per source row its 128-px segment crosses): the texture cache's tag look-ups, not HBM, bound the
 // kernel (rocprofv3: 2.75 x the cache accesses of the axis-aligned case).  Workgroups that see such a field hand
@@ -590,7 +430,6 @@ __device__ __forceinline__ int wave_minmax(int v)
 // per pixel, bit-identical results; axis-aligned fields keep the direct path.
 constexpr int kXpRowF2 = 128 + 4;             // LDS row stride in float2 (padding spreads the 8 rows over the banks)
 constexpr int kXposeRows = 6;                 // source rows one streamed 128-px segment may cross before we transpose
-constexpr int kC3XcdRows = 1;                 // vertically adjacent tiles one XCD owns per dispatch group (1 = natural tile order)
 
 template <int QUANT, bool STATS, bool BITS = false>
 __device__ __forceinline__ void c3_sample_block(const C3Args &a, const float *__restrict__ fa, const uint8_t *__restrict__ ma,
@@ -672,37 +511,21 @@ __device__ __forceinline__ void c3_sample_block(const C3Args &a, const float *__
     }
 }
 
-#ifndef OFL_C3_BITS_WAVES
-#define OFL_C3_BITS_WAVES 5          // the packed-mask form needs a few registers more than the 6-wave budget leaves (11 spilled there)
-#endif
+constexpr int kC3Waves = 6;                   // waves per SIMD the register allocator is asked to leave room for
+constexpr int kC3BitsWaves = 5;               // the packed-mask form needs a few registers more than the 6-wave budget leaves (11 spilled there)
 template <int QUANT, bool STATS, bool BITS = false>      // BITS: the three masks are packed bit planes (ofl_compose3_bits_dev)
-__global__ __launch_bounds__(256, BITS ? OFL_C3_BITS_WAVES : OFL_C3_ONESHOT_WAVES)
+__global__ __launch_bounds__(256, BITS ? kC3BitsWaves : kC3Waves)
 void compose3_xpose_kernel(const C3Args a)
 {
     static_assert(kC3LanesX == 32, "the transposed form assumes 128 x 8 tiles");
     __shared__ __attribute__((aligned(16))) float2 xp_v[8 * kXpRowF2];
     __shared__ __attribute__((aligned(16))) uint8_t xp_ok[8 * 128];
-    // Block -> tile.  Workgroups are dealt round-robin over the 8 XCDs (block b runs on XCD b % 8), each with its own L2.
-    // In natural tile order the tile BELOW a tile is tiles_x blocks later and on another XCD, so the source rows the two
-    // share (bilinear halo; for a rotated sampling grid most of their cache lines) are fetched once per XCD.  With
-    // swz_group = R > 1 a group of 8 R consecutive blocks covers 8 tile columns x R tile rows and XCD x owns column x of
-    // it: R vertically adjacent tiles, dispatched 8 blocks apart, meet in ONE L2 -- while all XCDs still sweep the same
-    // window of memory (whole-field contiguous runs per XCD were measured slower).
-    int tile = blockIdx.x;
-    if (a.swz_group > 1) {
-        const int R = a.swz_group, per = 8 * R;
-        const int g = blockIdx.x / per, i = blockIdx.x - g * per;
-        const int tiles_y = a.tiles_per_field / a.tiles_x, n_gx = (a.tiles_x + 7) >> 3, n_gy = (tiles_y + R - 1) / R;
-        const int fld = g / (n_gx * n_gy), gg = g - fld * (n_gx * n_gy), gy = gg / n_gx, gx = gg - gy * n_gx;
-        const int ty = gy * R + (i >> 3), tx = gx * 8 + (i & 7);
-        if (tx >= a.tiles_x || ty >= tiles_y) return;
-        tile = fld * a.tiles_per_field + ty * a.tiles_x + tx;
-    }
+    const int tile = blockIdx.x;          // natural tile order (XCD-aware orders were measured slower)
     if (tile >= a.ntiles) return;
     C3Stat st = { 0.0f, 0.0f, 0.0f };
-    const C3Stream in = c3_load_stream<kC3LanesX, BITS>(a, tile);
+    const C3Stream in = c3_load_stream<BITS>(a, tile);
     int b, y, xg[2];
-    c3_tile_coords<kC3LanesX>(a, tile, b, y, xg);
+    c3_tile_coords(a, tile, b, y, xg);
     const int H = a.H, W = a.W;
     const bool act[2] = { y < H && xg[0] < W, y < H && xg[1] < W };
     // Does a streamed row segment of this tile cross many source rows (sample row = y -/+ v)?  Every wave answers from
@@ -714,7 +537,7 @@ void compose3_xpose_kernel(const C3Args a)
     {
         const int x0 = tx * 128, x1 = min(x0 + 127, W - 1), yy = min(ty * 8, H - 1);
         const float *frow = a.fb + 2 * ((size_t)b * H * W + (size_t)yy * W);
-        rotated = fabsf(frow[2 * x1 + 1] - frow[2 * x0 + 1]) * 128.0f > (float)(a.xpose_rows * (x1 - x0 + 1));
+        rotated = fabsf(frow[2 * x1 + 1] - frow[2 * x0 + 1]) * 128.0f > (float)(kXposeRows * (x1 - x0 + 1));
     }
     if (!rotated) {
         c3_tile<QUANT, STATS, BITS>(a, tile, in, st);
@@ -765,163 +588,6 @@ void compose3_xpose_kernel(const C3Args a)
     }
     if (STATS) c3_flush_stats(a, tile / a.tiles_per_field, st);
 }
-
-#ifdef OFL_EXPERIMENTS
-template <int QUANT, bool STATS>
-__device__ __forceinline__ void c3_tile_lds(const C3Args &a, int tile, const C3Stream &in, C3Stat &st,
-                                            float4 *lds, int *box_now, int *box_next)
-{
-    int b, y, xg[2];
-    c3_tile_coords<kLdsLX>(a, tile, b, y, xg);
-    const int H = a.H, W = a.W, sign = a.sign;
-    const size_t field = (size_t)b * H * W;
-    const float   *fa = a.fa + field * 2;
-    const uint8_t *ma = a.ma + field;
-    const bool act[2] = { y < H && xg[0] < W, y < H && xg[1] < W };
-    const size_t row = field + (size_t)y * W;
-
-    const float bu[kC3Px] = { in.v[0].x, in.v[0].z, in.v[1].x, in.v[1].z };
-    const float bv[kC3Px] = { in.v[0].y, in.v[0].w, in.v[1].y, in.v[1].w };
-    const bool  bm[kC3Px] = { (in.m[0] & 0xffu) != 0, (in.m[0] & 0xff00u) != 0,
-                              (in.m[1] & 0xffu) != 0, (in.m[1] & 0xff00u) != 0 };
-
-    // ---- sample positions and this lane's share of the footprint
-    C3Pos tp[kC3Px];
-    bool  use[kC3Px];
-    int bx0 = 0x7fffffff, by0 = 0x7fffffff, bx1 = -0x7fffffff, by1 = -0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < kC3Px; ++j) {
-        tp[j] = c3_pos<QUANT>(xg[j >> 1] + (j & 1), y, bu[j], bv[j], sign);
-        const bool out_j = tp[j].ix < -1 || tp[j].ix >= W || tp[j].iy < -1 || tp[j].iy >= H;
-        use[j] = act[j >> 1] && !out_j && !OFL_ABLATE(a, 1);
-        if (use[j]) {
-            bx0 = min(bx0, max(tp[j].ix, 0));     bx1 = max(bx1, min(tp[j].ix + 1, W - 1));
-            by0 = min(by0, max(tp[j].iy, 0));     by1 = max(by1, min(tp[j].iy + 1, H - 1));
-        }
-    }
-    bx0 = wave_minmax<true>(bx0);  by0 = wave_minmax<true>(by0);
-    bx1 = wave_minmax<false>(bx1); by1 = wave_minmax<false>(by1);
-    if ((threadIdx.x & 63) == 0 && bx1 >= bx0) {
-        atomicMin(&box_now[0], bx0); atomicMin(&box_now[1], by0);
-        atomicMax(&box_now[2], bx1); atomicMax(&box_now[3], by1);
-    }
-    __syncthreads();                                                   // A: footprint complete
-    const int X0 = box_now[0] & ~1, Y0 = box_now[1], X1 = box_now[2], Y1 = box_now[3];
-    if (threadIdx.x == 0) {                                            // re-arm the other box for the next tile
-        box_next[0] = 0x7fffffff; box_next[1] = 0x7fffffff; box_next[2] = -0x7fffffff; box_next[3] = -0x7fffffff;
-    }
-    const bool any    = X1 >= X0 && Y1 >= Y0;
-    const int  bw     = any ? ((X1 - X0 + 2) & ~1) : 0;                // even number of columns covering X0..X1
-    const int  bh     = any ? (Y1 - Y0 + 1) : 0;
-    const bool staged = any && bw * bh <= kLdsCap && !OFL_ABLATE(a, 4);
-
-    if (staged) {
-        const int pairs = bw >> 1, total = pairs * bh;
-        for (int idx = threadIdx.x; idx < total; idx += 256) {
-            const int r = idx / pairs, cp = idx - r * pairs;
-            const size_t g = (size_t)(Y0 + r) * W + (X0 + 2 * cp);
-            const float4   v = *reinterpret_cast<const float4 *>(fa + 2 * g);
-            const uint32_t m = *reinterpret_cast<const uint16_t *>(ma + g);
-            lds[r * bw + 2 * cp]     = make_float4(v.x, v.y, (m & 0xffu) ? 1.0f : 0.0f, 0.0f);
-            lds[r * bw + 2 * cp + 1] = make_float4(v.z, v.w, (m & 0xff00u) ? 1.0f : 0.0f, 0.0f);
-        }
-    }
-    __syncthreads();                                                   // B: tile staged (and box_next re-armed)
-
-    float su[kC3Px], sv[kC3Px];
-    bool  ok[kC3Px];
-#pragma unroll
-    for (int j = 0; j < kC3Px; ++j) { su[j] = 0.0f; sv[j] = 0.0f; ok[j] = false; }
-
-    if (staged && !OFL_ABLATE(a, 8)) {
-#pragma unroll
-        for (int j = 0; j < kC3Px; ++j) {
-            if (!use[j]) continue;
-            const int ix = tp[j].ix, iy = tp[j].iy;
-            const bool cx0 = ix >= 0, cx1 = ix + 1 <= W - 1, cy0 = iy >= 0, cy1 = iy + 1 <= H - 1;
-            const int lx0 = max(ix, 0) - X0, lx1 = min(ix + 1, W - 1) - X0;
-            const int ly0 = max(iy, 0) - Y0, ly1 = min(iy + 1, H - 1) - Y0;
-            float4 t00 = lds[ly0 * bw + lx0], t01 = lds[ly0 * bw + lx1];
-            float4 t10 = lds[ly1 * bw + lx0], t11 = lds[ly1 * bw + lx1];
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!(cx0 && cy0)) t00 = z;                                // taps outside the image: BORDER_CONSTANT 0
-            if (!(cx1 && cy0)) t01 = z;
-            if (!(cx0 && cy1)) t10 = z;
-            if (!(cx1 && cy1)) t11 = z;
-            const C3Tap w = c3_weights<QUANT>(tp[j]);
-            su[j] = c3_blend(t00.x, t01.x, t10.x, t11.x, w);
-            sv[j] = c3_blend(t00.y, t01.y, t10.y, t11.y, w);
-            ok[j] = c3_valid<QUANT>(t00.z != 0.0f, t01.z != 0.0f, t10.z != 0.0f, t11.z != 0.0f, w);
-            if (STATS) st.amax_m = fmaxf(st.amax_m, t00.z != 0.0f ? fmaxf(fabsf(t00.x), fabsf(t00.y)) : 0.0f);
-        }
-    } else if (any) {
-        // footprint too large for the LDS budget: per-pixel gathers straight from global memory
-#pragma unroll
-        for (int j = 0; j < kC3Px; ++j) {
-            if (!use[j]) continue;
-            const int  ixc = min(max(tp[j].ix, 0), max(W - 2, 0));
-            const int  d   = tp[j].ix - ixc;
-            const bool r0  = (unsigned)tp[j].iy < (unsigned)H;
-            const bool r1  = (unsigned)(tp[j].iy + 1) < (unsigned)H;
-            const int  y0c = min(max(tp[j].iy, 0), H - 1);
-            const int  y1c = min(max(tp[j].iy + 1, 0), H - 1);
-            const size_t s0 = (size_t)y0c * W + ixc, s1 = (size_t)y1c * W + ixc;
-            const Pair2 p0 = *reinterpret_cast<const Pair2 *>(fa + 2 * s0);
-            const Pair2 p1 = *reinterpret_cast<const Pair2 *>(fa + 2 * s1);
-            const uint32_t q00 = ma[s0], q01 = ma[s0 + 1], q10 = ma[s1], q11 = ma[s1 + 1];
-            float u00, v00, u01, v01, u10, v10, u11, v11, a00, a01, a10, a11;
-            select_pair(p0, d, r0, u00, v00, u01, v01);
-            select_pair(p1, d, r1, u10, v10, u11, v11);
-            select_mask(q00, q01, d, r0, a00, a01);
-            select_mask(q10, q11, d, r1, a10, a11);
-            const C3Tap w = c3_weights<QUANT>(tp[j]);
-            su[j] = c3_blend(u00, u01, u10, u11, w);
-            sv[j] = c3_blend(v00, v01, v10, v11, w);
-            ok[j] = c3_valid<QUANT>(a00 != 0.0f, a01 != 0.0f, a10 != 0.0f, a11 != 0.0f, w);
-            if (STATS) st.amax_m = fmaxf(st.amax_m, a00 != 0.0f ? fmaxf(fabsf(u00), fabsf(v00)) : 0.0f);
-        }
-    }
-    c3_finish<STATS>(a, row, xg, act, bu, bv, bm, su, sv, ok, st);
-}
-
-template <int QUANT, bool STATS>
-__global__ __launch_bounds__(256)
-void compose3_lds_kernel(const C3Args a)
-{
-    __shared__ float4 lds[kLdsCap];
-    __shared__ int    box[2][4];
-    if (threadIdx.x < 8) box[threadIdx.x >> 2][threadIdx.x & 3] = (threadIdx.x & 2) ? -0x7fffffff : 0x7fffffff;
-    __syncthreads();
-    const int nb  = gridDim.x;
-    const int per = nb >> 3;
-    int tile = (nb & 7) == 0 ? (blockIdx.x & 7) * per + (blockIdx.x >> 3) : blockIdx.x;
-    if (tile >= a.ntiles) return;
-    C3Stat st = { 0.0f, 0.0f, 0.0f };
-    int cur_b = tile / a.tiles_per_field;
-    int parity = 0;
-    C3Stream in = c3_load_stream<kLdsLX>(a, tile);
-    while (true) {
-        const int next = tile + nb;
-        const bool more = next < a.ntiles;
-        C3Stream nxt;
-        if (more) nxt = c3_load_stream<kLdsLX>(a, next);     // prefetch across this tile's two barriers
-        c3_tile_lds<QUANT, STATS>(a, tile, in, st, lds, box[parity], box[parity ^ 1]);
-        if (!more) break;
-        if (STATS) {
-            const int nb_ = next / a.tiles_per_field;
-            if (nb_ != cur_b) {
-                c3_flush_stats(a, cur_b, st);
-                st.amax_m = st.bmax = st.bmax_m = 0.0f;
-                cur_b = nb_;
-            }
-        }
-        in = nxt;
-        tile = next;
-        parity ^= 1;
-    }
-    if (STATS) c3_flush_stats(a, cur_b, st);
-}
-#endif  // OFL_EXPERIMENTS
 
 // Generic-shape fallback (any W >= 1, one pixel per thread, no vector accesses).
 template <int QUANT>
@@ -1402,12 +1068,6 @@ __device__ __forceinline__ void gather2_core(const T *__restrict__ src, const ui
 
 }
 
-#ifndef OFL_G2_NT_FLOW
-#define OFL_G2_NT_FLOW 0       // measured: non-temporal flow loads / image stores do not help this kernel (they do help K2)
-#endif
-#ifndef OFL_G2_NT_DST
-#define OFL_G2_NT_DST 0
-#endif
 // SPEC: the (quant, arith, rule) triple as compile-time constants for the combinations the Flow algebra actually asks for --
 // 1 = cv2's 1/32-px snap + uint8 fixed point + `>= 1/2` (a uint8 image with a boolean mask, flow_class.py:644), 2 = the snap +
 // float accumulate + `== 1` (float images and Flow targets), 3 = the snap + float sum rounded half to even + `> 1/2` (a uint8 image
@@ -1420,7 +1080,7 @@ void gather2_kernel(const T *__restrict__ src0, int H, int W,
                     const float *__restrict__ flow0, int fH, int fW, int pad_top, int pad_left, int sign,
                     const uint8_t *__restrict__ smask0, const uint8_t *__restrict__ fmask0,
                     T *__restrict__ dst0, uint8_t *__restrict__ valid0,
-                    int quant, int arith, int rule, int tiles_x, int nblocks, int row0, int rows, int xpose_rows, GBatch bs)
+                    int quant, int arith, int rule, int tiles_x, int row0, int rows, GBatch bs)
 {
     if (SPEC == 1) { quant = OFL_QUANT_OPENCV; arith = OFL_ARITH_NATIVE; rule = OFL_RULE_GE_HALF; }
     if (SPEC == 2 || SPEC == 4) { quant = OFL_QUANT_OPENCV; arith = OFL_ARITH_NATIVE; rule = OFL_RULE_EQ1; }
@@ -1433,7 +1093,7 @@ void gather2_kernel(const T *__restrict__ src0, int H, int W,
     const uint8_t *__restrict__ fmask = fmask0 ? fmask0 + bi * bs.fmask : nullptr;
     T *__restrict__ dst = dst0 + bi * bs.dst;
     uint8_t *__restrict__ valid = valid0 ? valid0 + bi * bs.valid : nullptr;
-    const int tile = nblocks > 0 ? xcd_swizzle(blockIdx.x, nblocks) : (int)blockIdx.x;     // nblocks <= 0: natural order
+    const int tile = blockIdx.x;
     const int ty   = tile / tiles_x, tx = tile - ty * tiles_x;
     const int lx   = threadIdx.x & 31, yl = ty * 8 + (threadIdx.x >> 5), y = row0 + yl;     // output band [row0, row0 + rows)
     const int xg[2] = { tx * 128 + 2 * lx, tx * 128 + 64 + 2 * lx };
@@ -1475,11 +1135,7 @@ void gather2_kernel(const T *__restrict__ src0, int H, int W,
             }
         }
         if (aligned && inf[2 * g] && inf[2 * g + 1]) {
-#if OFL_G2_NT_FLOW
-            const v4f f = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(flow + (__umul24((uint32_t)fy, (uint32_t)fW) + (uint32_t)fx) * 2));
-#else
             const float4 f = *reinterpret_cast<const float4 *>(flow + (__umul24((uint32_t)fy, (uint32_t)fW) + (uint32_t)fx) * 2);
-#endif
             fu[2 * g] = f.x; fv[2 * g] = f.y; fu[2 * g + 1] = f.z; fv[2 * g + 1] = f.w;
         } else {
 #pragma unroll
@@ -1494,7 +1150,7 @@ void gather2_kernel(const T *__restrict__ src0, int H, int W,
     const bool want_valid = valid != nullptr;
     T    res[4][CT];
     bool ok[4];
-    // transposed gather for rotated sampling grids (see K2, variant 3) -- float images with 3 or 4 channels only:
+    // transposed gather for rotated sampling grids (see K2's transposed-gather form) -- float images with 3 or 4 channels only:
     // measured +10 % on a 30-degree grid.  For 1 / 2 channels and for 8- / 16-bit images the extra registers cost a wave
     // of occupancy (and the byte-wise LDS hand-over is slow), which loses more than the fewer tag look-ups save.
     constexpr bool kXp = sizeof(T) == 4 && CT >= 3;
@@ -1509,7 +1165,7 @@ void gather2_kernel(const T *__restrict__ src0, int H, int W,
         const bool rin = (unsigned)fy0 < (unsigned)fH;
         const float va = (rin && (unsigned)fxa < (unsigned)fW) ? flow[((size_t)fy0 * fW + fxa) * 2 + 1] : 0.0f;
         const float vb = (rin && (unsigned)fxb < (unsigned)fW) ? flow[((size_t)fy0 * fW + fxb) * 2 + 1] : 0.0f;
-        rotated = fabsf(vb - va) * 128.0f > (float)(xpose_rows * (x1 - x0 + 1));
+        rotated = fabsf(vb - va) * 128.0f > (float)(kXposeRows * (x1 - x0 + 1));
     }
     if (!rotated) {
         const int  gx[4]   = { xg[0], xg[0] + 1, xg[1], xg[1] + 1 };
@@ -1601,11 +1257,7 @@ void gather2_kernel(const T *__restrict__ src0, int H, int W,
 #pragma unroll
             for (int e = 0; e < 2; ++e)
 #pragma unroll
-#if OFL_G2_NT_DST
-                for (int c = 0; c < CT; ++c) __builtin_nontemporal_store(res[2 * g + e][c], &d[e * CT + c]);
-#else
                 for (int c = 0; c < CT; ++c) d[e * CT + c] = res[2 * g + e][c];
-#endif
         }
         if (act[g] && want_valid) {
             uint32_t m = (ok[2 * g] ? 1u : 0u) | (ok[2 * g + 1] ? 0x100u : 0u);
@@ -1644,17 +1296,14 @@ int launch_gather_t(const void *src, int C, int H, int W, const float *flow, int
     if (W % 2 == 0 && C >= 1 && C <= 4 && (unsigned long long)H * W * C * sizeof(T) < (1ull << 32) && (unsigned long long)fH * fW * 8 < (1ull << 32)) {
         const int tiles_x = (W + 127) / 128, tiles_y = (rows + 7) / 8;
         const int nblocks = tiles_x * tiles_y;
-        static const int swz = OFL_KNOB_INT("OFL_G2_SWZ", 0);                      // 1 = XCD swizzle (experiments build only)
-        static const int xpose_rows = OFL_KNOB_INT("OFL_G2_XPOSE_ROWS", kXposeRows);   // (experiments build only)
 #define OFL_GATHER2_LAUNCH_S(CT, SPEC)                                                                   \
         hipLaunchKernelGGL((gather2_kernel<T, CT, SPEC>), dim3(nblocks, batch), dim3(256), 0, s, (const T *)src, H, W, \
                            flow, fH, fW, pad_top, pad_left, sign, smask, fmask, (T *)dst, valid, quant,   \
-                           arith, rule, tiles_x, swz ? nblocks : 0, row0, rows, xpose_rows, bs)
+                           arith, rule, tiles_x, row0, rows, bs)
 #define OFL_GATHER2_LAUNCH(CT) OFL_GATHER2_LAUNCH_S(CT, 0)
-        static const int spec_on = OFL_KNOB_INT("OFL_G2_SPEC", 1);                 // (experiments build only) 0: the general kernel for everything
         // the combinations the Flow algebra asks for run as specialised instantiations (same code, branches folded: 7 - 10 % faster)
         int spec = 0;
-        if (spec_on && quant == OFL_QUANT_OPENCV) {
+        if (quant == OFL_QUANT_OPENCV) {
             if (std::is_same<T, uint8_t>::value && arith == OFL_ARITH_NATIVE && rule == OFL_RULE_GE_HALF) spec = 1;
             else if (std::is_same<T, float>::value && arith == OFL_ARITH_NATIVE && rule == OFL_RULE_EQ1)
                 spec = (unsigned long long)H * W * C * sizeof(T) > (128ull << 20) ? 4 : 2;      // a source beyond half the Infinity Cache: five waves
@@ -1698,39 +1347,6 @@ int launch_gather_t(const void *src, int C, int H, int W, const float *flow, int
     OFL_HIP(hipGetLastError());
     return OFL_OK;
 }
-
-#ifdef OFL_EXPERIMENTS
-// resident workgroups per CU of each compose3 instantiation (queried once per process)
-template <typename K>
-int c3_query_blocks(K kernel)
-{
-    int n = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, 0);
-    if (e != hipSuccess) { (void)hipGetLastError(); n = 4; }
-    return n;
-}
-
-int c3_blocks_per_cu(int quant, bool with_stats, bool lds)
-{
-    static int cache[2][2][2] = { { { 0, 0 }, { 0, 0 } }, { { 0, 0 }, { 0, 0 } } };
-    const int q = quant == OFL_QUANT_OPENCV ? 0 : 1;
-    int &v = cache[q][with_stats ? 1 : 0][lds ? 1 : 0];
-    if (v == 0) {
-        int n;
-        if (lds) {
-            if (q == 0) n = with_stats ? c3_query_blocks(compose3_lds_kernel<OFL_QUANT_OPENCV, true>) : c3_query_blocks(compose3_lds_kernel<OFL_QUANT_OPENCV, false>);
-            else        n = with_stats ? c3_query_blocks(compose3_lds_kernel<OFL_QUANT_EXACT, true>) : c3_query_blocks(compose3_lds_kernel<OFL_QUANT_EXACT, false>);
-        } else {
-            if (q == 0) n = with_stats ? c3_query_blocks(compose3_kernel<OFL_QUANT_OPENCV, true>) : c3_query_blocks(compose3_kernel<OFL_QUANT_OPENCV, false>);
-            else        n = with_stats ? c3_query_blocks(compose3_kernel<OFL_QUANT_EXACT, true>) : c3_query_blocks(compose3_kernel<OFL_QUANT_EXACT, false>);
-        }
-        const char *env = getenv("OFL_C3_BLOCKS_PER_CU");      // tuning knob
-        if (env && atoi(env) > 0) n = atoi(env);
-        v = n < 1 ? 1 : (n > 8 ? 8 : n);
-    }
-    return v;
-}
-#endif  // OFL_EXPERIMENTS
 
 size_t dtype_size(int dtype)
 {
@@ -1820,37 +1436,11 @@ int ofl_compose3_dev(const float *fa, const uint8_t *ma, const float *fb, const 
         // One workgroup per 128 x 8 tile in natural order -- the dispatcher keeps every wave slot filled and all XCDs sweep
         // one window of memory (measured +2..7 % over a persistent grid at 1..8 4K pairs per launch) -- with the gather
         // transposed through LDS in workgroups whose sampling grid is rotated.
-        int tiles_x = (W + kC3TileW - 1) / kC3TileW, tiles_y = (H + kC3TileH - 1) / kC3TileH;
-        long long nt = (long long)tiles_x * tiles_y * batch;
+        const int tiles_x = (W + kC3TileW - 1) / kC3TileW, tiles_y = (H + kC3TileH - 1) / kC3TileH;
+        const long long nt = (long long)tiles_x * tiles_y * batch;
         if (nt > 0x7fffffffLL) return fail(OFL_E_INVALID, "ofl_compose3: too many tiles");
-        static const int xpose_rows = OFL_KNOB_INT("OFL_C3_XPOSE_ROWS", kXposeRows);
-        static const int xcd_rows = OFL_KNOB_INT("OFL_C3_XCD_ROWS", kC3XcdRows);       // tile rows one XCD owns per group (see the kernel)
-        const long long n_groups = (long long)batch * ((tiles_x + 7) / 8) * ((tiles_y + xcd_rows - 1) / xcd_rows);
-        const long long nblk = xcd_rows > 1 ? n_groups * 8 * xcd_rows : nt;
-        if (nblk > 0x7fffffffLL) return fail(OFL_E_INVALID, "ofl_compose3: too many tiles");
-#ifdef OFL_EXPERIMENTS
-        // A/B variants: OFL_C3_VARIANT = 2 the same without the transposition, 0 persistent grid with stream prefetch,
-        // 1 source tile staged in LDS; OFL_C3_ABLATE switches parts of the kernel off, OFL_C3_SWZ tries XCD-aware tile orders
-        static const int ablate = OFL_KNOB_INT("OFL_C3_ABLATE", 0);
-        static const int variant = OFL_KNOB_INT("OFL_C3_VARIANT", 3);
-        static const int swz = OFL_KNOB_INT("OFL_C3_SWZ", 0);
-        const bool use_lds = variant == 1;
-        if (use_lds) {
-            tiles_x = (W + 4 * kLdsLX - 1) / (4 * kLdsLX); tiles_y = (H + 256 / kLdsLX - 1) / (256 / kLdsLX);
-            nt = (long long)tiles_x * tiles_y * batch;
-        }
-        C3Args a = { fa, ma, fb, mb, out, mout, stats, sign, H, W, tiles_x, tiles_x * tiles_y, (int)nt, th, 0, variant == 3 ? xcd_rows : swz, xpose_rows, ablate };
-        int grid = rt().n_cu * c3_blocks_per_cu(quant, stats != nullptr, use_lds);      // persistent variants: what the chip keeps resident
-        if (grid > (int)nt) grid = (int)nt;
-        if (grid >= 8) grid &= ~7;
-#define OFL_C3(Q, S) do { if (use_lds) hipLaunchKernelGGL((compose3_lds_kernel<Q, S>), dim3(grid), dim3(256), 0, s, a); \
-                          else if (variant == 2) hipLaunchKernelGGL((compose3_oneshot_kernel<Q, S>), dim3((int)nt), dim3(256), 0, s, a); \
-                          else if (variant == 0) hipLaunchKernelGGL((compose3_kernel<Q, S>), dim3(grid), dim3(256), 0, s, a); \
-                          else hipLaunchKernelGGL((compose3_xpose_kernel<Q, S>), dim3((int)nblk), dim3(256), 0, s, a); } while (0)
-#else
-        C3Args a = { fa, ma, fb, mb, out, mout, stats, sign, H, W, tiles_x, tiles_x * tiles_y, (int)nt, th, 0, xcd_rows, xpose_rows };
-#define OFL_C3(Q, S) hipLaunchKernelGGL((compose3_xpose_kernel<Q, S>), dim3((int)nblk), dim3(256), 0, s, a)
-#endif
+        C3Args a = { fa, ma, fb, mb, out, mout, stats, sign, H, W, tiles_x, tiles_x * tiles_y, (int)nt, th, 0 };
+#define OFL_C3(Q, S) hipLaunchKernelGGL((compose3_xpose_kernel<Q, S>), dim3((int)nt), dim3(256), 0, s, a)
         if (quant == OFL_QUANT_OPENCV) { if (stats) OFL_C3(OFL_QUANT_OPENCV, true); else OFL_C3(OFL_QUANT_OPENCV, false); }
         else                           { if (stats) OFL_C3(OFL_QUANT_EXACT, true);  else OFL_C3(OFL_QUANT_EXACT, false); }
 #undef OFL_C3
@@ -1914,11 +1504,7 @@ int ofl_compose3_bits_dev(const float *fa, const uint32_t *ma_bits, const float 
     const long long nt = (long long)tiles_x * tiles_y * batch;
     if (nt > 0x7fffffffLL) return fail(OFL_E_INVALID, "ofl_compose3_bits: too many tiles");
     C3Args a = { fa, reinterpret_cast<const uint8_t *>(ma_bits), fb, reinterpret_cast<const uint8_t *>(mb_bits), out,
-                 reinterpret_cast<uint8_t *>(mout_bits), stats, sign, H, W, tiles_x, tiles_x * tiles_y, (int)nt, 1e-3f, (W + 31) / 32, 1, kXposeRows
-#ifdef OFL_EXPERIMENTS
-                 , 0
-#endif
-    };
+                 reinterpret_cast<uint8_t *>(mout_bits), stats, sign, H, W, tiles_x, tiles_x * tiles_y, (int)nt, 1e-3f, (W + 31) / 32 };
     if (stats) hipLaunchKernelGGL((compose3_xpose_kernel<OFL_QUANT_OPENCV, true, true>), dim3((int)nt), dim3(256), 0, s, a);
     else       hipLaunchKernelGGL((compose3_xpose_kernel<OFL_QUANT_OPENCV, false, true>), dim3((int)nt), dim3(256), 0, s, a);
     OFL_HIP(hipGetLastError());

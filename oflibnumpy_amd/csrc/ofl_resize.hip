@@ -12,9 +12,6 @@ using namespace ofl;
 
 namespace {
 
-#ifndef OFL_RS_NT
-#define OFL_RS_NT 1            // non-temporal output stores
-#endif
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct ResizeCoef { int s0, s1; float w0, w1; };
@@ -93,15 +90,10 @@ void resize_flow_kernel(const float2 *__restrict__ src, const uint8_t *__restric
     if (dx + 1 < Wo) {
         const ResizeCoef cx1 = resize_coef(dx + 1, scale_x, W, true);
         const float2 p1 = resize_px(src, mask, W, cx1, cy, mul_u, mul_v, m1);
-        if ((o & 1) == 0) {                          // 16-byte aligned pair (always when Wo is even)
-#if OFL_RS_NT
+        if ((o & 1) == 0) {                          // 16-byte aligned pair (always when Wo is even): non-temporal stores
             const v4f v = { p0.x, p0.y, p1.x, p1.y };
             __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(out) + (o >> 1));
             if (mout) __builtin_nontemporal_store((uint16_t)(m0 | (m1 << 8)), reinterpret_cast<uint16_t *>(mout + o));
-#else
-            reinterpret_cast<float4 *>(out)[o >> 1] = make_float4(p0.x, p0.y, p1.x, p1.y);
-            if (mout) *reinterpret_cast<uint16_t *>(mout + o) = (uint16_t)(m0 | (m1 << 8));
-#endif
         } else {
             out[o] = p0; out[o + 1] = p1;
             if (mout) { mout[o] = m0; mout[o + 1] = m1; }
@@ -204,16 +196,10 @@ void resize_flow4_kernel(const float2 *__restrict__ src, const uint8_t *__restri
     }
     }
     const size_t o = (size_t)dy * Wo + dx;
-#if OFL_RS_NT
     const v4f v0 = { p[0].x, p[0].y, p[1].x, p[1].y }, v1 = { p[2].x, p[2].y, p[3].x, p[3].y };
     __builtin_nontemporal_store(v0, reinterpret_cast<v4f *>(out) + (o >> 1));
     __builtin_nontemporal_store(v1, reinterpret_cast<v4f *>(out) + (o >> 1) + 1);
     if (mout) __builtin_nontemporal_store(mo, reinterpret_cast<uint32_t *>(mout + o));
-#else
-    reinterpret_cast<float4 *>(out)[o >> 1] = make_float4(p[0].x, p[0].y, p[1].x, p[1].y);
-    reinterpret_cast<float4 *>(out)[(o >> 1) + 1] = make_float4(p[2].x, p[2].y, p[3].x, p[3].y);
-    if (mout) *reinterpret_cast<uint32_t *>(mout + o) = mo;
-#endif
 }
 
 }  // namespace
@@ -231,8 +217,7 @@ int ofl_resize_flow_dev(const float *vecs, const uint8_t *mask, int H, int W, in
     if ((mask == nullptr) != (mout == nullptr)) return fail(OFL_E_INVALID, "ofl_resize_flow: mask and mout go together");
     const unsigned gy = (unsigned)((Ho + 3) / 4), gx = (unsigned)((Wo + 127) / 128);
     if (gy > 65535u) return fail(OFL_E_INVALID, "ofl_resize_flow: output too tall");
-    static const bool no4 = OFL_KNOB_SET("OFL_RS_NO4");              // development knob (A/B; experiments build only)
-    if (!no4 && scale_x <= 1.0 && (Wo & 3) == 0 && W >= 6) {
+    if (scale_x <= 1.0 && (Wo & 3) == 0 && W >= 6) {
         if (scale_x == 0.5)
             hipLaunchKernelGGL(resize_flow4_kernel<true>, dim3((unsigned)((Wo + 255) / 256), gy), dim3(64, 4), 0, stream_of(stream),
                                reinterpret_cast<const float2 *>(vecs), mask, H, W, Ho, Wo, scale_y, scale_x, mul_u, mul_v,

@@ -475,35 +475,17 @@ __device__ __forceinline__ bool clearly_outside32(const WalkCert &wc, float x, f
     return out;
 }
 
-#ifndef OFL_WALK_WAVES
-#define OFL_WALK_WAVES 5      // waves per SIMD the allocator leaves room for: the kernel is VALU-bound (5: 156 us, 7: 159 us, 8 spills: 246 us at 4K)
-#endif
+constexpr int kWalkWaves = 5;     // waves per SIMD the allocator leaves room for: the kernel is VALU-bound (5: 156 us, 7: 159 us, 8 spills: 246 us at 4K)
 template <typename VT, int SP, bool BITS>
-__global__ __launch_bounds__(256, OFL_WALK_WAVES)
+__global__ __launch_bounds__(256, kWalkWaves)
 void scatter_walk_kernel(const float *__restrict__ flow, const VT *__restrict__ vals, int C,
                          const uint8_t *__restrict__ vmask, int H, int W, int row0, int rows,
                          VT *__restrict__ out, uint8_t *__restrict__ valid, int valid_rule, WalkCert wc,
-                         uint32_t *__restrict__ fail, int tiling)
+                         uint32_t *__restrict__ fail)
 {
-    // tiling bit 1: tiles of 64 x 4 nodes instead of 32 x 8; bit 0: a 1-D grid whose workgroup b (XCD b % 8) takes tile
-    // (b % 8) * chunk + b / 8 -- every XCD sweeps ONE band of rows, so the halo lines of neighbouring tiles meet in one L2
-    const int tws = (tiling & 2) ? 6 : 5;
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (tiling & 1) {
-        const int gx = (W + (1 << tws) - 1) >> tws, gy = (rows + (256 >> tws) - 1) / (256 >> tws);
-        const int rs = (tiling >> 2) & 3, xcd = (int)(blockIdx.x & 7), j = (int)(blockIdx.x >> 3);
-        if (rs == 0) {                                           // one contiguous band of tiles per XCD
-            const int nb = gx * gy, chunk = (nb + 7) >> 3, tile = xcd * chunk + j;
-            if (j >= chunk || tile >= nb) return;
-            by = tile / gx; bx = tile - by * gx;
-        } else {                                                 // bands of 2^rs tile rows dealt round-robin to the XCDs, walked column by column
-            const int sr = (int)blockIdx.y, jj = j;              // (grid: 8 * (gx << rs) by rounds -- no division)
-            bx = jj >> rs; by = (((sr << 3) + xcd) << rs) + (jj & ((1 << rs) - 1));
-            if (by >= gy) return;
-        }
-    }
-    const int x = (bx << tws) + (threadIdx.x & ((1 << tws) - 1));
-    const int yl = by * (256 >> tws) + (threadIdx.x >> tws), y = row0 + yl;
+    // tiles of 32 x 8 nodes in natural order
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31);
+    const int yl = blockIdx.y * 8 + (threadIdx.x >> 5), y = row0 + yl;
     if (x >= W || yl >= rows) return;
     const size_t o = (size_t)yl * W + x;
     Hit h;
@@ -669,19 +651,16 @@ int walk_launch(const float *flow, int sign_pp, const VT *vals, int C, const uin
     wc.not_affine = nullptr;
     for (int k = 0; k < 6; ++k) wc.ai[k] = 0.0;
     if (wc.diag && H >= 2 && W >= 2 && corner_affine_inverse(wc.c[0], wc.c[1], wc.c[3], H, W, wc.ai)) wc.not_affine = wc.diag + (size_t)(H - 1) * wc.diag_stride;
-    const int tiling = OFL_KNOB_INT("OFL_WALK_TILING", 0);
-    const int tws = (tiling & 2) ? 6 : 5, gx = (W + (1 << tws) - 1) >> tws, gy = (rows + (256 >> tws) - 1) / (256 >> tws);
-    const int rs = (tiling >> 2) & 3, bands = ((gy + (1 << rs) - 1) >> rs), rounds = (bands + 7) / 8;
-    const dim3 grid(!(tiling & 1) ? gx : rs == 0 ? 8 * (((size_t)gx * gy + 7) / 8) : (size_t)8 * (gx << rs), !(tiling & 1) ? gy : rs == 0 ? 1 : rounds), block(256);
+    const dim3 grid((W + 31) / 32, (rows + 7) / 8), block(256);
     // (a variant that took flow-valued targets -- invert, switch_ref -- and their mask bytes straight from the registers of the
     // cell test was measured SLOWER twice, in round 2 (168 vs 157 us at 4K) and again on this leaner kernel (85 vs 77 us): keeping
     // the corner loads alive to the end costs 30 VGPRs, more than the three cached reloads it saves; fetching only the corners'
     // mask bytes with the cell -- 6 VGPRs -- changed nothing: 78.7 vs 78.2 us)
 #define OFL_WALK_LAUNCH(SP)                                                                                                       \
     do { if (wc.diag) hipLaunchKernelGGL((scatter_walk_kernel<VT, SP, true>), grid, block, 0, s, flow, vals, C, vmask, H, W, row0, rows, \
-                                         out, valid, valid_rule, wc, fail_dev, tiling);                                                  \
+                                         out, valid, valid_rule, wc, fail_dev);                                                  \
          else hipLaunchKernelGGL((scatter_walk_kernel<VT, SP, false>), grid, block, 0, s, flow, vals, C, vmask, H, W, row0, rows, out,  \
-                                 valid, valid_rule, wc, fail_dev, tiling); } while (0)
+                                 valid, valid_rule, wc, fail_dev); } while (0)
     if (sign_pp == 1) OFL_WALK_LAUNCH(1); else if (sign_pp == -1) OFL_WALK_LAUNCH(-1);
     else if (sign_pp == 2) OFL_WALK_LAUNCH(2); else OFL_WALK_LAUNCH(-2);
 #undef OFL_WALK_LAUNCH
@@ -702,8 +681,6 @@ int walk_query_launch(const float *flow, int sign_pp, const float *vals, int C, 
     }
     wc.diag = nullptr; wc.diag_stride = 0; wc.not_affine = nullptr;
     for (int k = 0; k < 6; ++k) wc.ai[k] = 0.0;
-    // (the query kernel decides diagonals itself, but the certificate's "not affine" word -- in the last row of its plane -- serves it too)
-    if (cert->diag_bits && H >= 2 && W >= 2 && corner_affine_inverse(wc.c[0], wc.c[1], wc.c[3], H, W, wc.ai)) wc.not_affine = cert->diag_bits + (size_t)(H - 1) * ((W + 31) / 32);
     set_planes(wc, H, W);
     if (n == 0) return OFL_OK;
     const size_t nb = (n + 255) / 256;

@@ -131,16 +131,13 @@ void flow_extent_kernel(const float *__restrict__ flow, const uint8_t *__restric
 // Each thread moves two float4 (2 x 2 pixels, one per 1-KiB wave chunk) and one 4-byte mask word: every
 // wave instruction covers contiguous memory, and the 1-byte mask streams need half the instructions
 // the vector streams need instead of the same number.
+constexpr int kAxpyChunks = 2;      // float4 chunks of 128 px (32 mask words each) per wave and work unit
 __global__ __launch_bounds__(256)
 void axpy_kernel(const float *__restrict__ a, const uint8_t *__restrict__ ma,
                  const float *__restrict__ b, const uint8_t *__restrict__ mb, float alpha, size_t n_px,
                  float *__restrict__ out, uint8_t *__restrict__ mout)
 {
-#ifndef OFL_AXPY_CHUNKS
-#define OFL_AXPY_CHUNKS 2
-#endif
-    // work unit = 128 * OFL_AXPY_CHUNKS pixels per wave (float4 chunks of 128 px, 32 mask words each)
-    constexpr int kCh = OFL_AXPY_CHUNKS, kUnit = 128 * kCh;
+    constexpr int kCh = kAxpyChunks, kUnit = 128 * kCh;       // pixels per wave and work unit
     const size_t n_units = n_px / kUnit;
     const int lane = threadIdx.x & 63;
     const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((size_t)gridDim.x * blockDim.x) >> 6;
@@ -237,19 +234,13 @@ void sample_points_kernel(const float *__restrict__ flow, int H, int W, const do
     }
 }
 
-#ifndef OFL_AXPY_CHUNKS
-#define OFL_AXPY_CHUNKS 2
-#endif
-
 int stream_grid(size_t n_items)
 {
     size_t nb = (n_items + 255) / 256;
     if (nb < 1) nb = 1;
     // One workgroup per 256 items, no persistent cap: on MI355X a copy that is dispatched as one workgroup per
     // chunk streams at 6.0-6.3 TB/s, the same loop on a resident-sized grid at 5.1-5.3 (tools/copy_sweep.hip).
-    const size_t per_cu = (size_t)OFL_KNOB_INT("OFL_STREAM_GRID_CAP", 0);      // workgroups per CU, 0 = uncapped (experiments build only)
-    const size_t cap = per_cu ? (size_t)rt().n_cu * per_cu : (size_t)0x7fffffff;
-    return (int)(nb < cap ? nb : cap);
+    return (int)(nb < 0x7fffffff ? nb : 0x7fffffff);
 }
 
 template <typename S, typename D>
@@ -305,7 +296,7 @@ int ofl_axpy_dev(const float *a, const uint8_t *ma, const float *b, const uint8_
     if (!a || !out) return fail(OFL_E_INVALID, "ofl_axpy: NULL pointer");
     if (mout && !ma) return fail(OFL_E_INVALID, "ofl_axpy: mout requires ma");
     if (n_px == 0) return OFL_OK;
-    hipLaunchKernelGGL(axpy_kernel, dim3(stream_grid(n_px / (2 * OFL_AXPY_CHUNKS))), dim3(256), 0, stream_of(stream),
+    hipLaunchKernelGGL(axpy_kernel, dim3(stream_grid(n_px / (2 * kAxpyChunks))), dim3(256), 0, stream_of(stream),
                        a, ma, b, mb, alpha, n_px, out, mout);
     OFL_HIP(hipGetLastError());
     return OFL_OK;

@@ -33,6 +33,10 @@ CASES = [  # (shape, transforms f1, transforms f2)
     ((37, 53), [['rotation', 20, 10, -15]], [['translation', 2.5, -3.25]]),         # W % 4 != 0 -> generic kernel
     ((5, 1), [['translation', 0.5, 1]], [['translation', 0, 0.25]]),                # degenerate width
     ((1, 8), [['translation', 0.5, 0]], [['translation', 1.5, 0]]),
+    ((300, 400), [['rotation', 200, 150, -30]], [['scaling', 100, 80, 0.8]]),
+    ((257, 130), [['scaling', 60, 60, 0.9]], [['rotation', 65, 128, 40]]),              # odd tile remainders
+    ((96, 256), [['rotation', 10, 10, 5]], [['scaling', 128, 48, 3.5]]),                # large source footprint per tile
+    ((33, 66), [['translation', 1.5, -2.25]], [['translation', 70.5, 0]]),
 ]
 
 
@@ -532,88 +536,22 @@ def test_combine_flows_batch_api(gpu, oracle):
     np.testing.assert_array_equal(arr[1][1].vecs, of.combine_flows(f1s[1].vecs, f2s[1].vecs, 3, 's'))
 
 
-def test_lds_staged_variant_in_subprocess(gpu):
-    """The A/B compose kernel variants of the EXPERIMENTS build (libofl_hip_exp.so, OFL_C3_VARIANT read once per process;
-    the shipped library holds only the default kernel and reads no environment) produce the same bits as the oracle:
-    small and large footprints (the latter exceed the LDS budget and take the in-kernel direct path), both references,
-    odd tile remainders."""
-    import os
-    import subprocess
-    import sys
-    code = r"""
-import sys, numpy as np
-sys.path.insert(0, %r)
-import oflibnumpy_amd as of
-from oracle import np_oracle as O
-rng = np.random.default_rng(5)
-for shape, t1, t2 in (((300, 400), [['rotation', 200, 150, -30]], [['scaling', 100, 80, 0.8]]),
-                      ((257, 130), [['scaling', 60, 60, 0.9]], [['rotation', 65, 128, 40]]),
-                      ((96, 256), [['rotation', 10, 10, 5]], [['scaling', 128, 48, 3.5]]),       # footprint > LDS budget
-                      ((33, 66), [['translation', 1.5, -2.25]], [['translation', 70.5, 0]])):
-    for ref in 'ts':
-        f1 = of.Flow.from_transforms(t1, list(shape), ref, rng.random(shape) > 0.1)
-        f2 = of.Flow.from_transforms(t2, list(shape), ref, rng.random(shape) > 0.1)
-        got = f1.combine_with(f2, 3)
-        want = O.OFlow(f1.vecs, ref, f1.mask).combine_with(O.OFlow(f2.vecs, ref, f2.mask), 3)
-        assert np.array_equal(got.vecs, want.vecs) and np.array_equal(got.mask, want.mask), (shape, ref)
-print("lds-variant-ok")
-""" % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    # variant 1 = source tile staged in LDS, 2 = one-shot without the transposed gather, 0 = persistent grid;
-    # the default (3, transposed gather for rotated sampling grids) is what every other test runs
-    from oflibnumpy_amd import build_native
-    if not os.path.exists(build_native.EXP_OUT):
-        build_native.build_experiments()
-    for variant in ("1", "2", "0"):
-        env = dict(os.environ, OFL_C3_VARIANT=variant, OFL_LIB=build_native.EXP_OUT)
-        p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0 and "lds-variant-ok" in p.stdout, (variant, p.stderr[-2000:])
-
-
-def test_general_gather_kernel_and_walk_tilings_in_subprocess(gpu):
-    """What the product library runs by default has a twin in the EXPERIMENTS build: the paired gather kernel WITHOUT the folded
-    (quantisation, arithmetic, rule) instantiations (OFL_G2_SPEC=0: one kernel for every combination, as before round 4), and the
-    certified walk with XCD-banded tile orders / 64 x 4 tiles (OFL_WALK_TILING).  Same bits as the oracle ('t') and as the default
-    order ('s', whose values the oracle pins to 1e-4 only): 8-bit, 16-bit and float images, 1 - 4 channels, with and without a mask."""
-    import os
-    import subprocess
-    import sys
-    code = r"""
-import os, sys, numpy as np
-sys.path.insert(0, %r)
-import oflibnumpy_amd as of
-from oracle import np_oracle as O
-rng = np.random.default_rng(8)
-shape = (131, 258)
-tm = rng.random(shape) > 0.1
-f = of.Flow.from_transforms([['rotation', 100, 60, 17], ['scaling', 100, 60, 0.9]], list(shape), 't', rng.random(shape) > 0.05)
-o = O.OFlow(f.vecs, 't', f.mask)
-for dtype in (np.uint8, np.int16, np.float32):
-    for C in (1, 2, 3, 4):
-        img = (rng.random(shape + (C,)) * 255).astype(dtype)
-        for mask in (None, tm):
-            got, gv = f.apply(img, mask, return_valid_area=True)
-            want, wv = o.apply(img, mask, return_valid_area=True)
-            assert np.array_equal(got, want) and np.array_equal(gv, wv), (dtype, C, mask is None)
-fs = of.Flow.from_transforms([['rotation', 100, 60, 17], ['scaling', 100, 60, 0.9]], [200, 330], 's')
-inv = fs.invert()
-sw = fs.switch_ref()
-np.save(os.environ['OFL_TEST_OUT'], np.concatenate([inv.vecs.ravel(), inv.mask.ravel().astype(np.float32), sw.vecs.ravel(), sw.mask.ravel().astype(np.float32)]))
-print("twin-ok")
-""" % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    from oflibnumpy_amd import build_native
-    import tempfile
-    if not os.path.exists(build_native.EXP_OUT):
-        build_native.build_experiments()
-    outs = []
-    with tempfile.TemporaryDirectory() as tmp:
-        for k, (spec, tiling) in enumerate((("1", "0"), ("0", "5"), ("1", "13"), ("0", "1"), ("1", "7"))):
-            out = os.path.join(tmp, "o%d.npy" % k)
-            env = dict(os.environ, OFL_G2_SPEC=spec, OFL_WALK_TILING=tiling, OFL_LIB=build_native.EXP_OUT, OFL_TEST_OUT=out)
-            p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-            assert p.returncode == 0 and "twin-ok" in p.stdout, (spec, tiling, p.stderr[-2000:])
-            outs.append(np.load(out))
-    for o2 in outs[1:]:
-        np.testing.assert_array_equal(outs[0], o2)
+def test_gather_kernel_dtypes_channels_and_masks(gpu, oracle):
+    """The paired gather kernel, folded instantiations and general one, against the oracle bit for bit: 8-bit, 16-bit and float
+    images, 1 - 4 channels, with and without a mask, on a rotated and scaled sampling grid."""
+    of = gpu
+    rng = np.random.default_rng(8)
+    shape = (131, 258)
+    tm = rng.random(shape) > 0.1
+    f = of.Flow.from_transforms([['rotation', 100, 60, 17], ['scaling', 100, 60, 0.9]], list(shape), 't', rng.random(shape) > 0.05)
+    o = oracle.OFlow(f.vecs, 't', f.mask)
+    for dtype in (np.uint8, np.int16, np.float32):
+        for C in (1, 2, 3, 4):
+            img = (rng.random(shape + (C,)) * 255).astype(dtype)
+            for mask in (None, tm):
+                got, gv = f.apply(img, mask, return_valid_area=True)
+                want, wv = o.apply(img, mask, return_valid_area=True)
+                assert np.array_equal(got, want) and np.array_equal(gv, wv), (dtype, C, mask is None)
 
 
 def test_device_resident_image_warp(gpu, oracle):

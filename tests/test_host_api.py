@@ -32,8 +32,8 @@ def test_abi_exports_every_declared_symbol():
 
 
 def test_shipped_library_is_lean():
-    """The product library reads no environment knobs and carries none of the A/B kernel variants (they live in the
-    experiments build, libofl_hip_exp.so, which tools/ and two subprocess tests load through OFL_LIB)."""
+    """The product library reads no environment knobs and carries no A/B kernel variants.  The one test hook,
+    OFL_DL_NEAR2_MIN, is read only by the experiments build (libofl_hip_exp.so), which a subprocess test loads through OFL_LIB."""
     import subprocess
     from oflibnumpy_amd import build_native
     assert os.path.basename(nat.LIB_PATH) == "libofl_hip.so" or os.environ.get("OFL_LIB")
