@@ -10,6 +10,7 @@
 // Numerics follow oracle/ofl_oracle.c operation for operation (contraction disabled) so that the
 // float results and the validity masks are bit-identical to the CPU restatement.
 #include "ofl_common.h"
+#include "ofl_compose3_route.h"
 #include <type_traits>
 
 #pragma clang fp contract(off)
@@ -22,6 +23,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct __attribute__((aligned(8))) Pair2 { float lo_u, lo_v, hi_u, hi_v; };   // taps (ix, ix+1) of a float2 field
 struct __attribute__((packed, aligned(1))) U32u { uint32_t v; };               // a 4-byte load from any address
+struct __attribute__((packed, aligned(1))) U16u { uint16_t v; };               // a 2-byte load from any address
 
 // MI355X deals consecutive workgroups round-robin over its 8 XCDs.  Give every XCD a contiguous
 // run of tiles so that neighbouring tiles (which share gather halos) meet in the same L2.
@@ -80,13 +82,18 @@ __device__ __forceinline__ uint32_t c3_spread16(uint32_t x)
 // x = 2*lx and x = 64 + 2*lx of its tile row, so that every stream instruction of a wave covers
 // contiguous memory (32 lanes x 16 B = 512 B of vectors, 32 lanes x 2 B = 64 B of mask per row):
 // no half-filled 64-byte requests on either the read or the write side.
+//
+// Register budget (tests/test_k2_resources.py): kC3Waves per SIMD with no spills and <= 80 SGPRs, so that scalar registers
+// never limit residency.  Only the interior gather is unrolled over a lane's four pixels; the border paths take one pixel
+// per loop trip through the lane's LDS slots, sample positions stay in their compact form while the loads are in flight,
+// and every address is a wave-uniform field base plus a 32-bit offset (ofl_compose3_route.h sends fields whose vector
+// plane reaches 4 GiB to the generic kernel).
 constexpr int kC3LanesX = 32;      // lanes along x per tile row: tile = 4*LX px x 256/LX rows
 constexpr int kC3TileW = 4 * kC3LanesX, kC3TileH = 256 / kC3LanesX, kC3Px = 4;
 
-struct C3Pos {            // what must stay live while the gather is in flight
-    int   ix, iy;         // top-left tap
-    float fx, fy;         // fractional position (multiples of 1/32 with cv2's snapping)
-};
+// Sample position of one pixel in two registers: QUANT_OPENCV keeps cv2's 1/32-px fixed point (sx, sy), QUANT_EXACT the
+// float32 coordinate itself (as bits).  The top-left tap and the fraction are derived where they are used.
+struct C3Pos { int x, y; };
 
 struct C3Tap {
     int   ax, ay;         // "fraction is non-zero" indicators for the validity test
@@ -103,21 +110,30 @@ __device__ __forceinline__ C3Pos c3_pos(int gx, int gy, float fu, float fv, int 
 {
     const float px = sign >= 0 ? __fadd_rn((float)gx, fu) : __fsub_rn((float)gx, fu);
     const float py = sign >= 0 ? __fadd_rn((float)gy, fv) : __fsub_rn((float)gy, fv);
-    C3Pos p;
-    if (QUANT == OFL_QUANT_OPENCV) {
-        const int sx = cv_round(__fmul_rn(px, 32.0f)), sy = cv_round(__fmul_rn(py, 32.0f));
-        p.ix = sx >> 5; p.iy = sy >> 5;      // unsaturated: beyond +-32767 every tap is outside anyway
-        p.fx = (float)(sx & 31) * (1.0f / 32.0f);
-        p.fy = (float)(sy & 31) * (1.0f / 32.0f);
-    } else {
-        float flx = floorf(px), fly = floorf(py);
-        p.fx = __fsub_rn(px, flx); p.fy = __fsub_rn(py, fly);
-        flx = fminf(fmaxf(flx, -32768.0f), 32767.0f);
-        fly = fminf(fmaxf(fly, -32768.0f), 32767.0f);
-        p.ix = (int)flx; p.iy = (int)fly;
-    }
-    return p;
+    if (QUANT == OFL_QUANT_OPENCV) return { cv_round(__fmul_rn(px, 32.0f)), cv_round(__fmul_rn(py, 32.0f)) };
+    return { __float_as_int(px), __float_as_int(py) };
 }
+
+// top-left tap along one axis
+template <int QUANT>
+__device__ __forceinline__ int c3_tap(int s)
+{
+    if (QUANT == OFL_QUANT_OPENCV) return s >> 5;      // unsaturated: beyond +-32767 every tap is outside anyway
+    return (int)fminf(fmaxf(floorf(__int_as_float(s)), -32768.0f), 32767.0f);
+}
+
+// fractional position along one axis (multiples of 1/32 with cv2's snapping)
+template <int QUANT>
+__device__ __forceinline__ float c3_frac(int s)
+{
+    if (QUANT == OFL_QUANT_OPENCV) return (float)(s & 31) * (1.0f / 32.0f);
+    const float p = __int_as_float(s);
+    return __fsub_rn(p, floorf(p));
+}
+
+// Once a pixel's taps are addressed, QUANT_OPENCV weights need only the two 1/32-px fractions: one register instead of two.
+__device__ __forceinline__ int   c3_pack_frac(const C3Pos &p) { return (p.x & 31) | ((p.y & 31) << 8); }
+__device__ __forceinline__ C3Pos c3_unpack_frac(int f) { return { f & 0xff, f >> 8 }; }
 
 // Bilinear weights from the fractional position; evaluated AFTER the gather has been issued so that
 // they do not occupy registers while the loads are in flight.
@@ -125,11 +141,12 @@ template <int QUANT>
 __device__ __forceinline__ C3Tap c3_weights(const C3Pos &p)
 {
     C3Tap t;
-    t.ax = (QUANT == OFL_QUANT_OPENCV) ? (p.fx != 0.0f) : 1;
-    t.ay = (QUANT == OFL_QUANT_OPENCV) ? (p.fy != 0.0f) : 1;
-    const float x0 = __fsub_rn(1.0f, p.fx), y0 = __fsub_rn(1.0f, p.fy);
-    t.w0 = __fmul_rn(y0, x0); t.w1 = __fmul_rn(y0, p.fx);
-    t.w2 = __fmul_rn(p.fy, x0); t.w3 = __fmul_rn(p.fy, p.fx);
+    const float fx = c3_frac<QUANT>(p.x), fy = c3_frac<QUANT>(p.y);
+    t.ax = (QUANT == OFL_QUANT_OPENCV) ? (fx != 0.0f) : 1;
+    t.ay = (QUANT == OFL_QUANT_OPENCV) ? (fy != 0.0f) : 1;
+    const float x0 = __fsub_rn(1.0f, fx), y0 = __fsub_rn(1.0f, fy);
+    t.w0 = __fmul_rn(y0, x0); t.w1 = __fmul_rn(y0, fx);
+    t.w2 = __fmul_rn(fy, x0); t.w3 = __fmul_rn(fy, fx);
     return t;
 }
 
@@ -163,6 +180,36 @@ struct C3Args {
     int mwpr;              // BITS kernels: 32-bit words per row of the packed mask planes ma / mb / mout (bit x & 31 of word x >> 5); else 0
 };
 
+// The planes of field pair b: wave-uniform bases (scalar registers); everything below adds an offset of type C3Ix to them.
+struct C3Field {
+    const float *fa, *fb; const uint8_t *ma, *mb;
+    float *out; uint8_t *mout;
+};
+
+// Offsets within a field: 32 bits for the byte-mask kernels (the launcher keeps their fields below 4 GiB of vectors, so
+// every address is one scalar base plus one 32-bit VGPR), size_t for the packed-mask ones, which have no generic fallback.
+template <bool BITS> using C3Ix = typename std::conditional<BITS, size_t, uint32_t>::type;
+
+template <typename T, typename Ix>
+__device__ __forceinline__ T *c3_elem(T *base, Ix i)
+{
+    // the byte offset is formed in Ix so that a 32-bit one reaches the address unit as one VGPR next to the scalar base
+    typedef typename std::conditional<std::is_const<T>::value, const char, char>::type C;
+    return reinterpret_cast<T *>(reinterpret_cast<C *>(base) + (Ix)(i * (Ix)sizeof(T)));
+}
+
+// taps (s, s + 1) of a row of a float2 field
+template <typename Ix>
+__device__ __forceinline__ Pair2 c3_pair(const float *fa, Ix s) { return *reinterpret_cast<const Pair2 *>(c3_elem(fa, (Ix)(2 * s))); }
+
+template <bool BITS>
+__device__ __forceinline__ C3Field c3_field(const C3Args &a, int b)
+{
+    const size_t field = (size_t)b * a.H * a.W;
+    const size_t mfield = BITS ? (size_t)b * a.H * a.mwpr * 4 : field;      // BITS: the field's bit planes, rows of mwpr words
+    return { a.fa + 2 * field, a.fb + 2 * field, a.ma + mfield, a.mb + mfield, a.out + 2 * field, a.mout + mfield };
+}
+
 struct C3Stream {          // one lane's share of a tile row of the streamed field fb/mb
     float4   v[2];
     uint32_t m[2];
@@ -172,37 +219,25 @@ struct C3Stat {            // running maxima for the zero-flow predicates of one
     float amax_m, bmax, bmax_m;
 };
 
-// lane (lx, ly) owns the pixel pairs at x = 2*lx and x = 2*kC3LanesX + 2*lx of tile row ly
-__device__ __forceinline__ void c3_tile_coords(const C3Args &a, int tile, int &b, int &y, int (&xg)[2])
-{
-    b = tile / a.tiles_per_field;
-    const int t  = tile - b * a.tiles_per_field;
-    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
-    y = ty * kC3TileH + (threadIdx.x / kC3LanesX);
-    xg[0] = tx * kC3TileW + 2 * (threadIdx.x % kC3LanesX);
-    xg[1] = xg[0] + 2 * kC3LanesX;
-}
-
 template <bool BITS = false>
-__device__ __forceinline__ C3Stream c3_load_stream(const C3Args &a, int tile)
+__device__ __forceinline__ C3Stream c3_load_stream(const C3Args &a, const C3Field &F, int y, const int (&xg)[2])
 {
-    int b, y, xg[2];
-    c3_tile_coords(a, tile, b, y, xg);
-    const size_t base = (size_t)b * a.H * a.W + (size_t)y * a.W;
+    typedef C3Ix<BITS> Ix;
     C3Stream s;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
         s.v[g] = make_float4(0.f, 0.f, 0.f, 0.f);
         s.m[g] = 0;
         if (y < a.H && xg[g] < a.W) {
-            const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(a.fb + 2 * (base + xg[g])));
+            const Ix o = (Ix)y * (Ix)a.W + (Ix)xg[g];
+            const v4f t = __builtin_nontemporal_load(c3_elem(reinterpret_cast<const v4f *>(F.fb), o >> 1));
             s.v[g] = make_float4(t.x, t.y, t.z, t.w);
             if (BITS) {
                 // the pair's two bits (xg is even: both in one word; the 16 lanes of a word read the same address)
-                const uint32_t w = reinterpret_cast<const uint32_t *>(a.mb)[((size_t)b * a.H + y) * a.mwpr + (xg[g] >> 5)] >> (xg[g] & 31);
+                const uint32_t w = reinterpret_cast<const uint32_t *>(F.mb)[(size_t)y * a.mwpr + (xg[g] >> 5)] >> (xg[g] & 31);
                 s.m[g] = (w & 1u) | ((w & 2u) << 7);
             } else {
-                s.m[g] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(a.mb + base + xg[g]));
+                s.m[g] = __builtin_nontemporal_load(c3_elem(reinterpret_cast<const uint16_t *>(F.mb), o >> 1));
             }
         }
     }
@@ -215,32 +250,39 @@ __device__ __forceinline__ void c3_flush_stats(const C3Args &a, int b, const C3S
     // address would serialise at the memory side).  fb: all four predicates, exact.  fa: words 0/1
     // are set when a GATHERED masked vector is non-zero / above threshold -- a certificate that fa
     // is not zero; a clear word means "not observed" and is confirmed by ofl_flow_stats_dev.
+    // The wave asks for the six words it may set in one go (one round trip, not one per word) and stores the clear ones.
     const bool c[6] = { st.amax_m > 0.0f, st.amax_m >= a.th, st.bmax_m > 0.0f, st.bmax_m >= a.th,
                         st.bmax > 0.0f, st.bmax >= a.th };
     const int  slot[6] = { 0, 1, 4, 5, 6, 7 };
-    uint32_t *s = a.stats + (size_t)b * 8;
+    uint32_t need = 0;                        // wave-uniform: bit k = some lane saw predicate k
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const bool any = __ballot(c[k]) != 0ull;
-        if (any && (threadIdx.x & 63) == 0 &&
-            __hip_atomic_load(s + slot[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
-            s[slot[k]] = 1u;
+    for (int k = 0; k < 6; ++k) need |= (__ballot(c[k]) != 0ull) ? 1u << k : 0u;
+    if (need != 0u && (threadIdx.x & 63) == 0) {
+        uint32_t *s = a.stats + (size_t)b * 8;
+        uint32_t seen[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) seen[k] = __hip_atomic_load(s + slot[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            if (((need >> k) & 1u) && seen[k] == 0u) s[slot[k]] = 1u;
     }
 }
 
 // stream out: out = fb + B(fa), mout = mb & valid   (flow_class.py:332-334, 668, 680)
 template <bool STATS, bool BITS = false>
-__device__ __forceinline__ void c3_finish(const C3Args &a, size_t row, const int (&xg)[2], const bool (&act)[2],
+__device__ __forceinline__ void c3_finish(const C3Args &a, const C3Field &F, int y, const int (&xg)[2], const bool (&act)[2],
                                           const float (&bu)[kC3Px], const float (&bv)[kC3Px], const bool (&bm)[kC3Px],
                                           const float (&su)[kC3Px], const float (&sv)[kC3Px], const bool (&ok)[kC3Px],
                                           C3Stat &st)
 {
+    typedef C3Ix<BITS> Ix;
+    const Ix row = (Ix)y * (Ix)a.W;
     if constexpr (BITS) {
         // vectors as in the byte form; the mask leaves as whole words: a wave is two tile rows (lanes 0 .. 31 / 32 .. 63), the
         // ballots of the pairs' even and odd pixels are interleaved by the lanes that store (lane 0 / 16 of a row: the words of
         // pixels 0 .. 31 / 32 .. 63 of the 64-px stretch)
         const int lx = threadIdx.x & 31;
-        const size_t wrow = (row / (size_t)a.W) * (size_t)a.mwpr;       // row = (b * H + y) * W
+        const size_t wrow = (size_t)y * a.mwpr;
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             const int j = 2 * g;
@@ -250,7 +292,7 @@ __device__ __forceinline__ void c3_finish(const C3Args &a, size_t row, const int
                 const float4 o4 = make_float4(__fadd_rn(bu[j], su[j]), __fadd_rn(bv[j], sv[j]),
                                               __fadd_rn(bu[j + 1], su[j + 1]), __fadd_rn(bv[j + 1], sv[j + 1]));
                 const v4f t = { o4.x, o4.y, o4.z, o4.w };
-                __builtin_nontemporal_store(t, reinterpret_cast<v4f *>(a.out + 2 * (row + xg[g])));
+                __builtin_nontemporal_store(t, c3_elem(reinterpret_cast<v4f *>(F.out), (row + xg[g]) >> 1));
                 if (STATS) {
                     const float a0 = fmaxf(fabsf(bu[j]), fabsf(bv[j])), a1 = fmaxf(fabsf(bu[j + 1]), fabsf(bv[j + 1]));
                     st.bmax   = fmaxf(st.bmax, fmaxf(a0, a1));
@@ -261,7 +303,7 @@ __device__ __forceinline__ void c3_finish(const C3Args &a, size_t row, const int
             if ((lx & 15) == 0 && act[g]) {
                 const uint32_t e32 = (uint32_t)(me >> (threadIdx.x & 32)), o32 = (uint32_t)(mo >> (threadIdx.x & 32));
                 const uint32_t word = c3_spread16(e32 >> lx) | (c3_spread16(o32 >> lx) << 1);
-                __builtin_nontemporal_store(word, reinterpret_cast<uint32_t *>(a.mout) + wrow + (xg[g] >> 5));
+                __builtin_nontemporal_store(word, reinterpret_cast<uint32_t *>(F.mout) + wrow + (xg[g] >> 5));
             }
         }
         return;
@@ -276,12 +318,13 @@ __device__ __forceinline__ void c3_finish(const C3Args &a, size_t row, const int
         const uint32_t other = (uint32_t)__shfl_xor((int)mine, 1);
         if (act[g]) {
             const int j = 2 * g;
+            const Ix o = row + (Ix)xg[g];
             const v4f t = { __fadd_rn(bu[j], su[j]), __fadd_rn(bv[j], sv[j]), __fadd_rn(bu[j + 1], su[j + 1]), __fadd_rn(bv[j + 1], sv[j + 1]) };
-            __builtin_nontemporal_store(t, reinterpret_cast<v4f *>(a.out + 2 * (row + xg[g])));
+            __builtin_nontemporal_store(t, c3_elem(reinterpret_cast<v4f *>(F.out), o >> 1));
             if (quad) {
-                if ((threadIdx.x & 1) == 0) __builtin_nontemporal_store(mine | (other << 16), reinterpret_cast<uint32_t *>(a.mout + row + xg[g]));
+                if ((threadIdx.x & 1) == 0) __builtin_nontemporal_store(mine | (other << 16), c3_elem(reinterpret_cast<uint32_t *>(F.mout), o >> 2));
             } else {
-                __builtin_nontemporal_store((uint16_t)mine, reinterpret_cast<uint16_t *>(a.mout + row + xg[g]));
+                __builtin_nontemporal_store((uint16_t)mine, c3_elem(reinterpret_cast<uint16_t *>(F.mout), o >> 1));
             }
             if (STATS) {
                 const float a0 = fmaxf(fabsf(bu[j]), fabsf(bv[j])), a1 = fmaxf(fabsf(bu[j + 1]), fabsf(bv[j + 1]));
@@ -292,34 +335,83 @@ __device__ __forceinline__ void c3_finish(const C3Args &a, size_t row, const int
     }
 }
 
-// One tile: taps from the already loaded stream data, gather, blend, store.
-template <int QUANT, bool STATS, bool BITS = false>
-__device__ __forceinline__ void c3_tile(const C3Args &a, int tile, const C3Stream &in, C3Stat &st)
+// One pixel whose taps may lie partly outside the source: clamp the addresses, zero the taps that fall outside (cv2
+// BORDER_CONSTANT 0).  `v` holds the pixel's sampling vector on entry and B(fa) on return, `k` its validity: the border
+// paths run one pixel per loop trip through LDS slots so that this rare path does not set the kernel's register budget.
+template <int QUANT, bool STATS, bool BITS>
+__device__ __forceinline__ void c3_border_px(const C3Args &a, const C3Field &F, int gx, int gy, bool act,
+                                             float2 &v, uint8_t &k, C3Stat &st)
 {
-    int b, y, xg[2];
-    c3_tile_coords(a, tile, b, y, xg);
-    const int H = a.H, W = a.W, sign = a.sign;
-    const size_t field = (size_t)b * H * W;
-    const float   *fa = a.fa + field * 2;
-    const uint8_t *ma = BITS ? a.ma + (size_t)b * H * a.mwpr * 4 : a.ma + field;      // BITS: the field's bit plane, rows of mwpr words
-    const int      mrow = a.mwpr * 4;                                                  // ... and its row pitch in bytes
-    const bool act[2] = { y < H && xg[0] < W, y < H && xg[1] < W };
-    const size_t row = field + (size_t)y * W;
+    typedef C3Ix<BITS> Ix;
+    const int H = a.H, W = a.W;
+    const int mrow = a.mwpr * 4;              // BITS: row pitch of the bit planes in bytes
+    const C3Pos p = c3_pos<QUANT>(gx, gy, v.x, v.y, a.sign);
+    const int  ix  = c3_tap<QUANT>(p.x), iy = c3_tap<QUANT>(p.y);
+    const int  ixc = min(max(ix, 0), max(W - 2, 0));
+    const int  d   = ix - ixc;
+    const bool r0  = (unsigned)iy < (unsigned)H;
+    const bool r1  = (unsigned)(iy + 1) < (unsigned)H;
+    const int  y0c = min(max(iy, 0), H - 1);
+    const int  y1c = min(max(iy + 1, 0), H - 1);
+    const Ix s0 = (Ix)y0c * (Ix)W + (Ix)ixc, s1 = (Ix)y1c * (Ix)W + (Ix)ixc;
+    const Pair2 p0 = c3_pair(F.fa, s0);
+    const Pair2 p1 = c3_pair(F.fa, s1);
+    uint32_t q00, q01, q10, q11;
+    if (BITS) {
+        const uint8_t *r0p = F.ma + (size_t)y0c * mrow, *r1p = F.ma + (size_t)y1c * mrow;
+        q00 = c3_bit(r0p, ixc); q01 = c3_bit(r0p, min(ixc + 1, W - 1)); q10 = c3_bit(r1p, ixc); q11 = c3_bit(r1p, min(ixc + 1, W - 1));
+    } else {
+        q00 = *c3_elem(F.ma, s0); q01 = *c3_elem(F.ma, s0 + 1); q10 = *c3_elem(F.ma, s1); q11 = *c3_elem(F.ma, s1 + 1);
+    }
+    float u00, v00, u01, v01, u10, v10, u11, v11, a00, a01, a10, a11;
+    select_pair(p0, d, r0, u00, v00, u01, v01);
+    select_pair(p1, d, r1, u10, v10, u11, v11);
+    select_mask(q00, q01, d, r0, a00, a01);
+    select_mask(q10, q11, d, r1, a10, a11);
+    const C3Tap w = c3_weights<QUANT>(p);
+    v = make_float2(c3_blend(u00, u01, u10, u11, w), c3_blend(v00, v01, v10, v11, w));
+    k = c3_valid<QUANT>(a00 != 0.0f, a01 != 0.0f, a10 != 0.0f, a11 != 0.0f, w) ? 1 : 0;
+    if (STATS) st.amax_m = fmaxf(st.amax_m, (a00 != 0.0f && act) ? fmaxf(fabsf(u00), fabsf(v00)) : 0.0f);
+}
 
-    const float bu[kC3Px] = { in.v[0].x, in.v[0].z, in.v[1].x, in.v[1].z };
-    const float bv[kC3Px] = { in.v[0].y, in.v[0].w, in.v[1].y, in.v[1].w };
+// interior and outside tests of one pixel's taps, accumulated over a lane's pixels
+template <int QUANT>
+__device__ __forceinline__ void c3_classify(const C3Pos &p, int H, int W, bool act, bool &inside, bool &outside)
+{
+    const int ix = c3_tap<QUANT>(p.x), iy = c3_tap<QUANT>(p.y);
+    const bool in_j  = (unsigned)ix <= (unsigned)(W - 2) && (unsigned)iy <= (unsigned)(H - 2);
+    const bool out_j = ix < -1 || ix >= W || iy < -1 || iy >= H;
+    inside  = inside && (in_j || !act);
+    outside = outside && (out_j || !act);
+}
+
+constexpr int kXpRowF2 = 128 + 4;             // LDS row stride in float2 (padding spreads the 8 rows over the banks)
+constexpr int kXposeRows = 6;                 // source rows one streamed 128-px segment may cross before we transpose
+
+// One tile in the streaming layout: taps from the already loaded stream data, gather, blend, store.
+template <int QUANT, bool STATS, bool BITS = false>
+__device__ __forceinline__ void c3_tile(const C3Args &a, const C3Field &F, int y, const int (&xg)[2], const bool (&act)[2],
+                                        const C3Stream &in, float2 *xp_v, uint8_t *xp_ok, C3Stat &st)
+{
+    typedef C3Ix<BITS> Ix;
+    const int H = a.H, W = a.W, sign = a.sign;
+    const int mrow = a.mwpr * 4;              // BITS: row pitch of the bit planes in bytes
+
+    float       bu[kC3Px] = { in.v[0].x, in.v[0].z, in.v[1].x, in.v[1].z };
+    float       bv[kC3Px] = { in.v[0].y, in.v[0].w, in.v[1].y, in.v[1].w };
     const bool  bm[kC3Px] = { (in.m[0] & 0xffu) != 0, (in.m[0] & 0xff00u) != 0,
                               (in.m[1] & 0xffu) != 0, (in.m[1] & 0xff00u) != 0 };
+    // this lane's own LDS slots (the tile's transposition buffer, unused in the streaming layout; no other lane touches
+    // them, so no barrier)
+    float2  *v = xp_v + (threadIdx.x >> 5) * kXpRowF2 + 2 * (threadIdx.x & 31);
+    uint8_t *k = xp_ok + (threadIdx.x >> 5) * 128 + 2 * (threadIdx.x & 31);
 
     C3Pos tp[kC3Px];
     bool inside = true, outside = true;
 #pragma unroll
     for (int j = 0; j < kC3Px; ++j) {
         tp[j] = c3_pos<QUANT>(xg[j >> 1] + (j & 1), y, bu[j], bv[j], sign);
-        const bool in_j  = (unsigned)tp[j].ix <= (unsigned)(W - 2) && (unsigned)tp[j].iy <= (unsigned)(H - 2);
-        const bool out_j = tp[j].ix < -1 || tp[j].ix >= W || tp[j].iy < -1 || tp[j].iy >= H;
-        inside  = inside && (in_j || !act[j >> 1]);
-        outside = outside && (out_j || !act[j >> 1]);
+        c3_classify<QUANT>(tp[j], H, W, act[j >> 1], inside, outside);
     }
     if (H < 2) inside = false;
 
@@ -331,7 +423,10 @@ __device__ __forceinline__ void c3_tile(const C3Args &a, int tile, const C3Strea
     if (__all(outside)) {
         // every tap of every pixel of this wave lies outside the source: B(.) = 0, nothing to fetch
     } else if (__all(inside)) {
-        // interior fast path: all four taps in bounds, no clamping and no selects
+        // interior fast path: all four taps in bounds, no clamping and no selects.  The streamed vectors wait in LDS
+        // while the gather is in flight (8 VGPRs of the 64).
+        *reinterpret_cast<float4 *>(v)      = in.v[0];
+        *reinterpret_cast<float4 *>(v + 64) = in.v[1];
         Pair2    p0[kC3Px], p1[kC3Px];
         uint32_t m0[kC3Px], m1[kC3Px];
         // The two pixels of a pair usually sample the same two source rows at columns at most two apart (axis-aligned
@@ -339,46 +434,65 @@ __device__ __forceinline__ void c3_tile(const C3Args &a, int tile, const C3Strea
         // 4-byte load per row and pair instead of one 2-byte load per row and pixel (4 instead of 8 mask gathers per lane).
         bool share = true;
 #pragma unroll
-        for (int g = 0; g < 2; ++g)
-            share = share && (!act[g] || (tp[2 * g].iy == tp[2 * g + 1].iy && (unsigned)(tp[2 * g + 1].ix - tp[2 * g].ix) <= 2u &&
-                                          tp[2 * g].ix + 3 < W));
+        for (int g = 0; g < 2; ++g) {
+            const int ix0 = c3_tap<QUANT>(tp[2 * g].x), ix1 = c3_tap<QUANT>(tp[2 * g + 1].x);
+            share = share && (!act[g] || (c3_tap<QUANT>(tp[2 * g].y) == c3_tap<QUANT>(tp[2 * g + 1].y) &&
+                                          (unsigned)(ix1 - ix0) <= 2u && ix0 + 3 < W));
+        }
         share = __all(share);
+        Ix  s[kC3Px];                         // top-left taps as offsets in the field
+        int fr[kC3Px];                        // QUANT_OPENCV: all the weights need once the taps are addressed (c3_pack_frac)
+        // the second tap row through second scalar bases: all four loads of a pixel take the same 32-bit offset register
+        const float   *fa1 = F.fa + 2 * (size_t)W;
+        const uint8_t *ma1 = F.ma + (BITS ? (size_t)mrow : (size_t)W);
 #pragma unroll
         for (int j = 0; j < kC3Px; ++j) {
-            const size_t s0 = act[j >> 1] ? (size_t)tp[j].iy * W + tp[j].ix : 0;
-            p0[j] = *reinterpret_cast<const Pair2 *>(fa + 2 * s0);
-            p1[j] = *reinterpret_cast<const Pair2 *>(fa + 2 * (s0 + W));
+            const int ix = act[j >> 1] ? c3_tap<QUANT>(tp[j].x) : 0, iy = act[j >> 1] ? c3_tap<QUANT>(tp[j].y) : 0;
+            s[j] = (Ix)iy * (Ix)W + (Ix)ix;
+            fr[j] = c3_pack_frac(tp[j]);
             if (BITS) {
                 // bits 0 / 1 = taps ix / ix + 1 (bits 2, 3 serve the pair's other pixel when it shares the load)
                 if (share && (j & 1)) {
-                    const int sh = act[j >> 1] ? tp[j].ix - tp[j - 1].ix : 0;
+                    const int sh = act[j >> 1] ? c3_tap<QUANT>(tp[j].x) - c3_tap<QUANT>(tp[j - 1].x) : 0;
                     m0[j] = m0[j - 1] >> sh;
                     m1[j] = m1[j - 1] >> sh;
                 } else {
-                    const uint8_t *r0 = ma + (size_t)(act[j >> 1] ? tp[j].iy : 0) * mrow;
-                    const int ix = act[j >> 1] ? tp[j].ix : 0;
-                    m0[j] = c3_bits_at(r0, ix);
-                    m1[j] = c3_bits_at(r0 + mrow, ix);
+                    const size_t r0 = (size_t)iy * mrow;
+                    m0[j] = c3_bits_at(F.ma + r0, ix);
+                    m1[j] = c3_bits_at(ma1 + r0, ix);
                 }
-                continue;
             }
+        }
+        // mask taps first, so that their addresses are spent before the vector taps occupy their registers
+        if constexpr (!BITS) {
             if (share) {
-                if ((j & 1) == 0) {
-                    m0[j] = reinterpret_cast<const U32u *>(ma + s0)->v;
-                    m1[j] = reinterpret_cast<const U32u *>(ma + s0 + W)->v;
-                } else {
-                    const int sh = act[j >> 1] ? 8 * (tp[j].ix - tp[j - 1].ix) : 0;
+#pragma unroll
+                for (int j = 0; j < kC3Px; j += 2) {
+                    m0[j] = reinterpret_cast<const U32u *>(c3_elem(F.ma, s[j]))->v;
+                    m1[j] = reinterpret_cast<const U32u *>(c3_elem(ma1, s[j]))->v;
+                }
+#pragma unroll
+                for (int j = 1; j < kC3Px; j += 2) {
+                    const int sh = 8 * (int)(s[j] - s[j - 1]);      // same row: the column step (0 for a pair outside the field)
                     m0[j] = m0[j - 1] >> sh;
                     m1[j] = m1[j - 1] >> sh;
                 }
             } else {
-                m0[j] = (uint32_t)ma[s0] | ((uint32_t)ma[s0 + 1] << 8);
-                m1[j] = (uint32_t)ma[s0 + W] | ((uint32_t)ma[s0 + W + 1] << 8);
+#pragma unroll
+                for (int j = 0; j < kC3Px; ++j) {
+                    m0[j] = reinterpret_cast<const U16u *>(c3_elem(F.ma, s[j]))->v;
+                    m1[j] = reinterpret_cast<const U16u *>(c3_elem(ma1, s[j]))->v;
+                }
             }
         }
 #pragma unroll
         for (int j = 0; j < kC3Px; ++j) {
-            const C3Tap w = c3_weights<QUANT>(tp[j]);
+            p0[j] = c3_pair(F.fa, s[j]);
+            p1[j] = c3_pair(fa1, s[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < kC3Px; ++j) {
+            const C3Tap w = c3_weights<QUANT>(QUANT == OFL_QUANT_OPENCV ? c3_unpack_frac(fr[j]) : tp[j]);
             su[j] = c3_blend(p0[j].lo_u, p0[j].hi_u, p1[j].lo_u, p1[j].hi_u, w);
             sv[j] = c3_blend(p0[j].lo_v, p0[j].hi_v, p1[j].lo_v, p1[j].hi_v, w);
             const bool m00 = (m0[j] & (BITS ? 1u : 0xffu)) != 0, m01 = (m0[j] & (BITS ? 2u : 0xff00u)) != 0;
@@ -386,38 +500,26 @@ __device__ __forceinline__ void c3_tile(const C3Args &a, int tile, const C3Strea
             ok[j] = c3_valid<QUANT>(m00, m01, m10, m11, w);
             if (STATS) st.amax_m = fmaxf(st.amax_m, (m00 && act[j >> 1]) ? fmaxf(fabsf(p0[j].lo_u), fabsf(p0[j].lo_v)) : 0.0f);
         }
+        const float4 b01 = *reinterpret_cast<const float4 *>(v), b23 = *reinterpret_cast<const float4 *>(v + 64);
+        bu[0] = b01.x; bu[1] = b01.z; bu[2] = b23.x; bu[3] = b23.z;
+        bv[0] = b01.y; bv[1] = b01.w; bv[2] = b23.y; bv[3] = b23.w;
     } else {
-        // border path: clamp the addresses, zero the taps that fall outside (cv2 BORDER_CONSTANT 0)
-#pragma unroll
+        // border path, one pixel per trip through the lane's LDS slots
+        *reinterpret_cast<float4 *>(v)      = in.v[0];
+        *reinterpret_cast<float4 *>(v + 64) = in.v[1];
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
         for (int j = 0; j < kC3Px; ++j) {
-            const int  ixc = min(max(tp[j].ix, 0), max(W - 2, 0));
-            const int  d   = tp[j].ix - ixc;
-            const bool r0  = (unsigned)tp[j].iy < (unsigned)H;
-            const bool r1  = (unsigned)(tp[j].iy + 1) < (unsigned)H;
-            const int  y0c = min(max(tp[j].iy, 0), H - 1);
-            const int  y1c = min(max(tp[j].iy + 1, 0), H - 1);
-            const size_t s0 = (size_t)y0c * W + ixc, s1 = (size_t)y1c * W + ixc;
-            const Pair2 p0 = *reinterpret_cast<const Pair2 *>(fa + 2 * s0);
-            const Pair2 p1 = *reinterpret_cast<const Pair2 *>(fa + 2 * s1);
-            uint32_t q00, q01, q10, q11;
-            if (BITS) {
-                const uint8_t *r0p = ma + (size_t)y0c * mrow, *r1p = ma + (size_t)y1c * mrow;
-                q00 = c3_bit(r0p, ixc); q01 = c3_bit(r0p, min(ixc + 1, W - 1)); q10 = c3_bit(r1p, ixc); q11 = c3_bit(r1p, min(ixc + 1, W - 1));
-            } else { q00 = ma[s0]; q01 = ma[s0 + 1]; q10 = ma[s1]; q11 = ma[s1 + 1]; }
-            float u00, v00, u01, v01, u10, v10, u11, v11, a00, a01, a10, a11;
-            select_pair(p0, d, r0, u00, v00, u01, v01);
-            select_pair(p1, d, r1, u10, v10, u11, v11);
-            select_mask(q00, q01, d, r0, a00, a01);
-            select_mask(q10, q11, d, r1, a10, a11);
-            const C3Tap w = c3_weights<QUANT>(tp[j]);
-            su[j] = c3_blend(u00, u01, u10, u11, w);
-            sv[j] = c3_blend(v00, v01, v10, v11, w);
-            ok[j] = c3_valid<QUANT>(a00 != 0.0f, a01 != 0.0f, a10 != 0.0f, a11 != 0.0f, w);
-            if (STATS) st.amax_m = fmaxf(st.amax_m, (a00 != 0.0f && act[j >> 1]) ? fmaxf(fabsf(u00), fabsf(v00)) : 0.0f);
+            const int o = (j & 1) + 64 * (j >> 1);
+            c3_border_px<QUANT, STATS, BITS>(a, F, xg[0] + o, y, y < H && xg[0] + o < W, v[o], k[o], st);
         }
+        const float4 s01 = *reinterpret_cast<const float4 *>(v), s23 = *reinterpret_cast<const float4 *>(v + 64);
+        const uint32_t k01 = *reinterpret_cast<const uint16_t *>(k), k23 = *reinterpret_cast<const uint16_t *>(k + 64);
+        su[0] = s01.x; su[1] = s01.z; su[2] = s23.x; su[3] = s23.z;
+        sv[0] = s01.y; sv[1] = s01.w; sv[2] = s23.y; sv[3] = s23.w;
+        ok[0] = (k01 & 0xffu) != 0; ok[1] = (k01 & 0xff00u) != 0; ok[2] = (k23 & 0xffu) != 0; ok[3] = (k23 & 0xff00u) != 0;
     }
 
-    c3_finish<STATS, BITS>(a, row, xg, act, bu, bv, bm, su, sv, ok, st);
+    c3_finish<STATS, BITS>(a, F, y, xg, act, bu, bv, bm, su, sv, ok, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -428,91 +530,69 @@ __device__ __forceinline__ void c3_tile(const C3Args &a, int tile, const C3Strea
 // their sampling vectors through LDS to a BLOCK layout (a wave = 32 px x 8 rows, every gather instruction one 8 x 8
 // block of it), gather and blend there (~15 lines per instruction), and hand the results back for the streaming stores.  Same arithmetic
 // per pixel, bit-identical results; axis-aligned fields keep the direct path.
-constexpr int kXpRowF2 = 128 + 4;             // LDS row stride in float2 (padding spreads the 8 rows over the banks)
-constexpr int kXposeRows = 6;                 // source rows one streamed 128-px segment may cross before we transpose
-
+//
+// Block layout, lane (r, c) of wave w: pixel j at row r, column 32 w + c + 8 j, whose LDS slot holds its sampling vector on
+// entry and B(fa) / validity on return.
 template <int QUANT, bool STATS, bool BITS = false>
-__device__ __forceinline__ void c3_sample_block(const C3Args &a, const float *__restrict__ fa, const uint8_t *__restrict__ ma,
-                                                const int (&gx)[4], int gy, const float (&fu)[4], const float (&fv)[4],
-                                                float (&su)[4], float (&sv)[4], bool (&ok)[4], C3Stat &st)
+__device__ __forceinline__ void c3_sample_block(const C3Args &a, const C3Field &F, int gx0, int gy,
+                                                float2 *v, uint8_t *k, C3Stat &st)
 {
+    typedef C3Ix<BITS> Ix;
     const int H = a.H, W = a.W;
-    const int mrow = a.mwpr * 4;              // BITS: `ma` is the field's bit plane, rows of mwpr words
+    const int mrow = a.mwpr * 4;              // BITS: row pitch of the bit planes in bytes
     C3Pos tp[4];
-    bool act[4], inside = true, outside = true;
+    bool inside = true, outside = true;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        act[j] = gy < H && gx[j] < W;
-        tp[j] = c3_pos<QUANT>(gx[j], gy, fu[j], fv[j], a.sign);
-        const bool in_j  = (unsigned)tp[j].ix <= (unsigned)(W - 2) && (unsigned)tp[j].iy <= (unsigned)(H - 2);
-        const bool out_j = tp[j].ix < -1 || tp[j].ix >= W || tp[j].iy < -1 || tp[j].iy >= H;
-        inside  = inside && (in_j || !act[j]);
-        outside = outside && (out_j || !act[j]);
-        su[j] = 0.0f; sv[j] = 0.0f; ok[j] = false;
+        const float2 f = v[8 * j];
+        tp[j] = c3_pos<QUANT>(gx0 + 8 * j, gy, f.x, f.y, a.sign);
+        c3_classify<QUANT>(tp[j], H, W, gy < H && gx0 + 8 * j < W, inside, outside);
     }
     if (H < 2) inside = false;
-    if (__all(outside)) return;
+    if (__all(outside)) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { v[8 * j] = make_float2(0.0f, 0.0f); k[8 * j] = 0; }
+        return;
+    }
     if (__all(inside)) {
         Pair2    p0[4], p1[4];
         uint32_t m0[4], m1[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const size_t s0 = act[j] ? (size_t)tp[j].iy * W + tp[j].ix : 0;
-            p0[j] = *reinterpret_cast<const Pair2 *>(fa + 2 * s0);
-            p1[j] = *reinterpret_cast<const Pair2 *>(fa + 2 * (s0 + W));
+            const bool act = gy < H && gx0 + 8 * j < W;
+            const int ix = act ? c3_tap<QUANT>(tp[j].x) : 0, iy = act ? c3_tap<QUANT>(tp[j].y) : 0;
+            const Ix s0 = (Ix)iy * (Ix)W + (Ix)ix;
+            p0[j] = c3_pair(F.fa, s0);
+            p1[j] = c3_pair(F.fa, (Ix)(s0 + (Ix)W));
             if (BITS) {
-                const uint8_t *r0 = ma + (size_t)(act[j] ? tp[j].iy : 0) * mrow;
-                const int ix = act[j] ? tp[j].ix : 0;
+                const uint8_t *r0 = F.ma + (size_t)iy * mrow;
                 m0[j] = c3_bits_at(r0, ix);
                 m1[j] = c3_bits_at(r0 + mrow, ix);
             } else {
-                m0[j] = (uint32_t)ma[s0] | ((uint32_t)ma[s0 + 1] << 8);
-                m1[j] = (uint32_t)ma[s0 + W] | ((uint32_t)ma[s0 + W + 1] << 8);
+                m0[j] = reinterpret_cast<const U16u *>(c3_elem(F.ma, s0))->v;
+                m1[j] = reinterpret_cast<const U16u *>(c3_elem(F.ma, s0 + (Ix)W))->v;
             }
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const C3Tap w = c3_weights<QUANT>(tp[j]);
-            su[j] = c3_blend(p0[j].lo_u, p0[j].hi_u, p1[j].lo_u, p1[j].hi_u, w);
-            sv[j] = c3_blend(p0[j].lo_v, p0[j].hi_v, p1[j].lo_v, p1[j].hi_v, w);
+            v[8 * j] = make_float2(c3_blend(p0[j].lo_u, p0[j].hi_u, p1[j].lo_u, p1[j].hi_u, w),
+                                   c3_blend(p0[j].lo_v, p0[j].hi_v, p1[j].lo_v, p1[j].hi_v, w));
             const bool m00 = (m0[j] & (BITS ? 1u : 0xffu)) != 0, m01 = (m0[j] & (BITS ? 2u : 0xff00u)) != 0;
             const bool m10 = (m1[j] & (BITS ? 1u : 0xffu)) != 0, m11 = (m1[j] & (BITS ? 2u : 0xff00u)) != 0;
-            ok[j] = c3_valid<QUANT>(m00, m01, m10, m11, w);
-            if (STATS) st.amax_m = fmaxf(st.amax_m, (m00 && act[j]) ? fmaxf(fabsf(p0[j].lo_u), fabsf(p0[j].lo_v)) : 0.0f);
+            k[8 * j] = c3_valid<QUANT>(m00, m01, m10, m11, w) ? 1 : 0;
+            const bool act = gy < H && gx0 + 8 * j < W;
+            if (STATS) st.amax_m = fmaxf(st.amax_m, (m00 && act) ? fmaxf(fabsf(p0[j].lo_u), fabsf(p0[j].lo_v)) : 0.0f);
         }
         return;
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {       // border path, as in c3_tile
-        const int  ixc = min(max(tp[j].ix, 0), max(W - 2, 0));
-        const int  d   = tp[j].ix - ixc;
-        const bool r0  = (unsigned)tp[j].iy < (unsigned)H;
-        const bool r1  = (unsigned)(tp[j].iy + 1) < (unsigned)H;
-        const int  y0c = min(max(tp[j].iy, 0), H - 1);
-        const int  y1c = min(max(tp[j].iy + 1, 0), H - 1);
-        const size_t s0 = (size_t)y0c * W + ixc, s1 = (size_t)y1c * W + ixc;
-        const Pair2 p0 = *reinterpret_cast<const Pair2 *>(fa + 2 * s0);
-        const Pair2 p1 = *reinterpret_cast<const Pair2 *>(fa + 2 * s1);
-        uint32_t q00, q01, q10, q11;
-        if (BITS) {
-            const uint8_t *r0p = ma + (size_t)y0c * mrow, *r1p = ma + (size_t)y1c * mrow;
-            q00 = c3_bit(r0p, ixc); q01 = c3_bit(r0p, min(ixc + 1, W - 1)); q10 = c3_bit(r1p, ixc); q11 = c3_bit(r1p, min(ixc + 1, W - 1));
-        } else { q00 = ma[s0]; q01 = ma[s0 + 1]; q10 = ma[s1]; q11 = ma[s1 + 1]; }
-        float u00, v00, u01, v01, u10, v10, u11, v11, a00, a01, a10, a11;
-        select_pair(p0, d, r0, u00, v00, u01, v01);
-        select_pair(p1, d, r1, u10, v10, u11, v11);
-        select_mask(q00, q01, d, r0, a00, a01);
-        select_mask(q10, q11, d, r1, a10, a11);
-        const C3Tap w = c3_weights<QUANT>(tp[j]);
-        su[j] = c3_blend(u00, u01, u10, u11, w);
-        sv[j] = c3_blend(v00, v01, v10, v11, w);
-        ok[j] = c3_valid<QUANT>(a00 != 0.0f, a01 != 0.0f, a10 != 0.0f, a11 != 0.0f, w);
-        if (STATS) st.amax_m = fmaxf(st.amax_m, (a00 != 0.0f && act[j]) ? fmaxf(fabsf(u00), fabsf(v00)) : 0.0f);
-    }
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (int j = 0; j < 4; ++j)               // border path, as in c3_tile
+        c3_border_px<QUANT, STATS, BITS>(a, F, gx0 + 8 * j, gy, gy < H && gx0 + 8 * j < W, v[8 * j], k[8 * j], st);
 }
 
-constexpr int kC3Waves = 6;                   // waves per SIMD the register allocator is asked to leave room for
-constexpr int kC3BitsWaves = 5;               // the packed-mask form needs a few registers more than the 6-wave budget leaves (11 spilled there)
+constexpr int kC3Waves = 6;                   // waves per SIMD the register allocator is asked to leave room for (7 and 8 spill and are slower: HISTORY, round 5)
+constexpr int kC3BitsWaves = 5;               // the packed-mask form needs a few registers more than the 6-wave budget leaves
 template <int QUANT, bool STATS, bool BITS = false>      // BITS: the three masks are packed bit planes (ofl_compose3_bits_dev)
 __global__ __launch_bounds__(256, BITS ? kC3BitsWaves : kC3Waves)
 void compose3_xpose_kernel(const C3Args a)
@@ -522,54 +602,41 @@ void compose3_xpose_kernel(const C3Args a)
     __shared__ __attribute__((aligned(16))) uint8_t xp_ok[8 * 128];
     const int tile = blockIdx.x;          // natural tile order (XCD-aware orders were measured slower)
     if (tile >= a.ntiles) return;
-    C3Stat st = { 0.0f, 0.0f, 0.0f };
-    const C3Stream in = c3_load_stream<BITS>(a, tile);
-    int b, y, xg[2];
-    c3_tile_coords(a, tile, b, y, xg);
     const int H = a.H, W = a.W;
+    // lane (lx, ly) owns the pixel pairs at x = 2*lx and x = 2*kC3LanesX + 2*lx of tile row ly
+    const int b   = tile / a.tiles_per_field;
+    const int t   = tile - b * a.tiles_per_field;
+    const int ty  = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const int ly  = threadIdx.x >> 5, lx = threadIdx.x & 31;
+    const int y   = ty * kC3TileH + ly;
+    const int xg[2] = { tx * kC3TileW + 2 * lx, tx * kC3TileW + 2 * lx + 2 * kC3LanesX };
     const bool act[2] = { y < H && xg[0] < W, y < H && xg[1] < W };
+    const C3Field F = c3_field<BITS>(a, b);
+    C3Stat st = { 0.0f, 0.0f, 0.0f };
+    const C3Stream in = c3_load_stream<BITS>(a, F, y, xg);
     // Does a streamed row segment of this tile cross many source rows (sample row = y -/+ v)?  Every wave answers from
     // the SAME two values -- the vertical flow at the two ends of the tile's first row (uniform loads, L2 hits) -- so
     // the workgroup agrees without a barrier and the direct path costs nothing extra.
-    const int t   = tile - b * a.tiles_per_field;
-    const int ty  = t / a.tiles_x, tx = t - ty * a.tiles_x;
     bool rotated;
     {
         const int x0 = tx * 128, x1 = min(x0 + 127, W - 1), yy = min(ty * 8, H - 1);
-        const float *frow = a.fb + 2 * ((size_t)b * H * W + (size_t)yy * W);
+        const float *frow = F.fb + 2 * (size_t)yy * W;
         rotated = fabsf(frow[2 * x1 + 1] - frow[2 * x0 + 1]) * 128.0f > (float)(kXposeRows * (x1 - x0 + 1));
     }
     if (!rotated) {
-        c3_tile<QUANT, STATS, BITS>(a, tile, in, st);
-        if (STATS) c3_flush_stats(a, tile / a.tiles_per_field, st);
+        c3_tile<QUANT, STATS, BITS>(a, F, y, xg, act, in, xp_v, xp_ok, st);
+        if (STATS) c3_flush_stats(a, b, st);
         return;
     }
-    const int ly = threadIdx.x >> 5, lx = threadIdx.x & 31;
     // streaming layout -> LDS: the sampling vectors of this lane's two pixel pairs
     *reinterpret_cast<float4 *>(&xp_v[ly * kXpRowF2 + 2 * lx])      = in.v[0];
     *reinterpret_cast<float4 *>(&xp_v[ly * kXpRowF2 + 64 + 2 * lx]) = in.v[1];
     __syncthreads();
     // block layout: wave w owns columns [32 w, 32 w + 32) of all 8 rows, a lane four adjacent pixels
     // every gather INSTRUCTION (fixed j) then covers a compact 8 x 8 block: pixel j of lane (r, c) is column 8 j + c
-    const int w4  = threadIdx.x >> 6, l = threadIdx.x & 63, r = l >> 3, c0 = 32 * w4 + (l & 7);
     {
-        float fu[4], fv[4];
-        int   gx[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float2 f = xp_v[r * kXpRowF2 + c0 + 8 * j];
-            fu[j] = f.x; fv[j] = f.y;
-            gx[j] = tx * 128 + c0 + 8 * j;
-        }
-        float su[4], sv[4];
-        bool  ok[4];
-        const size_t field = (size_t)b * H * W;
-        c3_sample_block<QUANT, STATS, BITS>(a, a.fa + field * 2, BITS ? a.ma + (size_t)b * H * a.mwpr * 4 : a.ma + field, gx, ty * 8 + r, fu, fv, su, sv, ok, st);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            xp_v[r * kXpRowF2 + c0 + 8 * j] = make_float2(su[j], sv[j]);
-            xp_ok[r * 128 + c0 + 8 * j] = ok[j] ? 1 : 0;
-        }
+        const int w4 = threadIdx.x >> 6, l = threadIdx.x & 63, r = l >> 3, c0 = 32 * w4 + (l & 7);
+        c3_sample_block<QUANT, STATS, BITS>(a, F, tx * 128 + c0, ty * 8 + r, &xp_v[r * kXpRowF2 + c0], &xp_ok[r * 128 + c0], st);
     }
     __syncthreads();
     // back in the streaming layout: add, combine the masks, store
@@ -583,10 +650,9 @@ void compose3_xpose_kernel(const C3Args a)
         const float bu[kC3Px] = { in.v[0].x, in.v[0].z, in.v[1].x, in.v[1].z };
         const float bv[kC3Px] = { in.v[0].y, in.v[0].w, in.v[1].y, in.v[1].w };
         const bool  bm[kC3Px] = { (in.m[0] & 0xffu) != 0, (in.m[0] & 0xff00u) != 0, (in.m[1] & 0xffu) != 0, (in.m[1] & 0xff00u) != 0 };
-        const size_t row = (size_t)b * H * W + (size_t)y * W;
-        c3_finish<STATS, BITS>(a, row, xg, act, bu, bv, bm, su, sv, ok, st);
+        c3_finish<STATS, BITS>(a, F, y, xg, act, bu, bv, bm, su, sv, ok, st);
     }
-    if (STATS) c3_flush_stats(a, tile / a.tiles_per_field, st);
+    if (STATS) c3_flush_stats(a, b, st);
 }
 
 // Generic-shape fallback (any W >= 1, one pixel per thread, no vector accesses).
@@ -1432,7 +1498,7 @@ int ofl_compose3_dev(const float *fa, const uint8_t *ma, const float *fb, const 
     hipStream_t s = stream_of(stream);
     const float th = 1e-3f;   // DEFAULT_THRESHOLD, utils.py:22 (compared in float32)
 
-    if (W % 2 == 0) {
+    if (c3_tiled_fits(H, W)) {
         // One workgroup per 128 x 8 tile in natural order -- the dispatcher keeps every wave slot filled and all XCDs sweep
         // one window of memory (measured +2..7 % over a persistent grid at 1..8 4K pairs per launch) -- with the gather
         // transposed through LDS in workgroups whose sampling grid is rotated.
