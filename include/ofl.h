@@ -402,6 +402,39 @@ int ofl_resize_flow_dev(const float *vecs, const uint8_t *mask, int H, int W, in
                         double scale_y, double scale_x, float mul_u, float mul_v,
                         float *out, uint8_t *mout, void *stream);
 
+/* ------------------------------------------------------------------ K7: flow visualisation
+ * Replaces Flow.visualise (flow_class.py:869-951) and visualise_flow (flow_operations.py:274-284): the field as an
+ * HSV / RGB / BGR image, optionally with invalid areas dimmed (V = 180) and the mask border drawn black.  Per pixel:
+ * components with -threshold < c < threshold become 0 (threshold_vectors); magnitude sqrt(u*u + v*v) and angle
+ * (OpenCV 4.x fastAtan2, degrees) in float32; H = mod(angle, 360) / 2, S = clip(float32(mag * 255) / range, 0, 255),
+ * V = 255; a border pixel (mask true, on the image frame or with a mask-false 4-neighbour) gets H = S = V = 0.
+ * hsv bytes are rint(H, S, V); rgb / bgr bytes come from the reference's float64 colour-wheel arithmetic.
+ * Layouts: flow float32 [batch][H][W][2], mask uint8 [batch][H][W] (0/1), out uint8 [batch][H][W][3].
+ *
+ *   ofl_visualise_range_dev  the default scale of every field of the batch, range_out float32[batch] (device):
+ *                            np.percentile(mag, 99) if it is > 0, else max(mag) if that is > 0, else 1
+ *                            (flow_class.py:910-916).  The caller passes the ranks lo <= hi < H * W of the two
+ *                            order statistics NumPy interpolates between and its float32 weight gamma (they depend on
+ *                            H * W only: numpy/lib/_function_base_impl.py, _quantile / _lerp); the kernels find both
+ *                            values exactly (a radix select over the magnitude bits) and apply _lerp in float32.
+ *                            workspace: ofl_visualise_workspace_bytes(H, W, batch) bytes of device memory, no
+ *                            initialisation needed.  flow 8-byte aligned.  Nothing is synchronised.
+ *   ofl_visualise_dev        the image.  range_dev: float32[batch] on the device (from ofl_visualise_range_dev), or
+ *                            NULL -- then range_const (> 0, +inf allowed) serves every field.  mask may be NULL (all
+ *                            valid).  flow 16-byte, mask and out 4-byte aligned.
+ * A field holding NaN / Inf gives an unspecified image but never reads or writes out of bounds.
+ */
+enum { OFL_VIS_HSV = 0, OFL_VIS_RGB = 1, OFL_VIS_BGR = 2 };
+enum {
+    OFL_VIS_SHOW_MASK    = 1,   /* show_mask: V = 180 where the mask is false */
+    OFL_VIS_MASK_BORDERS = 2    /* show_mask_borders: the border of the mask in black */
+};
+int ofl_visualise_workspace_bytes(int H, int W, int batch, size_t *bytes);
+int ofl_visualise_range_dev(const float *flow, int H, int W, int batch, float threshold, size_t lo, size_t hi,
+                            float gamma, void *workspace, size_t workspace_bytes, float *range_out, void *stream);
+int ofl_visualise_dev(const float *flow, const uint8_t *mask, int H, int W, int batch, float threshold,
+                      const float *range_dev, float range_const, int mode, int flags, uint8_t *out, void *stream);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

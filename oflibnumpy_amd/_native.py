@@ -19,6 +19,8 @@ ARITH_NATIVE, ARITH_FLOAT_RNE = 0, 1
 RULE_EQ1, RULE_GE_HALF, RULE_GT_HALF = 0, 1, 2
 SCATTER_ROUND, SCATTER_NEGATE, SCATTER_UNCERTIFIED = 0x100, 0x200, 0x400
 STAT_NONZERO_MASKED, STAT_NONZERO_TH_MASKED, STAT_NONZERO, STAT_NONZERO_TH, STAT_NONFINITE, STAT_MASK_HAS_ZERO = 1, 2, 4, 8, 16, 32
+VIS_HSV, VIS_RGB, VIS_BGR = 0, 1, 2
+VIS_SHOW_MASK, VIS_MASK_BORDERS = 1, 2
 
 
 class MeshCert(ctypes.Structure):
@@ -104,6 +106,9 @@ SIGNATURES = {
     "ofl_grid_offset_dev": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp]),
     "ofl_resize_flow": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _cd, _cd, _cf, _cf, _vp, _vp]),
     "ofl_resize_flow_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _cd, _cd, _cf, _cf, _vp, _vp, _vp]),
+    "ofl_visualise_workspace_bytes": (_ci, [_ci, _ci, _ci, ctypes.POINTER(_cs)]),
+    "ofl_visualise_range_dev": (_ci, [_vp, _ci, _ci, _ci, _cf, _cs, _cs, _cf, _vp, _cs, _vp, _vp]),
+    "ofl_visualise_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _cf, _vp, _cf, _ci, _ci, _vp, _vp]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

@@ -108,6 +108,26 @@ class DeviceFlowBatch:
         return dev.gather_bilinear_batch(images, dtype, channels, h, w, self.n, self.vecs, -1, smask=target_masks, fmask=self.mask,
                                          valid=True, shared_src=shared, shared_smask=shared_masks, quant=quant, arith=arith, rule=rule)
 
+    def visualise(self, mode, show_mask=False, show_mask_borders=False, range_max=None):
+        """self[i].visualise(...) for every i -> DeviceImage uint8 (n, H, W, 3): ONE range select (each field gets its own
+        99th percentile unless `range_max` fixes one scale for all) and ONE render launch, asynchronous."""
+        code, flags, rc = dev.visualise_args(mode, show_mask, show_mask_borders, range_max)
+        h, w = self.shape
+        rng = None
+        if rc is None:
+            rng = dev.DeviceBuffer(4 * self.n)
+            dev.visualise_range_launch(self.vecs, h, w, self.n, rng)
+        img = dev.visualise_launch(self.vecs, self.mask if flags else None, h, w, self.n, code, flags, rng, rc)
+        img.shape = (self.n, h, w, 3)
+        return img
+
+    def visualise_range(self):
+        """float32 array (n,): the default range_max of every field (one synchronisation)."""
+        h, w = self.shape
+        rng = dev.DeviceBuffer(4 * self.n)
+        dev.visualise_range_launch(self.vecs, h, w, self.n, rng)
+        return rng.to_host((self.n,), np.float32)
+
 
 def combine_flows_batch(flows_1, flows_2, ref=None, rank=0, world=1, thresholded=False):
     """Mode-3 composition of many independent pairs.  `flows_1[i] (+) flows_2[i]`; inputs are lists of

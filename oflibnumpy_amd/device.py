@@ -1,7 +1,7 @@
 """HBM-resident flow fields and the device-side flow algebra.
 
 `DeviceFlow` mirrors the hot-path methods of the reference's `Flow` (apply / switch_ref / invert /
-combine_with / valid_target / valid_source / + - neg / is_zero; src/oflibnumpy/flow_class.py) but
+combine_with / valid_target / valid_source / + - neg / is_zero / visualise; src/oflibnumpy/flow_class.py) but
 keeps vectors and mask in GPU memory between operations, so chains such as combine_with(mode=1)
 (1 scatter + 2 gathers, flow_class.py:1369-1370) never cross PCIe.  The host `Flow` class is a thin
 upload -> DeviceFlow op -> download wrapper around this module.
@@ -364,6 +364,70 @@ def compose3_bits_launch(fa_vecs, fa_bits, fb_vecs, fb_bits, sign, shape, out_ve
                                            out_vecs.ptr, out_bits.ptr, sp, stream))
 
 
+_VIS_MODES = {'hsv': nat.VIS_HSV, 'rgb': nat.VIS_RGB, 'bgr': nat.VIS_BGR}
+
+
+def visualise_args(mode, show_mask=False, show_mask_borders=False, range_max=None):
+    """Validation of Flow.visualise's arguments (flow_class.py:887-892, 917-920, 948-951), on the host before any device
+    work: -> (mode code, OFL_VIS_* flags, float32 range or None for the per-field default).  `range_max` must be a
+    Python float or int (bool included, NumPy's float32 not), > 0 and -- beyond the reference -- finite."""
+    if not isinstance(show_mask, bool):
+        raise TypeError("Error visualising flow: show_mask must be a bool, got {}".format(type(show_mask).__name__))
+    if not isinstance(show_mask_borders, bool):
+        raise TypeError("Error visualising flow: show_mask_borders must be a bool, got {}".format(type(show_mask_borders).__name__))
+    rc = None
+    if range_max is not None:
+        if not isinstance(range_max, (float, int)):
+            raise TypeError("Error visualising flow: range_max must be a float or an int, got {}".format(type(range_max).__name__))
+        if range_max <= 0:
+            raise ValueError("Error visualising flow: range_max must be positive, got {}".format(range_max))
+        if isinstance(range_max, float) and not np.isfinite(range_max):
+            raise ValueError("Error visualising flow: range_max must be finite, got {}".format(range_max))
+        with np.errstate(over='ignore'):        # a finite value beyond float32 divides like NumPy's float32 inf
+            rc = np.float32(float(range_max)) if abs(range_max) < 1e300 else np.float32(np.inf)
+    if not isinstance(mode, str) or mode not in _VIS_MODES:
+        raise ValueError("Error visualising flow: mode must be 'rgb', 'bgr' or 'hsv', got {!r}".format(mode))
+    flags = (nat.VIS_SHOW_MASK if show_mask else 0) | (nat.VIS_MASK_BORDERS if show_mask_borders else 0)
+    return _VIS_MODES[mode], flags, rc
+
+
+def percentile_ranks(n, q=99):
+    """(lo, hi, gamma) of np.percentile(a, q) over n float32 values (NumPy 2.x, method 'linear'): the result is
+    _lerp(sorted[lo], sorted[hi], gamma).  NumPy works in the array's dtype: q / float32(100), the virtual index
+    (n - 1) * q and gamma are float32 (numpy/lib/_function_base_impl.py, percentile / _quantile / _get_indexes)."""
+    qq = np.asanyarray(np.true_divide(q, np.float32(100)))
+    vi = np.asanyarray((n - 1) * qq)
+    prev = np.asanyarray(np.floor(vi))
+    if vi >= n - 1:                                      # NumPy then takes the last element twice
+        prev = np.asanyarray(-1.0)
+    prev = prev.astype(np.intp)
+    gamma = np.asanyarray(vi - prev, dtype=vi.dtype)
+    lo = n - 1 if prev < 0 else int(prev)
+    return lo, min(lo + 1, n - 1) if prev >= 0 else lo, np.float32(gamma)
+
+
+def visualise_range_launch(vecs, h, w, batch, out, stream=None):
+    """K7 range select: out (float32[batch] on the device) <- the default range_max of every field, flow_class.py:910-916.
+    Asynchronous."""
+    lo, hi, gamma = percentile_ranks(h * w)
+    nb = ctypes.c_size_t(0)
+    nat.check(_lib().ofl_visualise_workspace_bytes(h, w, batch, ctypes.byref(nb)))
+    ws = DeviceBuffer(nb.value)
+    nat.check(_lib().ofl_visualise_range_dev(vecs.ptr, h, w, batch, np.float32(DEFAULT_THRESHOLD), lo, hi, gamma,
+                                             ws.ptr, ws.nbytes, out.ptr, stream))
+
+
+def visualise_launch(vecs, mask, h, w, batch, mode, flags, range_buf=None, range_const=None, stream=None):
+    """K7 render of `batch` fields -> DeviceImage uint8 (batch, H, W, 3), or (H, W, 3) for batch 1.  The scale comes from
+    range_buf (float32[batch] on the device) or, if that is None, from range_const.  Asynchronous."""
+    shape = (h, w, 3) if batch == 1 else (batch, h, w, 3)
+    img = DeviceImage(DeviceBuffer(batch * h * w * 3), shape, np.uint8)
+    nat.check(_lib().ofl_visualise_dev(vecs.ptr, mask.ptr if mask is not None and flags else None, h, w, batch,
+                                       np.float32(DEFAULT_THRESHOLD), range_buf.ptr if range_buf is not None else None,
+                                       np.float32(1.0 if range_const is None else range_const), mode, flags, img.buf.ptr, stream))
+    return img
+
+
 _STATS_KNOW_MASK = 1 << 30        # private flag in DeviceFlow._stats: STAT_MASK_HAS_ZERO has been evaluated
 
 
@@ -642,6 +706,26 @@ class DeviceFlow:
         nat.check(_lib().ofl_resize_flow_dev(self.vecs.ptr, self.mask.ptr, h, w, ho, wo, 1.0 / fy, 1.0 / fx,
                                              float(np.float32(fx)), float(np.float32(fy)), out.vecs.ptr, out.mask.ptr, None))
         return out
+
+    def visualise(self, mode, show_mask=False, show_mask_borders=False, range_max=None):
+        """Flow.visualise (flow_class.py:869-951) on HBM-resident data -> DeviceImage uint8 (H, W, 3), asynchronous: the
+        default scale (99th percentile of the magnitudes, with the reference's fallbacks) is selected on the device and read
+        there by the render kernel."""
+        code, flags, rc = visualise_args(mode, show_mask, show_mask_borders, range_max)
+        h, w = self.shape
+        rng = None
+        if rc is None:
+            rng = DeviceBuffer(16)
+            visualise_range_launch(self.vecs, h, w, 1, rng)
+        return visualise_launch(self.vecs, self.mask, h, w, 1, code, flags, rng, rc)
+
+    def visualise_range(self):
+        """The range_max visualise() uses by default, as a Python float (one synchronisation): fixes one scale for a
+        sequence of fields."""
+        h, w = self.shape
+        rng = DeviceBuffer(16)
+        visualise_range_launch(self.vecs, h, w, 1, rng)
+        return float(rng.to_host((1,), np.float32)[0])
 
     def _and_mask(self, other):
         """vecs unchanged, mask = self.mask & other.mask (zero-flow identity warp of a Flow target)."""

@@ -8,7 +8,7 @@ use `DeviceFlow` directly.
 
 Next-tier row already widened into: `track` / `track_pts`.
 Dataset loaders (KITTI, Sintel + mask) are host I/O with a small built-in PNG reader.
-Out of scope (not on the hot path): matrix fitting, visualisation.
+Out of scope (not on the hot path): matrix fitting, arrow drawing and display (`visualise_arrows`, `show*`).
 """
 from __future__ import annotations
 
@@ -406,6 +406,17 @@ class Flow(object):
         if not isinstance(thresholded, bool):
             raise TypeError("Error checking whether flow is zero: Thresholded needs to be a boolean")
         return self.to_device().is_zero(thresholded, masked)
+
+    def visualise(self, mode: str, show_mask: bool = None, show_mask_borders: bool = None,
+                  range_max: float = None) -> np.ndarray:
+        """The flow as a uint8 (H, W, 3) 'rgb' / 'bgr' / 'hsv' image: hue = direction, saturation = magnitude over
+        `range_max` (default: the 99th percentile of the magnitudes), invalid areas dimmed with `show_mask`, the mask
+        outline black with `show_mask_borders` (reference flow_class.py:869-951).  A non-finite `range_max` raises
+        ValueError.  Rendered by the device (DeviceFlow.visualise); arguments are checked before any device work."""
+        show_mask = False if show_mask is None else show_mask
+        show_mask_borders = False if show_mask_borders is None else show_mask_borders
+        dev.visualise_args(mode, show_mask, show_mask_borders, range_max)
+        return self.to_device().visualise(mode, show_mask, show_mask_borders, range_max).to_host()
 
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
         """flow_1 (+) flow_2 = flow_3: mode k returns flow_k from the other two (`self` comes first in

@@ -1,6 +1,7 @@
 """Array-in / array-out wrappers over the `Flow` hot-path methods (masks are dropped), with the same
-names and signatures as the reference's src/oflibnumpy/flow_operations.py:70-228.
-The visualisation helpers of that module are display-only and out of scope."""
+names and signatures as the reference's src/oflibnumpy/flow_operations.py:70-284.
+Of its visualisation helpers only the arrow and window ones (visualise_definition, visualise_flow_arrows, show_flow,
+show_flow_arrows) stay out of scope: they are cv2 drawing and GUI work.  visualise_flow renders on the device."""
 from typing import Union
 
 import numpy as np
@@ -8,7 +9,8 @@ import numpy as np
 from .flow_class import Flow
 
 nd = np.ndarray
-__all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding']
+__all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
+           'visualise_flow']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -47,3 +49,8 @@ def valid_source(flow: nd, ref: str) -> nd:
 def get_flow_padding(flow: nd, ref: str) -> list:
     """Padding [top, bottom, left, right] needed to keep every warped pixel (reference flow_operations.py:231-248)."""
     return Flow(flow, ref).get_padding()
+
+
+def visualise_flow(flow: nd, mode: str, range_max: float = None) -> nd:
+    """uint8 (H, W, 3) 'rgb' / 'bgr' / 'hsv' image of a flow array (reference flow_operations.py:274-284)."""
+    return Flow(flow).visualise(mode=mode, range_max=range_max)
