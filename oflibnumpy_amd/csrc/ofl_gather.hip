@@ -244,17 +244,53 @@ __device__ __forceinline__ C3Stream c3_load_stream(const C3Args &a, const C3Fiel
     return s;
 }
 
-__device__ __forceinline__ void c3_flush_stats(const C3Args &a, int b, const C3Stat &st)
+// Flag words of field pair b (set-only, plain idempotent stores; thousands of waves issuing atomics on one address would
+// serialise at the memory side).  fb: all four predicates, exact.  fa: words 0/1 are set when a GATHERED masked vector is
+// non-zero / above threshold -- a certificate that fa is not zero; a clear word means "not observed" and is confirmed by
+// ofl_flow_stats_dev.  Words 2/3 are never touched here.
+//
+// A wave reads the row ONCE, at its top: lane k loads word k & 7 (one instruction on one 32-byte segment), ahead of the stream loads,
+// so that the wait for the stream data covers it, and keeps "which words were clear" as a wave-uniform bit mask (one scalar
+// register) while it makes the stream and gather round trips it makes anyway.  At its end the wave only stores, and only the
+// words it needs that its early copy showed clear: nothing is loaded or waited for after the output stores.  The words
+// never go back to 0 within a launch (the caller zeroes them beforehand), so a stale copy can only show 0 where memory
+// already holds 1, which costs a redundant store of the same value and never a wrong word.
+//
+// The load is a plain, L1-cacheable VECTOR load (measured faster than an agent-scope one, HISTORY round 6): L1 is invalidated
+// at kernel start and a stale line of zeros lives only until the streaming traffic evicts it.  It must not become a scalar
+// load -- the scalar cache would hold the hot line for the whole kernel and every wave would store -- which the per-lane
+// address (lane & 7) rules out.
+__device__ __forceinline__ uint32_t c3_load_flags(const C3Args &a, int b)
 {
-    // Flag words (set-only, plain idempotent stores; thousands of waves issuing atomics on one
-    // address would serialise at the memory side).  fb: all four predicates, exact.  fa: words 0/1
-    // are set when a GATHERED masked vector is non-zero / above threshold -- a certificate that fa
-    // is not zero; a clear word means "not observed" and is confirmed by ofl_flow_stats_dev.
-    // The wave asks for the six words it may set in one go (one round trip, not one per word) and stores the clear ones.
+    // every lane asks for word (lane & 7): no branch around the load, so nothing ties the wait for it to this place
+    return a.stats[(size_t)b * 8 + (threadIdx.x & 7)];
+}
+
+// bit k = word k of the row was clear when the wave read it
+__device__ __forceinline__ uint32_t c3_clear_flags(uint32_t seen) { return (uint32_t)__ballot(seen == 0u) & 0xffu; }
+
+__device__ __forceinline__ void c3_flush_stats(const C3Args &a, int b, const C3Stat &st, uint32_t clear)
+{
+    const bool c[6] = { st.amax_m > 0.0f, st.amax_m >= a.th, st.bmax_m > 0.0f, st.bmax_m >= a.th,
+                        st.bmax > 0.0f, st.bmax >= a.th };
+    uint32_t need = 0;                        // wave-uniform: bit k = some lane saw predicate k
+#pragma unroll
+    for (int k = 0; k < 6; ++k) need |= (__ballot(c[k]) != 0ull) ? 1u << k : 0u;
+    const uint32_t words = ((need & 3u) | ((need >> 2) << 4)) & clear;      // predicates 0 .. 5 live in words 0, 1, 4, 5, 6, 7
+    const uint32_t lane = __lane_id();        // (not threadIdx.x: no vector register has to live to the end of the wave for it)
+    if (lane < 8u && ((words >> lane) & 1u))
+        a.stats[(size_t)b * 8 + lane] = 1u;
+}
+
+// The read-at-the-end form of the same flush (one round trip for the six words, then the stores), kept for the QUANT_EXACT
+// byte-mask instantiation: that kernel sits at exactly the 80 VGPRs of kC3Waves, and with the store-only tail above the
+// register allocator spills two of them in the interior gather, with or without the early read (HISTORY round 6).
+__device__ __forceinline__ void c3_flush_stats_late(const C3Args &a, int b, const C3Stat &st)
+{
     const bool c[6] = { st.amax_m > 0.0f, st.amax_m >= a.th, st.bmax_m > 0.0f, st.bmax_m >= a.th,
                         st.bmax > 0.0f, st.bmax >= a.th };
     const int  slot[6] = { 0, 1, 4, 5, 6, 7 };
-    uint32_t need = 0;                        // wave-uniform: bit k = some lane saw predicate k
+    uint32_t need = 0;
 #pragma unroll
     for (int k = 0; k < 6; ++k) need |= (__ballot(c[k]) != 0ull) ? 1u << k : 0u;
     if (need != 0u && (threadIdx.x & 63) == 0) {
@@ -614,6 +650,9 @@ void compose3_xpose_kernel(const C3Args a)
     const C3Field F = c3_field<BITS>(a, b);
     C3Stat st = { 0.0f, 0.0f, 0.0f };
     const C3Stream in = c3_load_stream<BITS>(a, F, y, xg);
+    constexpr bool early = STATS && (BITS || QUANT != OFL_QUANT_EXACT);      // (c3_flush_stats_late: the one instantiation without)
+    const uint32_t seen = early ? c3_load_flags(a, b) : 1u;      // the field's flag row, in flight with the stream (c3_flush_stats)
+    const uint32_t clear = early ? c3_clear_flags(seen) : 0u;
     // Does a streamed row segment of this tile cross many source rows (sample row = y -/+ v)?  Every wave answers from
     // the SAME two values -- the vertical flow at the two ends of the tile's first row (uniform loads, L2 hits) -- so
     // the workgroup agrees without a barrier and the direct path costs nothing extra.
@@ -625,7 +664,7 @@ void compose3_xpose_kernel(const C3Args a)
     }
     if (!rotated) {
         c3_tile<QUANT, STATS, BITS>(a, F, y, xg, act, in, xp_v, xp_ok, st);
-        if (STATS) c3_flush_stats(a, b, st);
+        if (early) c3_flush_stats(a, b, st, clear); else if (STATS) c3_flush_stats_late(a, b, st);
         return;
     }
     // streaming layout -> LDS: the sampling vectors of this lane's two pixel pairs
@@ -652,7 +691,7 @@ void compose3_xpose_kernel(const C3Args a)
         const bool  bm[kC3Px] = { (in.m[0] & 0xffu) != 0, (in.m[0] & 0xff00u) != 0, (in.m[1] & 0xffu) != 0, (in.m[1] & 0xff00u) != 0 };
         c3_finish<STATS, BITS>(a, F, y, xg, act, bu, bv, bm, su, sv, ok, st);
     }
-    if (STATS) c3_flush_stats(a, b, st);
+    if (early) c3_flush_stats(a, b, st, clear); else if (STATS) c3_flush_stats_late(a, b, st);
 }
 
 // Generic-shape fallback (any W >= 1, one pixel per thread, no vector accesses).
