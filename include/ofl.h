@@ -435,6 +435,78 @@ int ofl_visualise_range_dev(const float *flow, int H, int W, int batch, float th
 int ofl_visualise_dev(const float *flow, const uint8_t *mask, int H, int W, int batch, float threshold,
                       const float *range_dev, float range_const, int mode, int flags, uint8_t *out, void *stream);
 
+/* ------------------------------------------------------------------ K8: fitting a matrix to a flow field
+ * The O(H * W) passes of Flow.matrix (flow_class.py:797-867) and get_flow_matrix (flow_operations.py:251-271): affine
+ * (dof 4 / 6) and homography (dof 8) fitting by least squares, RANSAC or least median.  The tiny linear algebra stays with
+ * the caller (oflibnumpy_amd/matrix_fit.py); parity with OpenCV's estimators is not pinned.
+ *
+ * Correspondences are rebuilt per pixel (col, row) with vector v, in float64 from the float32 vector (exact):
+ *     sign +1 (ref 's'): src = (col, row), dst = src + v        sign -1 (ref 't'): dst = (col, row), src = dst - v
+ * A pixel whose mask byte is 0 is skipped (mask NULL: none is); a non-finite vector is skipped and counted.
+ *
+ * RESIDUAL of a model M (9 doubles, row-major 3x3) at a correspondence (x, y) -> (X, Y), every operation a float64
+ * operation rounded once, in exactly this order, nothing contracted:
+ *     w  = (M[6]*x + M[7]*y) + M[8]
+ *     px = ((M[0]*x + M[1]*y) + M[2]) / w          py = ((M[3]*x + M[4]*y) + M[5]) / w
+ *     dx = px - X                                   dy = py - Y
+ *     r  = float32(dx*dx + dy*dy)                   NaN or Inf (w == 0, overflow) -> +Inf
+ * The float32 r is the quantity that is thresholded (r <= thr), counted and ranked; r >= 0, so its bits sort as uint32.
+ * GATE: the sum entries take gate_model (host, 9 doubles, or NULL = no gate) and gate_thr; only correspondences with
+ * residual(gate_model) <= gate_thr contribute -- "refit on the inliers" is the same kernel as "fit on everything".
+ * Models, origins and normalisations are HOST pointers (they travel as kernel arguments); flow, mask, workspace and
+ * every output are DEVICE pointers.  flow 16-byte, mask 4-byte aligned; H * W < 2^31.  Nothing is synchronised.
+ *
+ * SUMS (device float64): one workgroup per 4096 px writes its partial sums to the workspace -- per thread its <= 19 terms in
+ * pixel order, per wave a six-level butterfly, then ((w0 + w1) + w2) + w3 -- and one thread per sum adds the
+ * ceil(H*W / 4096) partials in order.  No floating-point atomics, a grid that depends on H * W only: two calls on the
+ * same input return the same bits.
+ *   ofl_fit_moments_dev  sums[16]: with v = (x - ox, y - oy, X - ox, Y - oy, 1), origin = (ox, oy): the 15 products
+ *                        v[i]*v[j], i <= j, row by row ((0,0), (0,1), .. (0,4), (1,1), .. (4,4) -- the last is the number
+ *                        of correspondences), then [15] the number of non-finite vectors skipped.
+ *   ofl_fit_dlt_dev      sums[47]: with norm = (cx, cy, s, cX, cY, S) and the normalised x~ = (x - cx)*s, y~ = (y - cy)*s,
+ *                        X~ = (X - cX)*S, Y~ = (Y - cY)*S, the rows a1 = (x~, y~, 1, 0, 0, 0, -(X~*x~), -(X~*y~), -X~),
+ *                        a2 = (0, 0, 0, x~, y~, 1, -(Y~*x~), -(Y~*y~), -Y~): the 45 terms a1[i]*a1[j] + a2[i]*a2[j],
+ *                        i <= j, row by row (L^T L of the direct linear transform), [45] n, [46] non-finite.
+ *   ofl_fit_gn_dev       sums[47] at the homography h = model (normalised coordinates, h[8] held fixed): with
+ *                        w = (h[6]*x~ + h[7]*y~) + h[8], px = ((h[0]*x~ + h[1]*y~) + h[2]) / w, py likewise, rx = px - X~,
+ *                        ry = py - Y~, j1 = (x~/w, y~/w, 1/w, 0, 0, 0, -(x~*px)/w, -(y~*px)/w),
+ *                        j2 = (0, 0, 0, x~/w, y~/w, 1/w, -(x~*py)/w, -(y~*py)/w): [0..36) j1[i]*j1[j] + j2[i]*j2[j], i <= j
+ *                        (J^T J), [36..44) j1[i]*rx + j2[i]*ry (J^T r), [44] rx*rx + ry*ry, [45] n, [46] non-finite.
+ * COUNTS AND RANKS (device uint32, exact):
+ *   ofl_fit_score_dev    counts[K]: correspondences with residual(models[k]) <= thr, K in [1, 32], one read of the field.
+ *   ofl_fit_median_dev   out[2*k], out[2*k + 1]: the bits of the residuals of models[k] at ranks rank_lo <= rank_hi (0-based,
+ *                        ascending) among the valid correspondences -- the two values a median interpolates between
+ *                        ((n - 1) / 2 and n / 2 for n correspondences).  Any K >= 1; three models share one pass.
+ * SAMPLING (a pixel is valid when its mask byte is not 0 and its vector is finite):
+ *   ofl_fit_index_dev    builds the rank index of the valid pixels in the workspace (kept until the next call on it; the
+ *                        other entries leave it alone).
+ *   ofl_fit_pick_dev     idx[i] = pixel index (row * W + col) of the ranks[i]-th valid pixel in row-major order,
+ *                        0xffffffff when there are fewer.  ranks, idx: device uint32[count].
+ *   ofl_fit_gather_dev   out[i] = { idx[i], bits of u, bits of v, mask byte (1 without a mask) } as uint32[count][4], 16-byte
+ *                        aligned; { idx[i], 0, 0, 0 } for an index outside the field.
+ * workspace: ofl_fit_workspace_bytes(H, W) bytes of device memory, no initialisation needed.
+ * A field holding NaN / Inf gives an unspecified matrix but never reads or writes out of bounds.
+ */
+int ofl_fit_workspace_bytes(int H, int W, size_t *bytes);
+int ofl_fit_moments_dev(const float *flow, const uint8_t *mask, int H, int W, int sign, const double *origin,
+                        const double *gate_model, float gate_thr, void *workspace, size_t workspace_bytes,
+                        double *sums, void *stream);
+int ofl_fit_dlt_dev(const float *flow, const uint8_t *mask, int H, int W, int sign, const double *norm,
+                    const double *gate_model, float gate_thr, void *workspace, size_t workspace_bytes,
+                    double *sums, void *stream);
+int ofl_fit_gn_dev(const float *flow, const uint8_t *mask, int H, int W, int sign, const double *norm, const double *model,
+                   const double *gate_model, float gate_thr, void *workspace, size_t workspace_bytes,
+                   double *sums, void *stream);
+int ofl_fit_score_dev(const float *flow, const uint8_t *mask, int H, int W, int sign, const double *models, int K,
+                      float thr, uint32_t *counts, void *stream);
+int ofl_fit_median_dev(const float *flow, const uint8_t *mask, int H, int W, int sign, const double *models, int K,
+                       size_t rank_lo, size_t rank_hi, void *workspace, size_t workspace_bytes, uint32_t *out, void *stream);
+int ofl_fit_index_dev(const float *flow, const uint8_t *mask, int H, int W, void *workspace, size_t workspace_bytes, void *stream);
+int ofl_fit_pick_dev(const float *flow, const uint8_t *mask, int H, int W, const void *workspace, size_t workspace_bytes,
+                     const uint32_t *ranks, size_t count, uint32_t *idx, void *stream);
+int ofl_fit_gather_dev(const float *flow, const uint8_t *mask, int H, int W, const uint32_t *idx, size_t count,
+                       uint32_t *out, void *stream);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

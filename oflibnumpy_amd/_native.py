@@ -109,6 +109,15 @@ SIGNATURES = {
     "ofl_visualise_workspace_bytes": (_ci, [_ci, _ci, _ci, ctypes.POINTER(_cs)]),
     "ofl_visualise_range_dev": (_ci, [_vp, _ci, _ci, _ci, _cf, _cs, _cs, _cf, _vp, _cs, _vp, _vp]),
     "ofl_visualise_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _cf, _vp, _cf, _ci, _ci, _vp, _vp]),
+    "ofl_fit_workspace_bytes": (_ci, [_ci, _ci, ctypes.POINTER(_cs)]),
+    "ofl_fit_moments_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _cf, _vp, _cs, _vp, _vp]),
+    "ofl_fit_dlt_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _cf, _vp, _cs, _vp, _vp]),
+    "ofl_fit_gn_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _cf, _vp, _cs, _vp, _vp]),
+    "ofl_fit_score_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _ci, _cf, _vp, _vp]),
+    "ofl_fit_median_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _vp, _ci, _cs, _cs, _vp, _cs, _vp, _vp]),
+    "ofl_fit_index_dev": (_ci, [_vp, _vp, _ci, _ci, _vp, _cs, _vp]),
+    "ofl_fit_pick_dev": (_ci, [_vp, _vp, _ci, _ci, _vp, _cs, _vp, _cs, _vp, _vp]),
+    "ofl_fit_gather_dev": (_ci, [_vp, _vp, _ci, _ci, _vp, _cs, _vp, _vp]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

@@ -428,6 +428,86 @@ def visualise_launch(vecs, mask, h, w, batch, mode, flags, range_buf=None, range
     return img
 
 
+class FitField:
+    """The K8 passes over one HBM-resident field (csrc/ofl_fit.hip), as the object matrix_fit.fit drives: each method
+    enqueues one entry of include/ofl.h and reads its few numbers back.  mask: DeviceBuffer or None (every pixel counts);
+    gate: None or (3x3 model, float32 squared threshold)."""
+
+    def __init__(self, vecs, mask, shape, sign, stream=None):
+        self.vecs, self.mask, self.sign, self.stream = vecs, mask, sign, stream
+        self.h, self.w = int(shape[0]), int(shape[1])
+        self.origin = ((self.w - 1) / 2.0, (self.h - 1) / 2.0)            # the grid centre
+        nb = ctypes.c_size_t(0)
+        nat.check(_lib().ofl_fit_workspace_bytes(self.h, self.w, ctypes.byref(nb)))
+        self.ws = DeviceBuffer(nb.value)
+        self.out = DeviceBuffer(1024)
+
+    def _field(self):
+        return (self.vecs.ptr, self.mask.ptr if self.mask is not None else None, self.h, self.w)
+
+    @staticmethod
+    def _doubles(values):
+        a = np.ascontiguousarray(values, np.float64)
+        return a, a.ctypes.data
+
+    def _gate(self, gate):
+        if gate is None:
+            return None, None, np.float32(0)
+        keep, ptr = self._doubles(gate[0])
+        return keep, ptr, np.float32(gate[1])
+
+    def _sums(self, entry, count, gate, *params):
+        keep, gptr, thr = self._gate(gate)
+        held = [self._doubles(p) for p in params]
+        nat.check(entry(*self._field(), self.sign, *[p for _, p in held], gptr, thr, self.ws.ptr, self.ws.nbytes,
+                        self.out.ptr, self.stream))
+        return self.out.to_host((count,), np.float64, self.stream)
+
+    def moments(self, gate=None):
+        return self._sums(_lib().ofl_fit_moments_dev, 16, gate, self.origin)
+
+    def dlt(self, norm, gate=None):
+        return self._sums(_lib().ofl_fit_dlt_dev, 47, gate, norm)
+
+    def gn(self, norm, model, gate=None):
+        return self._sums(_lib().ofl_fit_gn_dev, 47, gate, norm, model)
+
+    def score(self, models, thr):
+        m, ptr = self._doubles(models)
+        k = m.size // 9
+        nat.check(_lib().ofl_fit_score_dev(*self._field(), self.sign, ptr, k, np.float32(thr), self.out.ptr, self.stream))
+        return self.out.to_host((k,), np.uint32, self.stream)
+
+    def median(self, models, rank_lo, rank_hi):
+        m, ptr = self._doubles(models)
+        k = m.size // 9
+        out = self.out if k * 8 <= self.out.nbytes else DeviceBuffer(k * 8)
+        nat.check(_lib().ofl_fit_median_dev(*self._field(), self.sign, ptr, k, rank_lo, rank_hi, self.ws.ptr, self.ws.nbytes,
+                                            out.ptr, self.stream))
+        return out.to_host((k, 2), np.uint32, self.stream)
+
+    def index(self):
+        nat.check(_lib().ofl_fit_index_dev(*self._field(), self.ws.ptr, self.ws.nbytes, self.stream))
+
+    def pick(self, ranks):
+        """pixel indices and gathered records (count, 4) uint32 of the ranks-th valid pixels (after index())"""
+        ranks = np.ascontiguousarray(ranks, np.uint32)
+        n = ranks.size
+        rbuf = DeviceBuffer.from_host(ranks, self.stream)
+        idx, rec = DeviceBuffer(n * 4), DeviceBuffer(n * 16)
+        nat.check(_lib().ofl_fit_pick_dev(*self._field(), self.ws.ptr, self.ws.nbytes, rbuf.ptr, n, idx.ptr, self.stream))
+        nat.check(_lib().ofl_fit_gather_dev(*self._field(), idx.ptr, n, rec.ptr, self.stream))
+        return rec.to_host((n, 4), np.uint32, self.stream)
+
+    def sample(self, ranks):
+        """-> (src, dst): (count, 2) float64 correspondences of the ranks-th valid pixels"""
+        rec = self.pick(ranks)
+        idx = rec[:, 0].astype(np.int64)
+        grid = np.stack([idx % self.w, idx // self.w], axis=-1).astype(np.float64)
+        v = np.ascontiguousarray(rec[:, 1:3]).view(np.float32).astype(np.float64)
+        return (grid, grid + v) if self.sign > 0 else (grid - v, grid)
+
+
 _STATS_KNOW_MASK = 1 << 30        # private flag in DeviceFlow._stats: STAT_MASK_HAS_ZERO has been evaluated
 
 
@@ -726,6 +806,16 @@ class DeviceFlow:
         rng = DeviceBuffer(16)
         visualise_range_launch(self.vecs, h, w, 1, rng)
         return float(rng.to_host((1,), np.float32)[0])
+
+    def matrix(self, dof=None, method=None, masked=None, seed=None):
+        """Flow.matrix (flow_class.py:797-867) on HBM-resident data -> (3, 3) float64: the affine (dof 4 / 6) or projective
+        (dof 8) matrix fitted to the field by least squares ('lms', dof 8), RANSAC or least median ('lmeds').  Every pass
+        over the field runs on the device (K8); the host solves the small systems (matrix_fit).  `seed` seeds the sampling
+        of minimal sets: the same field and seed give the same bits.  Not bit-compatible with OpenCV's estimators."""
+        from . import matrix_fit
+        dof, method, masked, seed = matrix_fit.matrix_args(dof, method, masked, seed)
+        field = FitField(self.vecs, self.mask if masked else None, self.shape, -1 if self.ref == 't' else 1)
+        return matrix_fit.fit(field, dof, method, seed, zero=self.is_zero(thresholded=False, masked=masked))
 
     def _and_mask(self, other):
         """vecs unchanged, mask = self.mask & other.mask (zero-flow identity warp of a Flow target)."""

@@ -8,7 +8,7 @@ use `DeviceFlow` directly.
 
 Next-tier row already widened into: `track` / `track_pts`.
 Dataset loaders (KITTI, Sintel + mask) are host I/O with a small built-in PNG reader.
-Out of scope (not on the hot path): matrix fitting, arrow drawing and display (`visualise_arrows`, `show*`).
+Out of scope (not on the hot path): arrow drawing and display (`visualise_arrows`, `show*`).
 """
 from __future__ import annotations
 
@@ -417,6 +417,16 @@ class Flow(object):
         show_mask_borders = False if show_mask_borders is None else show_mask_borders
         dev.visualise_args(mode, show_mask, show_mask_borders, range_max)
         return self.to_device().visualise(mode, show_mask, show_mask_borders, range_max).to_host()
+
+    def matrix(self, dof: int = None, method: str = None, masked: bool = None) -> np.ndarray:
+        """The (3, 3) float64 transformation matrix fitted to the flow: `dof` 4 (rotation, translation, scaling), 6 (affine)
+        or 8 (homography, the default); `method` 'lms' (dof 8 only, otherwise replaced by 'ransac' with a warning), 'ransac'
+        (default) or 'lmeds'; `masked` (default True) ignores vectors where the mask is False (reference
+        flow_class.py:797-867).  Fitted by the device (DeviceFlow.matrix): the estimators follow OpenCV's scheme and
+        parameters without being bit-compatible with it.  Arguments are checked before any device work."""
+        from . import matrix_fit
+        dof, method, masked, _ = matrix_fit.matrix_args(dof, method, masked)
+        return self.to_device().matrix(dof, method, masked)
 
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
         """flow_1 (+) flow_2 = flow_3: mode k returns flow_k from the other two (`self` comes first in

@@ -10,7 +10,7 @@ from .flow_class import Flow
 
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
-           'visualise_flow']
+           'get_flow_matrix', 'visualise_flow']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -49,6 +49,12 @@ def valid_source(flow: nd, ref: str) -> nd:
 def get_flow_padding(flow: nd, ref: str) -> list:
     """Padding [top, bottom, left, right] needed to keep every warped pixel (reference flow_operations.py:231-248)."""
     return Flow(flow, ref).get_padding()
+
+
+def get_flow_matrix(flow: nd, ref: str, dof: int = None, method: str = None) -> nd:
+    """(3, 3) matrix fitted to a flow array: dof 4 / 6 / 8, method 'lms' / 'ransac' / 'lmeds' (reference
+    flow_operations.py:251-271)."""
+    return Flow(flow, ref).matrix(dof=dof, method=method)
 
 
 def visualise_flow(flow: nd, mode: str, range_max: float = None) -> nd:
