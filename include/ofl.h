@@ -507,6 +507,41 @@ int ofl_fit_pick_dev(const float *flow, const uint8_t *mask, int H, int W, const
 int ofl_fit_gather_dev(const float *flow, const uint8_t *mask, int H, int W, const uint32_t *idx, size_t count,
                        uint32_t *out, void *stream);
 
+/* ------------------------------------------------------------------ K9: building, scaling, padding, cropping fields
+ * The constructors and element-wise / shape operations of Flow that had no device form: Flow.from_matrix /
+ * from_transforms (flow_class.py:173-234 over utils.flow_from_matrix, utils.py:91-111, and from_matrix :319-344),
+ * Flow.__mul__ / __truediv__ (flow_class.py:377-443), Flow.pad (:508-526) and Flow.__getitem__ (:297-308).  Streaming
+ * kernels; every entry only enqueues work.  Vector buffers that are written (and ofl_scale_dev's source) are 16-byte
+ * aligned, written masks 2-byte aligned; outputs must not alias inputs.
+ *
+ *   ofl_flow_from_matrix_dev  n fields out_vecs [n][H][W][2] from n row-major 3x3 float64 matrices in DEVICE memory
+ *                             (mats_dev [n][9]), one launch; n in [1, 65535].  Per pixel (x, y), every operation a float64
+ *                             operation rounded once, in exactly this order, nothing contracted:
+ *                                 X = (m[0]*x + m[1]*y) + m[2]    Y = (m[3]*x + m[4]*y) + m[5]    Z = (m[6]*x + m[7]*y) + m[8]
+ *                                 u = float32(X / Z - x)          v = float32(Y / Z - y)
+ *                             and for sign -1 (u, v) = (-u, -v) after the cast (a zero becomes -0.0f).  This is
+ *                             utils.flow_from_matrix bit for bit (np.matmul of the float64 matrix with the float32 column
+ *                             (x, y, 1)); reference 't' passes pinv(matrix) and sign -1 (utils.py:343-344).  A matrix whose
+ *                             last row is exactly (0, 0, 1) skips Z and the quotients: Z is exactly 1.
+ *   ofl_scale_dev             out = vecs * (k0, k1) per channel, or vecs / (k0, k1) with divide != 0; n_px pixels.
+ *                             wide == 0: float32 arithmetic with float32(k) -- NumPy's result for a Python scalar or a float32
+ *                             operand; wide != 0: float32(float64(v) op k) -- a float64 or integer array operand.
+ *                             Correctly rounded, never contracted.  The mask is not involved.
+ *   ofl_pad_flow_dev          out [H + top + bottom][W + left + right]; mode 0 'constant' (zero vectors), 1 'edge' (source
+ *                             index clamped), 2 'symmetric' (source index reflected with period 2n: i mod 2n, mirrored when
+ *                             >= n -- np.pad for any pad width, pads larger than the field included).  out_mask is the mask
+ *                             inside the original frame and 0 outside in every mode.
+ *   ofl_crop_flow_dev         out [rows][cols]: out[r][c] = field[row0 + r * row_step][col0 + c * col_step], vectors and
+ *                             mask; steps may be negative or larger than 1; every source index must lie inside the field
+ *                             (the caller normalises a slice with slice.indices).
+ */
+int ofl_flow_from_matrix_dev(const double *mats_dev, int n, int sign, int H, int W, float *out_vecs, void *stream);
+int ofl_scale_dev(const float *vecs, double k0, double k1, int divide, int wide, size_t n_px, float *out, void *stream);
+int ofl_pad_flow_dev(const float *vecs, const uint8_t *mask, int H, int W, int top, int bottom, int left, int right,
+                     int mode, float *out_vecs, uint8_t *out_mask, void *stream);
+int ofl_crop_flow_dev(const float *vecs, const uint8_t *mask, int H, int W, int row0, int row_step, int rows,
+                      int col0, int col_step, int cols, float *out_vecs, uint8_t *out_mask, void *stream);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

@@ -118,6 +118,10 @@ SIGNATURES = {
     "ofl_fit_index_dev": (_ci, [_vp, _vp, _ci, _ci, _vp, _cs, _vp]),
     "ofl_fit_pick_dev": (_ci, [_vp, _vp, _ci, _ci, _vp, _cs, _vp, _cs, _vp, _vp]),
     "ofl_fit_gather_dev": (_ci, [_vp, _vp, _ci, _ci, _vp, _cs, _vp, _vp]),
+    "ofl_flow_from_matrix_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _vp]),
+    "ofl_scale_dev": (_ci, [_vp, _cd, _cd, _ci, _ci, _cs, _vp, _vp]),
+    "ofl_pad_flow_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "ofl_crop_flow_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

@@ -63,6 +63,22 @@ class DeviceFlowBatch:
             nat.check(lib.ofl_stream_sync(None))
         return b.pack() if packed else b
 
+    @classmethod
+    def from_matrices(cls, matrices, shape, ref=None):
+        """n fields from n transformation matrices ((n, 3, 3), taken as float64), built in HBM: n * 72 bytes go up and ONE
+        launch of the constructor kernel writes all fields -- field i is DeviceFlow.from_matrix(matrices[i], shape, ref) bit
+        for bit.  Every mask is all valid."""
+        if not isinstance(matrices, np.ndarray):
+            raise TypeError("Error creating flows from matrices: Matrices need to be a numpy array")
+        if matrices.ndim != 3 or matrices.shape[0] == 0 or matrices.shape[1:] != (3, 3):
+            raise ValueError("Error creating flows from matrices: Matrices need to be a numpy array of shape (n, 3, 3), n > 0")
+        args = [dev.matrix_args(m, shape, ref) for m in matrices]
+        sign, ref = args[0][1], args[0][2]
+        b = cls(len(args), shape, ref)
+        dev.flow_from_matrix_launch(dev.DeviceBuffer.from_host(np.stack([a[0] for a in args])), b.n, sign, b.shape, b.vecs)
+        nat.check(nat.load().ofl_memset(b.mask.ptr, 1, b.n * b.shape[0] * b.shape[1], None))
+        return b
+
     def to_flows(self):
         h, w = self.shape
         v = self.vecs.to_host((self.n, h, w, 2), np.float32)

@@ -1,7 +1,8 @@
 """HBM-resident flow fields and the device-side flow algebra.
 
 `DeviceFlow` mirrors the hot-path methods of the reference's `Flow` (apply / switch_ref / invert /
-combine_with / valid_target / valid_source / + - neg / is_zero / visualise; src/oflibnumpy/flow_class.py) but
+combine_with / valid_target / valid_source / + - neg / is_zero / visualise, and the constructors zero / from_matrix /
+from_transforms, * / by a factor, pad and slicing; src/oflibnumpy/flow_class.py) but
 keeps vectors and mask in GPU memory between operations, so chains such as combine_with(mode=1)
 (1 scatter + 2 gathers, flow_class.py:1369-1370) never cross PCIe.  The host `Flow` class is a thin
 upload -> DeviceFlow op -> download wrapper around this module.
@@ -511,6 +512,134 @@ class FitField:
 _STATS_KNOW_MASK = 1 << 30        # private flag in DeviceFlow._stats: STAT_MASK_HAS_ZERO has been evaluated
 
 
+# ------------------------------------------------------------------------------ K9: build / scale / pad / crop
+# Host halves of the DeviceFlow constructors and operators: argument checks with the reference's exception types, raised
+# before the device is touched.
+_PAD_MODES = {'constant': 0, 'edge': 1, 'symmetric': 2}
+_N_TRANSFORM_VALUES = {'translation': 2, 'rotation': 3, 'scaling': 3}
+
+
+def matrix_args(matrix, shape, ref):
+    """Validation of utils.from_matrix (utils.py:328-334) -> (the float64 matrix the kernel evaluates, sign, ref): the
+    matrix itself and +1 for 's', its pseudo-inverse and -1 for 't' (utils.py:335-344)."""
+    from .utils import validate_shape, get_valid_ref
+    validate_shape(shape)
+    if not isinstance(matrix, np.ndarray):
+        raise TypeError("Error creating flow from matrix: Matrix needs to be a numpy array")
+    if matrix.shape != (3, 3):
+        raise ValueError("Error creating flow from matrix: Matrix needs to be a numpy array of shape (3, 3)")
+    ref = get_valid_ref(ref)
+    m = matrix if ref == 's' else np.linalg.pinv(matrix)
+    return np.ascontiguousarray(m, np.float64), (1 if ref == 's' else -1), ref
+
+
+def validate_transforms(transform_list, shape):
+    """Validation of utils.from_transforms (utils.py:381-420)."""
+    from .utils import validate_shape
+    validate_shape(shape)
+    if not isinstance(transform_list, list):
+        raise TypeError("Error creating flow from transforms: Transform_list needs to be a list")
+    if not all(isinstance(t, list) for t in transform_list):
+        raise TypeError("Error creating flow from transforms: Transform_list needs to be a list of lists")
+    if not all(len(t) > 1 for t in transform_list):
+        raise ValueError("Error creating flow from transforms: Invalid transforms passed")
+    for t in transform_list:
+        if t[0] not in _N_TRANSFORM_VALUES:
+            raise ValueError("Error creating flow from transforms: Transform '{}' not recognised".format(t[0]))
+        if len(t) - 1 != _N_TRANSFORM_VALUES[t[0]]:
+            raise ValueError("Error creating flow from transforms: Not enough transform values passed for "
+                             "'{}' - expected {}, got {}".format(t[0], _N_TRANSFORM_VALUES[t[0]], len(t) - 1))
+        if not all(isinstance(v, (float, int)) for v in t[1:]):
+            raise ValueError("Error creating flow from transforms: "
+                             "Transform values for '{}' need to be integers or floats".format(t[0]))
+
+
+def _valid_mask(mask, shape):
+    """A constructor's `mask` argument: None, a DeviceBuffer of at least H * W bytes (0 / 1, taken as it is), or a host array
+    checked like the Flow.mask setter (flow_class.py:142-161) -> None, the buffer, or uint8 (H, W)."""
+    if mask is None:
+        return None
+    n = int(shape[0]) * int(shape[1])
+    if isinstance(mask, (DeviceBuffer, _BufferView)):
+        if mask.nbytes < n:
+            raise ValueError("Error setting flow mask: Input has a different shape than the flow vectors")
+        return mask
+    if not isinstance(mask, np.ndarray):
+        raise TypeError("Error setting flow mask: Input is not a numpy array")
+    if mask.ndim != 2:
+        raise ValueError("Error setting flow mask: Input not 2-dimensional")
+    if mask.shape != (shape[0], shape[1]):
+        raise ValueError("Error setting flow mask: Input has a different shape than the flow vectors")
+    if ((mask != 0) & (mask != 1)).any():
+        raise ValueError("Error setting flow mask: Values must be 0 or 1")
+    return np.ascontiguousarray(mask.astype(np.bool_)).view(np.uint8)
+
+
+def _mask_buffer(mask, shape):
+    if mask is None:
+        buf = DeviceBuffer(int(shape[0]) * int(shape[1]))
+        nat.check(_lib().ofl_memset(buf.ptr, 1, int(shape[0]) * int(shape[1]), None))
+        return buf
+    return DeviceBuffer.from_host(mask) if isinstance(mask, np.ndarray) else mask
+
+
+def flow_from_matrix_launch(mats, n, sign, shape, out, stream=None):
+    """K9 constructor: `n` fields [n][H][W][2] into `out` from `mats`, n x 9 float64 on the device.  Asynchronous."""
+    nat.check(_lib().ofl_flow_from_matrix_dev(mats.ptr, n, sign, shape[0], shape[1], out.ptr, stream))
+
+
+def scale_operand(other, shape, verb, noun):
+    """The operand of DeviceFlow * and /, checked like Flow._broadcast_operand (flow_class.py:377-443) -> (k0, k1, wide):
+    the factors of the two channels and whether NumPy would compute in float64 (np.result_type of float32 and the operand:
+    a float64 or integer list / array) or in float32 (a number, which NumPy treats as a weak scalar, or a float32 array)."""
+    try:
+        k = float(other)
+        return k, k, 0
+    except TypeError:
+        pass
+    if isinstance(other, list):
+        if len(other) != 2:
+            raise ValueError("Error {} flow: {} list not length 2".format(verb, noun))
+        arr = np.array(other)
+    elif isinstance(other, np.ndarray):
+        if other.ndim == 1 and other.size == 2:
+            arr = other
+        elif (other.ndim == 2 and other.shape == tuple(shape)) or other.shape == tuple(shape) + (2,):
+            raise TypeError("Error {} flow: {} arrays of the shape of the flow are not supported on the device; "
+                            "use the host Flow (Flow.from_device)".format(verb, noun))
+        else:
+            raise ValueError("Error {} flow: {} array is not one of the following: size 2, shape of the "
+                             "flow object, shape of the flow vectors".format(verb, noun))
+    else:
+        raise TypeError("Error {} flow: {} cannot be converted to float, or isn't a list or numpy array"
+                        .format(verb, noun))
+    try:
+        res = np.result_type(np.float32, arr.dtype)
+    except TypeError:
+        res = None
+    if res not in (np.float32, np.float64):
+        raise TypeError("Error {} flow: {} of dtype {} does not combine with float32 vectors to float32 or float64"
+                        .format(verb, noun, arr.dtype))
+    return float(arr[0]), float(arr[1]), int(res == np.float64)
+
+
+def crop_args(item, shape):
+    """The index of DeviceFlow[...] -> ((row0, row_step, rows), (col0, col_step, cols)), normalised with slice.indices."""
+    if isinstance(item, slice):
+        item = (item,)
+    if not isinstance(item, tuple) or not 1 <= len(item) <= 2 or not all(isinstance(s, slice) for s in item):
+        raise TypeError("Error slicing flow: DeviceFlow takes a slice or a tuple of one or two slices (rows, columns); "
+                        "for any other index use the host Flow (Flow.from_device)")
+    out = []
+    for s, n in zip(item + (slice(None),) * (2 - len(item)), shape):
+        start, stop, step = s.indices(n)
+        count = len(range(start, stop, step))
+        if count == 0:
+            raise ValueError("Error slicing flow: the slices select no pixels of the {}x{} field".format(*shape))
+        out.append((start, step, count))
+    return tuple(out)
+
+
 # ------------------------------------------------------------------------------ DeviceFlow
 class DeviceFlow:
     """(vecs, mask, ref) resident in HBM.  Buffers are immutable once wrapped."""
@@ -538,6 +667,41 @@ class DeviceFlow:
             m = np.ascontiguousarray(mask)
             m = m.view(np.uint8) if m.dtype == np.bool_ else m.astype(np.uint8)
         return cls(DeviceBuffer.from_host(vecs), DeviceBuffer.from_host(m), (h, w), ref)
+
+    @classmethod
+    def zero(cls, shape, ref=None, mask=None):
+        """Flow.zero (flow_class.py:173-186) in HBM: a memset."""
+        from .utils import validate_shape, get_valid_ref
+        validate_shape(shape)
+        ref, mask = get_valid_ref(ref), _valid_mask(mask, shape)
+        return cls(DeviceBuffer.zeros(shape[0] * shape[1] * 8), _mask_buffer(mask, shape), shape, ref)
+
+    @classmethod
+    def from_matrix(cls, matrix, shape, ref=None, mask=None):
+        """Flow.from_matrix (flow_class.py:188-207, utils.py:319-344) built in HBM: 72 bytes go up, one launch of the
+        constructor kernel writes the field -- bit for bit what utils.from_matrix computes on the host.  `mask`: a host array
+        (validated like Flow.mask), a uint8 DeviceBuffer [H][W], or None (all valid).  Arguments are validated before the
+        device is touched."""
+        m, sign, ref = matrix_args(matrix, shape, ref)
+        mask = _valid_mask(mask, shape)
+        vecs = DeviceBuffer(shape[0] * shape[1] * 8)
+        flow_from_matrix_launch(DeviceBuffer.from_host(m), 1, sign, shape, vecs)
+        return cls(vecs, _mask_buffer(mask, shape), shape, ref)
+
+    @classmethod
+    def from_transforms(cls, transform_list, shape, ref=None, mask=None):
+        """Flow.from_transforms (flow_class.py:209-234, utils.py:347-423) built in HBM, see from_matrix."""
+        from .utils import matrix_from_transforms
+        validate_transforms(transform_list, shape)
+        return cls.from_matrix(matrix_from_transforms(transform_list), shape, ref, mask)
+
+    def copy(self):
+        """Flow.copy (flow_class.py:277-284): fresh buffers with the same content."""
+        out = DeviceFlow.empty(self.shape, self.ref)
+        nat.check(_lib().ofl_copy_dev(out.vecs.ptr, self.vecs.ptr, self.n_px * 8, None))
+        nat.check(_lib().ofl_copy_dev(out.mask.ptr, self.mask.ptr, self.n_px, None))
+        out._stats, out._certs = self._stats, dict(self._certs)
+        return out
 
     def to_host(self):
         """-> (vecs float32 [H,W,2], mask bool [H,W])"""
@@ -620,6 +784,57 @@ class DeviceFlow:
         out = self._axpy(None, -1.0)
         out._stats = self._stats            # the zero-flow predicates do not change under negation
         out._certs = {(-sg, pp): c for (sg, pp), c in self._certs.items()}      # x - (-f) is x + f: same warped grid
+        return out
+
+    # -- scaling (Flow.__mul__/__truediv__, flow_class.py:377-443) with a number, a list of 2 or an array of size 2
+    def _scale(self, other, divide, verb, noun):
+        k0, k1, wide = scale_operand(other, self.shape, verb, noun)
+        out = DeviceFlow(DeviceBuffer(self.n_px * 8), self.mask, self.shape, self.ref)     # buffers are immutable: the mask is shared
+        nat.check(_lib().ofl_scale_dev(self.vecs.ptr, k0, k1, divide, wide, self.n_px, out.vecs.ptr, None))
+        return out              # fresh _stats / _certs: scaling moves vectors across the thresholds and changes the warped grid
+
+    def __mul__(self, other):
+        return self._scale(other, 0, "multiplying", "Multiplier")
+
+    def __rmul__(self, other):
+        try:
+            float(other)
+        except TypeError:
+            return NotImplemented
+        return self._scale(other, 0, "multiplying", "Multiplier")
+
+    def __truediv__(self, other):
+        return self._scale(other, 1, "dividing", "Divisor")
+
+    def __pow__(self, other):
+        raise TypeError("Error exponentiating flow: DeviceFlow has no '**' (NumPy's float32 power cannot be reproduced bit for "
+                        "bit on the device); use the host Flow: Flow.from_device(f) ** exponent")
+
+    # -- shape operations
+    def pad(self, padding=None, mode=None):
+        """Flow.pad (flow_class.py:508-526) in HBM: vectors padded with zeros ('constant'), the border values ('edge') or
+        their mirror image ('symmetric'), the mask with 0.  All-zero padding returns `self`."""
+        from .utils import get_valid_padding
+        mode = 'constant' if mode is None else mode
+        if mode not in _PAD_MODES:
+            raise ValueError("Error padding flow: Mode should be one of "
+                             "'constant', 'edge', 'symmetric', but instead got '{}'".format(mode))
+        p = get_valid_padding(padding, "Error padding flow: ")
+        if not any(p):
+            return self
+        h, w = self.shape
+        out = DeviceFlow.empty((h + p[0] + p[1], w + p[2] + p[3]), self.ref)
+        nat.check(_lib().ofl_pad_flow_dev(self.vecs.ptr, self.mask.ptr, h, w, p[0], p[1], p[2], p[3], _PAD_MODES[mode],
+                                          out.vecs.ptr, out.mask.ptr, None))
+        return out
+
+    def __getitem__(self, item):
+        """Flow.__getitem__ (flow_class.py:297-308) for a slice or a tuple of one or two slices (rows, columns; steps may
+        be negative): a strided copy of vectors and mask."""
+        (r0, rs, rows), (c0, cs, cols) = crop_args(item, self.shape)
+        out = DeviceFlow.empty((rows, cols), self.ref)
+        nat.check(_lib().ofl_crop_flow_dev(self.vecs.ptr, self.mask.ptr, self.shape[0], self.shape[1], r0, rs, rows, c0, cs, cols,
+                                           out.vecs.ptr, out.mask.ptr, None))
         return out
 
     def _compose(self, sampled, sign, quant=nat.QUANT_OPENCV):
