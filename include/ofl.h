@@ -368,6 +368,61 @@ int ofl_scatter_query_dev(const float *flow, int sign, int point_precision, cons
                           const double *query_xy, size_t n_query, double *out, uint8_t *found,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* Tracking with RESIDENT points (K10, csrc/ofl_track.hip): the NumPy halves of track_pts (utils.py:547-622) and Flow.track
+ * (flow_class.py:755-795) on the device, so that points, like fields, stay in HBM between steps.  All four entries are
+ * asynchronous on `stream` (ofl_scatter_query_dev, which the query paths call in between, synchronises as before).
+ * Common conventions:
+ *   points    [n][2] in (row, col) order, 16-byte aligned: float64, or int32 / int64 where a dtype code is taken;
+ *   stats     device uint32 per field, the OFL_STAT_* word ofl_flow_stats_dev writes, or NULL: a field whose
+ *             OFL_STAT_NONZERO_TH bit is clear leaves the points where they are (is_zero_flow(flow, thresholded=True),
+ *             utils.py:588) -- read on the device, no host round trip;
+ *   valid     uint8 [H][W] per field (Flow.valid_source()) or NULL; with it, status [..] = valid[rint(row)][rint(col)] at the
+ *             position BEFORE the step, rint = round-half-even like np.round (flow_class.py:791-793).  A rounded position
+ *             that is no pixel of the field gives 0 (NumPy wraps negative indices and raises beyond the end).  status and
+ *             valid are given together or not at all;
+ *   int_out   != 0: the result is int32 after rint (np.round(warped).astype('i'), utils.py:619-620), else float64;
+ *   n == 0    is no error: nothing is launched.
+ *
+ * ofl_track_bilinear_dev   ref 's', bilinear sampling (utils.py:593-606): p + sample(p), sample being exactly what
+ *     ofl_sample_points_dev computes, then one float64 add.  flows: B fields back to back, [B][H][W][2]; stats [B];
+ *     valid [B][H][W].
+ *       chain == 0: every field is applied to the same n points: out [B][n][2], status [B][n].  A point outside
+ *           0 <= row <= H-1, 0 <= col <= W-1 (NaN included) -- where the reference raises IndexError -- is left unchanged and
+ *           counted in *outside_count (device uint32, zeroed by the caller, required).
+ *       chain != 0: field k maps frame k to frame k+1 and each point runs through all B fields in one launch: out [n][2];
+ *           a point whose position before step k is outside is frozen there, lost_at[i] = k (int32 [n], required; -1 = never
+ *           lost); status [n] is the AND over the steps taken and 0 for a lost point; path (or NULL) float64 [B+1][n][2]
+ *           receives every intermediate position, path[0] being the input.
+ * ofl_track_pixels_dev     ref 's', integer points (utils.py:590-591): (double)p + (double)flow[row, col, ::-1].  pts_dtype
+ *     OFL_TRACK_I32 or OFL_TRACK_I64.  An index outside [0, H) x [0, W) is counted in *outside_count and left unchanged
+ *     (NumPy's wrap-around of negative indices is not reproduced).
+ * ofl_track_query_points_dev   points of dtype pts_dtype (OFL_TRACK_*) -> query_xy float64 [n][2] = (x, y), the layout
+ *     ofl_scatter_query_dev takes (pts[:, ::-1].astype(float64), utils.py:603 / :614).
+ * ofl_track_query_epilogue_dev the tail of ref 't' and s_exact_mode (utils.py:603-620): query_xy / vals_uv (float64 [n][2], C = 2)
+ *     / found are the input and the results of ofl_scatter_query_dev; the values are swapped back to (row, col) and added.
+ *     One field: stats one word, valid [H][W].  Outputs, each optional (at least one is required): out_rc float64
+ *     [n][2], out_int int32 [n][2] after rint, next_query_xy float64 [n][2] -- the result in (x, y) order, the next step's query.
+ *       step < 0: one call of track_pts -- a point that was not found becomes (0, 0) (utils.py:616-618).
+ *       step >= 0: step `step` of a sequence -- such a point is LOST: frozen where it is, lost_at[i] = step (int32 [n],
+ *           required; read when step > 0, so step 0 initialises it); a point lost earlier stays frozen; status is ANDed with
+ *           the previous steps' (read when step > 0) and 0 for lost points.
+ */
+enum {
+    OFL_TRACK_F64 = 0,
+    OFL_TRACK_I32 = 1,
+    OFL_TRACK_I64 = 2
+};
+int ofl_track_bilinear_dev(const float *flows, int B, int H, int W, int chain, const double *pts_rc, size_t n,
+                           const uint32_t *stats, const uint8_t *valid, int int_out, void *out, uint8_t *status,
+                           uint32_t *outside_count, int32_t *lost_at, double *path, void *stream);
+int ofl_track_pixels_dev(const float *flow, int H, int W, const void *pts_rc, int pts_dtype, size_t n,
+                         const uint32_t *stats, const uint8_t *valid, int int_out, void *out, uint8_t *status,
+                         uint32_t *outside_count, void *stream);
+int ofl_track_query_points_dev(const void *pts_rc, int pts_dtype, size_t n, double *query_xy, void *stream);
+int ofl_track_query_epilogue_dev(const double *query_xy, const double *vals_uv, const uint8_t *found, size_t n, int H, int W,
+                                 const uint32_t *stats, const uint8_t *valid, int step, double *out_rc, int32_t *out_int,
+                                 double *next_query_xy, uint8_t *status, int32_t *lost_at, void *stream);
+
 /* small device helpers of the flow algebra:
  *   ofl_mask_and_dev     out = a & b                      (flow_class.py:643)
  *   ofl_grid_offset_dev  out[y][x] = float32((x, y) + sign * vecs[y][x])   (flow_class.py:1398-1406)

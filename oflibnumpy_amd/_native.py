@@ -21,6 +21,7 @@ SCATTER_ROUND, SCATTER_NEGATE, SCATTER_UNCERTIFIED = 0x100, 0x200, 0x400
 STAT_NONZERO_MASKED, STAT_NONZERO_TH_MASKED, STAT_NONZERO, STAT_NONZERO_TH, STAT_NONFINITE, STAT_MASK_HAS_ZERO = 1, 2, 4, 8, 16, 32
 VIS_HSV, VIS_RGB, VIS_BGR = 0, 1, 2
 VIS_SHOW_MASK, VIS_MASK_BORDERS = 1, 2
+TRACK_F64, TRACK_I32, TRACK_I64 = 0, 1, 2
 
 
 class MeshCert(ctypes.Structure):
@@ -100,6 +101,10 @@ SIGNATURES = {
     "ofl_scatter_linear": (_ci, [_vp, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _ci, _vp, _vp, _vp, _ci]),
     "ofl_sample_points_dev": (_ci, [_vp, _ci, _ci, _vp, _cs, _vp, _vp]),
     "ofl_scatter_query_dev": (_ci, [_vp, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _vp, _cs, _vp, _vp, _vp, _cs, _vp]),
+    "ofl_track_bilinear_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _cs, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ofl_track_pixels_dev": (_ci, [_vp, _ci, _ci, _vp, _ci, _cs, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "ofl_track_query_points_dev": (_ci, [_vp, _ci, _cs, _vp, _vp]),
+    "ofl_track_query_epilogue_dev": (_ci, [_vp, _vp, _vp, _cs, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofl_flow_extent_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _cf, _vp, _vp]),
     "ofl_convert_dev": (_ci, [_vp, _ci, _vp, _ci, _cs, _vp]),
     "ofl_mask_and_dev": (_ci, [_vp, _vp, _vp, _cs, _vp]),

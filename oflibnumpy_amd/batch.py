@@ -145,6 +145,141 @@ class DeviceFlowBatch:
         return rng.to_host((self.n,), np.float32)
 
 
+    # -- point tracking (K10)
+    def field(self, i):
+        """Field i as a DeviceFlow on this batch's memory (a view: it keeps the batch alive, nothing is copied)."""
+        if not 0 <= i < self.n:
+            raise IndexError("field {} of a batch of {}".format(i, self.n))
+        px = self.shape[0] * self.shape[1]
+        f = dev.DeviceFlow(dev._BufferView(self.vecs.ptr + i * px * 8, px * 8), dev._BufferView(self.mask.ptr + i * px, px),
+                           self.shape, self.ref)
+        f._owner = self
+        return f
+
+    def _stats_words(self):
+        """uint32 [n] in HBM: the OFL_STAT_* word of every field, one launch of the statistics kernel per field and no
+        read-back (the tracking kernels read the zero-flow predicate there).  Evaluated once: the fields are immutable."""
+        words = getattr(self, "_words", None)
+        if words is None:
+            px = self.shape[0] * self.shape[1]
+            words = dev.DeviceBuffer(4 * self.n)
+            for k in range(self.n):
+                dev.stats_word_launch(self.vecs.ptr + k * px * 8, None, px, words.ptr + 4 * k)
+            self._words = words
+        return words
+
+    def _valid_sources(self):
+        """uint8 [n][H][W]: valid_source() of every ref-'s' field, by the gather kernel.  (A thresholded-zero field needs
+        no special case: under the gather's 1/32-px snapping its warp is the identity, which leaves its mask.)"""
+        h, w = self.shape
+        px = h * w
+        maps = dev.DeviceBuffer(self.n * px)
+        lib = nat.load()
+        for k in range(self.n):
+            nat.check(lib.ofl_gather_bilinear_dev(None, nat.U8, 0, h, w, self.vecs.ptr + k * px * 8, h, w, 0, 0, +1, None,
+                                                  self.mask.ptr + k * px, None, maps.ptr + k * px, nat.QUANT_OPENCV,
+                                                  nat.ARITH_NATIVE, nat.RULE_EQ1, None))
+        return maps
+
+    @staticmethod
+    def _float_points(pts, what):
+        on_host = not isinstance(pts, dev.DevicePoints)
+        dp = dev.DevicePoints.from_host(pts) if on_host else pts
+        if dp.dtype != np.float64:
+            raise TypeError("Error tracking points: {} takes float points, got {}".format(what, dp.dtype))
+        return dp, on_host
+
+    def track(self, pts, int_out=None, get_valid_status=None):
+        """The SAME points through every field of a ref-'s' batch, independently, in ONE launch: -> (n_fields, n, 2) points
+        (float64, int32 with int_out) and, with get_valid_status, an (n_fields, n) status; row i is
+        DeviceFlow.track(pts, int_out, get_valid_status) on field i bit for bit (bilinear sampling).  `pts`: float points, a
+        DevicePoints (answered with a DevicePoints of shape (n_fields, n, 2) and a uint8 DeviceBuffer) or an (n, 2) array
+        (answered with arrays).  Raises IndexError if a point is outside the area, like the single call."""
+        int_out, get_valid_status, _ = dev.track_args(pts, int_out, get_valid_status, None)
+        if self.ref != 's':
+            raise ValueError("Error tracking points: DeviceFlowBatch.track batches the bilinear ('s') step; 't' fields go through "
+                             "DeviceFlow.track one by one (field(i)) or through track_sequence")
+        dp, on_host = self._float_points(pts, "DeviceFlowBatch.track")
+        n, B = dp.n, self.n
+        out = dev.DevicePoints(dev.DeviceBuffer(B * n * (8 if int_out else 16)), B * n, np.int32 if int_out else np.float64, (B, n, 2))
+        status = dev.DeviceBuffer(B * n) if get_valid_status else None
+        if n:
+            valid = self._valid_sources() if get_valid_status else None
+            outside = dev.DeviceBuffer.zeros(16)
+            dev.track_bilinear_launch(self.vecs.ptr, B, self.shape, False, dp, self._stats_words(), valid, int_out, out.buf, status,
+                                      outside=outside)
+            if int(outside.to_host((1,), np.uint32)[0]):
+                raise IndexError("Some points are outside of the data area.")
+        if not on_host:
+            return (out, status) if get_valid_status else out
+        res = out.to_host()
+        return (res, status.to_host((B, n), np.uint8).view(np.bool_)) if get_valid_status else res
+
+    def track_sequence(self, pts, int_out=None, get_valid_status=None, return_path=False):
+        """Points chained through the batch as a SEQUENCE: field k maps frame k to frame k + 1.  -> (points, lost_at
+        [, status][, path]): the final positions (float64, int32 with int_out); lost_at int32 (n,), the step at which a point
+        was lost or -1; with get_valid_status the Flow.track status ANDed over the steps, False for lost points; with
+        return_path the float64 (n_fields + 1, n, 2) positions before, between and after the steps.
+
+        ref 's' (bilinear sampling): ONE launch takes every point through all fields.  A point whose position before step k is
+        outside the area (where a single call raises IndexError) is lost at k: it stays where it is.  The status maps
+        (valid_source of every field) are built first, one gather per field.
+        ref 't': one resident query and one epilogue per field; a point the interpolation finds no triangle for (which a
+        single call moves to (0, 0)) is lost at that step and stays where it is.
+        Never raises for points that leave the area.  `pts`: float64 points, a DevicePoints (answered with DevicePoints for
+        points and path, DeviceBuffers int32 / uint8 for lost_at and status) or an (n, 2) array (answered with arrays).  The
+        fields, and between the steps the points, stay in HBM."""
+        int_out, get_valid_status, _ = dev.track_args(pts, int_out, get_valid_status, None)
+        if not isinstance(return_path, bool):
+            raise TypeError("Error tracking points: Return_path needs to be a boolean")
+        dp, on_host = self._float_points(pts, "DeviceFlowBatch.track_sequence")
+        n, B = dp.n, self.n
+        out = dev.DevicePoints(dev.DeviceBuffer(n * (8 if int_out else 16)), n, np.int32 if int_out else np.float64)
+        lost_at = dev.DeviceBuffer(4 * n)
+        status = dev.DeviceBuffer(n) if get_valid_status else None
+        path = dev.DevicePoints(dev.DeviceBuffer((B + 1) * n * 16), (B + 1) * n, np.float64, (B + 1, n, 2)) if return_path else None
+        if n and self.ref == 's':
+            valid = self._valid_sources() if get_valid_status else None
+            dev.track_bilinear_launch(self.vecs.ptr, B, self.shape, True, dp, self._stats_words(), valid, int_out, out.buf, status,
+                                      lost_at=lost_at, path=path.buf if return_path else None)
+        elif n:
+            self._sequence_t(dp, int_out, out, lost_at, status, path)
+        res = [out, lost_at] + ([status] if get_valid_status else []) + ([path] if return_path else [])
+        if on_host:
+            res[0], res[1] = out.to_host(), lost_at.to_host((n,), np.int32)
+            if get_valid_status:
+                res[2] = status.to_host((n,), np.uint8).view(np.bool_)
+            if return_path:
+                res[-1] = path.to_host()
+        return tuple(res)
+
+    def _sequence_t(self, dp, int_out, out, lost_at, status, path):
+        """track_sequence for ref 't': per field, the scatter kernel's query mode on the resident positions and the epilogue
+        kernel, which also writes the next field's queries."""
+        h, w = self.shape
+        n, B, px = dp.n, self.n, self.shape[0] * self.shape[1]
+        words = self._stats_words()
+        query = dev.track_query_points(dp)
+        if path is not None:
+            nat.check(nat.load().ofl_copy_dev(path.buf.ptr, dp.buf.ptr, n * 16, None))
+        for k in range(B):
+            last = k == B - 1
+            vecs = dev._BufferView(self.vecs.ptr + k * px * 8, px * 8)
+            valid = self.field(k).valid_source() if status is not None else None
+            vals, found = dev.scatter_query_resident(vecs, -1, vecs, h, w, query, n)
+            nxt = None if last else dev.DeviceBuffer(n * 16)
+            out_rc = None
+            if path is not None:
+                out_rc = dev._BufferView(path.buf.ptr + (k + 1) * n * 16, n * 16)
+            elif last and not int_out:
+                out_rc = out.buf
+            dev.track_query_epilogue(query, vals, found, n, self.shape, dev._BufferView(words.ptr + 4 * k, 4), valid, k, status,
+                                     out_rc=out_rc, out_int=out.buf if last and int_out else None, next_query=nxt, lost_at=lost_at)
+            query = nxt
+        if path is not None and not int_out:
+            nat.check(nat.load().ofl_copy_dev(out.buf.ptr, path.buf.ptr + B * n * 16, n * 16, None))
+
+
 def combine_flows_batch(flows_1, flows_2, ref=None, rank=0, world=1, thresholded=False):
     """Mode-3 composition of many independent pairs.  `flows_1[i] (+) flows_2[i]`; inputs are lists of
     `Flow` objects or of (H, W, 2) arrays with reference `ref`.  With world > 1 only the contiguous block of

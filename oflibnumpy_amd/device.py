@@ -258,6 +258,41 @@ class DeviceImage:
         return self.buf.to_host(self.shape, self.dtype)
 
 
+_TRACK_DT = {np.dtype('float64'): nat.TRACK_F64, np.dtype('int32'): nat.TRACK_I32, np.dtype('int64'): nat.TRACK_I64}
+
+
+def _points_array(arr):
+    """A host array of points, checked like track_pts (utils.py:571-574, :592) -> contiguous (n, 2) float64, int32 or int64.
+    Other float dtypes become float64; any other dtype -- the narrow integers, which NumPy would add to the float32 vectors
+    in float32, included -- is a TypeError (the reference raises it for ref 's' only)."""
+    if not isinstance(arr, np.ndarray):
+        raise TypeError("Error tracking points: Pts needs to be a numpy array")
+    if arr.ndim != 2 or arr.shape[1] != 2:
+        raise ValueError("Error tracking points: Pts needs to have shape N-2")
+    if np.issubdtype(arr.dtype, np.floating):
+        return np.ascontiguousarray(arr, np.float64)
+    if arr.dtype in _TRACK_DT:
+        return np.ascontiguousarray(arr)
+    raise TypeError("Error tracking points: Pts numpy array needs to have a float or int (int32, int64) dtype")
+
+
+class DevicePoints:
+    """(n, 2) points in (row, col) order in HBM: float64, int32 or int64.  What DeviceFlow.track and DeviceFlowBatch.track* take
+    and hand back, so that points tracked through a sequence of fields never leave the device."""
+
+    def __init__(self, buf, n, dtype, shape=None):
+        self.buf, self.n, self.dtype = buf, int(n), np.dtype(dtype)
+        self.shape = (self.n, 2) if shape is None else tuple(shape)      # the batch calls stack results: (fields, n, 2)
+
+    @classmethod
+    def from_host(cls, arr):
+        arr = _points_array(arr)
+        return cls(DeviceBuffer.from_host(arr), arr.shape[0], arr.dtype)
+
+    def to_host(self):
+        return self.buf.to_host(self.shape, self.dtype)
+
+
 # ------------------------------------------------------------------------------ kernels
 def gather_bilinear(src, flow_buf, flow_shape, sign, smask=None, fmask=None, want_valid=False,
                     pad=(0, 0), quant=nat.QUANT_OPENCV, arith=nat.ARITH_NATIVE, rule=nat.RULE_EQ1,
@@ -390,6 +425,24 @@ def visualise_args(mode, show_mask=False, show_mask_borders=False, range_max=Non
         raise ValueError("Error visualising flow: mode must be 'rgb', 'bgr' or 'hsv', got {!r}".format(mode))
     flags = (nat.VIS_SHOW_MASK if show_mask else 0) | (nat.VIS_MASK_BORDERS if show_mask_borders else 0)
     return _VIS_MODES[mode], flags, rc
+
+
+def track_args(pts, int_out=None, get_valid_status=None, s_exact_mode=None):
+    """Validation of Flow.track's arguments (flow_class.py:781-784, utils.py:571-582) with the reference's defaults and
+    exception types, on the host before any device work -> (int_out, get_valid_status, s_exact_mode).  `pts`: a
+    DevicePoints or an (n, 2) array of a dtype DevicePoints.from_host takes."""
+    if not isinstance(pts, DevicePoints):
+        _points_array(pts)
+    int_out = False if int_out is None else int_out
+    get_valid_status = False if get_valid_status is None else get_valid_status
+    s_exact_mode = False if s_exact_mode is None else s_exact_mode
+    if not isinstance(int_out, bool):
+        raise TypeError("Error tracking points: Int_out needs to be a boolean")
+    if not isinstance(get_valid_status, bool):
+        raise TypeError("Error tracking points: Get_tracked needs to be a boolean")
+    if not isinstance(s_exact_mode, bool):
+        raise TypeError("Error tracking points: S_exact_mode needs to be a boolean")
+    return int_out, get_valid_status, s_exact_mode
 
 
 def percentile_ranks(n, q=99):
@@ -649,6 +702,7 @@ class DeviceFlow:
         self.shape = (int(shape[0]), int(shape[1]))
         self.ref = ref
         self._stats = stats
+        self._stats_buf = None      # the OFL_STAT_* word in HBM, for kernels that read the zero-flow predicate themselves
         self._certs = {}            # (sign, point_precision) -> MeshCert of the warped grid without a point mask
 
     # -- construction / transfer
@@ -710,6 +764,7 @@ class DeviceFlow:
 
     def relabel(self, ref):
         out = DeviceFlow(self.vecs, self.mask, self.shape, ref, self._stats)
+        out._stats_buf = self._stats_buf
         out._certs = self._certs        # same vectors: same warped grid
         return out
 
@@ -1031,6 +1086,62 @@ class DeviceFlow:
         dof, method, masked, seed = matrix_fit.matrix_args(dof, method, masked, seed)
         field = FitField(self.vecs, self.mask if masked else None, self.shape, -1 if self.ref == 't' else 1)
         return matrix_fit.fit(field, dof, method, seed, zero=self.is_zero(thresholded=False, masked=masked))
+
+    def _stats_word(self):
+        """The field's OFL_STAT_* word as a device uint32 (what the tracking kernels read for the zero-flow rule): the cached
+        statistics go up as 4 bytes; a field without any gets one asynchronous launch of the statistics kernel."""
+        if self._stats_buf is None:
+            if self._stats is not None:
+                self._stats_buf = DeviceBuffer.from_host(np.array([self._stats & 0x3f], np.uint32))
+            else:
+                self._stats_buf = DeviceBuffer(16)
+                stats_word_launch(self.vecs.ptr, self.mask.ptr, self.n_px, self._stats_buf.ptr)
+        return self._stats_buf
+
+    def track(self, pts, int_out=None, get_valid_status=None, s_exact_mode=None):
+        """Flow.track (flow_class.py:755-795, utils.py:547-622) on an HBM-resident field: the field is neither uploaded nor
+        downloaded.  `pts`: a DevicePoints -- the answer is a DevicePoints (and, with get_valid_status, a uint8 DeviceBuffer
+        [n]) -- or an (n, 2) array, which is uploaded, points only, and answered with arrays like the reference.  All four
+        paths: ref 's' with integer points, with bilinear sampling and with s_exact_mode, and ref 't'.  Equal to Flow.track
+        bit for bit, except that
+          - the result is float64 (int32 with int_out) whatever the points' dtype: for a thresholded-zero flow the reference
+            hands integer points back as they are;
+          - an integer index outside the field raises IndexError, also a negative one that NumPy would wrap around;
+          - the status of a point whose rounded position is no pixel of the field is False, where NumPy wraps or raises.
+        Raises IndexError for points outside the area on the non-query 's' paths (one 4-byte read-back), like the reference."""
+        int_out, get_valid_status, s_exact_mode = track_args(pts, int_out, get_valid_status, s_exact_mode)
+        on_host = not isinstance(pts, DevicePoints)
+        dp = DevicePoints.from_host(pts) if on_host else pts
+        h, w = self.shape
+        n = dp.n
+        out = DevicePoints(DeviceBuffer(n * (8 if int_out else 16)), n, np.int32 if int_out else np.float64)
+        valid = self.valid_source() if get_valid_status else None
+        status = DeviceBuffer(n) if get_valid_status else None
+        if n:
+            words = self._stats_word()
+            if self.ref == 's' and (dp.dtype.kind == 'i' or not s_exact_mode):
+                outside = DeviceBuffer.zeros(16)
+                if dp.dtype.kind == 'i':
+                    nat.check(_lib().ofl_track_pixels_dev(self.vecs.ptr, h, w, dp.buf.ptr, _TRACK_DT[dp.dtype], n, words.ptr,
+                                                          _ptr(valid), int(int_out), out.buf.ptr, _ptr(status), outside.ptr, None))
+                else:
+                    track_bilinear_launch(self.vecs.ptr, 1, self.shape, False, dp, words, valid, int_out, out.buf, status,
+                                          outside=outside)
+                if int(outside.to_host((1,), np.uint32)[0]):
+                    raise IndexError("Some points are outside of the data area.")
+            else:
+                query = track_query_points(dp)
+                if self.ref == 's':      # exact mode: values live on the undisplaced regular grid
+                    pos, sign = DeviceBuffer.zeros(self.n_px * 8), 1
+                else:                    # 't': values live at grid - flow
+                    pos, sign = self.vecs, -1
+                vals, found = scatter_query_resident(pos, sign, self.vecs, h, w, query, n)
+                track_query_epilogue(query, vals, found, n, self.shape, words, valid, -1, status,
+                                     out_rc=None if int_out else out.buf, out_int=out.buf if int_out else None)
+        if not on_host:
+            return (out, status) if get_valid_status else out
+        res = out.to_host()
+        return (res, status.to_host((n,), np.uint8).view(np.bool_)) if get_valid_status else res
 
     def _and_mask(self, other):
         """vecs unchanged, mask = self.mask & other.mask (zero-flow identity warp of a Flow target)."""
@@ -1477,3 +1588,48 @@ def scatter_query(pos_flow_buf, sign, vals_buf, C, h, w, query_xy, pmask=None):
     nat.check(_lib().ofl_scatter_query_dev(pos_flow_buf.ptr, sign, 0, pmask.ptr if pmask is not None else None,
                                            vals_buf.ptr, C, h, w, dq.ptr, n, out.ptr, found.ptr, ws.ptr, ws.nbytes, None))
     return out.to_host((n, C), np.float64), found.to_host((n,), np.uint8).view(np.bool_)
+
+
+# ------------------------------------------------------------------------------ K10: tracking with resident points
+def _ptr(buf):
+    return buf.ptr if buf is not None else None
+
+
+def stats_word_launch(vecs_ptr, mask_ptr, n_px, out_ptr, stream=None):
+    """K4 into a device uint32 at out_ptr, asynchronous: the OFL_STAT_* word of one field, left in HBM for a kernel to read."""
+    nat.check(_lib().ofl_flow_stats_dev(vecs_ptr, mask_ptr, n_px, np.float32(DEFAULT_THRESHOLD), out_ptr, stream))
+
+
+def track_bilinear_launch(flows_ptr, n_fields, shape, chain, pts, stats, valid, int_out, out, status, outside=None,
+                          lost_at=None, path=None, stream=None):
+    """K10, ref 's' with bilinear sampling (ofl_track_bilinear_dev); asynchronous.  pts: float64 DevicePoints."""
+    if pts.dtype != np.float64:
+        raise TypeError("Error tracking points: the bilinear tracking kernel takes float64 points, got {}".format(pts.dtype))
+    nat.check(_lib().ofl_track_bilinear_dev(flows_ptr, n_fields, shape[0], shape[1], 1 if chain else 0, pts.buf.ptr, pts.n,
+                                            _ptr(stats), _ptr(valid), int(bool(int_out)), out.ptr, _ptr(status),
+                                            _ptr(outside), _ptr(lost_at), _ptr(path), stream))
+
+
+def track_query_points(pts, stream=None):
+    """DevicePoints (row, col) -> DeviceBuffer of float64 (x, y) queries for the scatter kernel; asynchronous."""
+    query = DeviceBuffer(pts.n * 16)
+    nat.check(_lib().ofl_track_query_points_dev(pts.buf.ptr, _TRACK_DT[pts.dtype], pts.n, query.ptr, stream))
+    return query
+
+
+def scatter_query_resident(pos_flow_buf, sign, vals_buf, h, w, query, n):
+    """scatter_query with the queries already on the device, and the answers left there: (values float64 [n][2] as (u, v),
+    found uint8 [n]) DeviceBuffers."""
+    vals, found = DeviceBuffer(n * 16), DeviceBuffer(n)
+    ws = _workspace(h, w, 2)
+    nat.check(_lib().ofl_scatter_query_dev(pos_flow_buf.ptr, sign, 0, None, vals_buf.ptr, 2, h, w, query.ptr, n, vals.ptr,
+                                           found.ptr, ws.ptr, ws.nbytes, None))
+    return vals, found
+
+
+def track_query_epilogue(query, vals, found, n, shape, stats, valid, step, status, out_rc=None, out_int=None, next_query=None,
+                         lost_at=None, stream=None):
+    """K10 tail of the query paths (ofl_track_query_epilogue_dev); asynchronous."""
+    nat.check(_lib().ofl_track_query_epilogue_dev(query.ptr, vals.ptr, found.ptr, n, shape[0], shape[1], _ptr(stats), _ptr(valid),
+                                                  step, _ptr(out_rc), _ptr(out_int), _ptr(next_query), _ptr(status),
+                                                  _ptr(lost_at), stream))
