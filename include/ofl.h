@@ -47,6 +47,9 @@ enum {
 /* element types of warp targets (what cv2.remap accepts for INTER_LINEAR) */
 enum { OFL_U8 = 0, OFL_I16 = 1, OFL_U16 = 2, OFL_F32 = 3, OFL_F64 = 4 };
 
+/* element types of flow fields that cross to or from another framework (K11) */
+enum { OFL_EL_F16 = 0, OFL_EL_BF16 = 1, OFL_EL_F32 = 2, OFL_EL_F64 = 3 };
+
 /* sample-position quantisation of the bilinear gather */
 enum {
     OFL_QUANT_OPENCV = 0,   /* cv2.remap semantics: coordinates snapped to 1/32 px (INTER_BITS = 5) */
@@ -107,6 +110,15 @@ int         ofl_host_free(void *hptr);
 int         ofl_stream_create(void **stream);
 int         ofl_stream_destroy(void *stream);
 int         ofl_stream_sync(void *stream);        /* NULL = default stream */
+/* `stream` (NULL = the library's) waits, on the device, for everything queued so far on `producer_stream`, a stream of
+ * another framework in this process (NULL = the legacy default stream, (void *)2 = the per-thread default stream): an
+ * event without timing is recorded there, hipStreamWaitEvent enqueued here, the event destroyed.  Never blocks the host.
+ * Needed because the library's streams are non-blocking: they do not order themselves after anyone else's work. */
+int         ofl_stream_wait_external(void *producer_stream, void *stream);
+/* hipPointerGetAttributes: *is_device = 1 and *device = its ordinal for device memory, 0 and -1 for anything else --
+ * NULL, registered host memory, managed memory, and plain host memory the runtime has never seen (HIP's error for that is
+ * cleared: it is an answer, not a failure).  Callers check every foreign pointer with it before a kernel is launched. */
+int         ofl_pointer_info(const void *p, int *is_device, int *device);
 int         ofl_device_sync(void);
 int         ofl_event_create(void **event);
 int         ofl_event_destroy(void *event);
@@ -596,6 +608,33 @@ int ofl_pad_flow_dev(const float *vecs, const uint8_t *mask, int H, int W, int t
                      int mode, float *out_vecs, uint8_t *out_mask, void *stream);
 int ofl_crop_flow_dev(const float *vecs, const uint8_t *mask, int H, int W, int row0, int row_step, int rows,
                       int col0, int col_step, int cols, float *out_vecs, uint8_t *out_mask, void *stream);
+
+/* ------------------------------------------------------------------ K11: fields and images of another framework
+ * Conversions between the layouts and element types other frameworks keep in device memory and the library's own
+ * ([H][W][2] float32 + uint8 mask, images [H][W][C]).  Strides are in ELEMENTS, >= 0 (0 = a broadcast dimension), 64-bit;
+ * the caller guarantees that every address they reach is device memory of this device (ofl_pointer_info).  Streaming
+ * kernels, every entry only enqueues work.  A lane owns 4 horizontally adjacent pixels of a row and accesses each
+ * address as widely as its alignment allows -- decided per address, so any element-aligned view is correct.
+ *
+ *   ofl_import_flow_dev    n fields from `src` (OFL_EL_*) with strides (field, channel, row, column) into out_vecs
+ *                          [n][H][W][2] float32 and out_mask [n][H][W] uint8.  f16 / bf16 -> float32 exactly, f64 ->
+ *                          float32 to nearest even.  mask_src: 1-byte elements with strides (field, row, column), out =
+ *                          (m != 0); NULL: all valid.  counters (device uint32[2], zeroed by the caller) or NULL:
+ *                          [0] += vector components whose float32 value is not finite, [1] += mask bytes that are neither
+ *                          0 nor 1.  out_vecs and out_mask may both be NULL: count only.  out_vecs 8-byte aligned.
+ *   ofl_export_flow_dev    vecs [n][H][W][2] float32 into a contiguous dst of OFL_EL_F16 / BF16 / F32, [n][H][W][2] or, with
+ *                          planar != 0, [n][2][H][W].  To nearest even, overflow to +-inf; bf16 on the bit pattern, every
+ *                          NaN becomes 0x7fc0.
+ *   ofl_permute_image_dev  to_hwc != 0: src [C][H][W] with strides (channel, row, column) -> dst contiguous [H][W][C];
+ *                          to_hwc == 0: src contiguous [H][W][C] -> dst [C][H][W] with those strides.  Elements of 1, 2, 4
+ *                          or 8 bytes move unchanged; C in [1, 6].
+ */
+int ofl_import_flow_dev(const void *src, int elem, int64_t s_field, int64_t s_chan, int64_t s_row, int64_t s_col,
+                        int n, int H, int W, const uint8_t *mask_src, int64_t m_field, int64_t m_row, int64_t m_col,
+                        float *out_vecs, uint8_t *out_mask, uint32_t *counters, void *stream);
+int ofl_export_flow_dev(const float *vecs, int n, int H, int W, int elem, int planar, void *dst, void *stream);
+int ofl_permute_image_dev(const void *src, void *dst, int elem_bytes, int C, int H, int W,
+                          int64_t s_chan, int64_t s_row, int64_t s_col, int to_hwc, void *stream);
 
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`

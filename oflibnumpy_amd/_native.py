@@ -22,6 +22,7 @@ STAT_NONZERO_MASKED, STAT_NONZERO_TH_MASKED, STAT_NONZERO, STAT_NONZERO_TH, STAT
 VIS_HSV, VIS_RGB, VIS_BGR = 0, 1, 2
 VIS_SHOW_MASK, VIS_MASK_BORDERS = 1, 2
 TRACK_F64, TRACK_I32, TRACK_I64 = 0, 1, 2
+EL_F16, EL_BF16, EL_F32, EL_F64 = 0, 1, 2, 3
 
 
 class MeshCert(ctypes.Structure):
@@ -45,6 +46,7 @@ class NoDeviceError(NativeError):
 
 _vp, _ci, _cs, _cf, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_double
 _pvp = ctypes.POINTER(ctypes.c_void_p)
+_i64 = ctypes.c_int64
 
 # name -> (restype, argtypes); must list every symbol of include/ofl.h (tests check this)
 SIGNATURES = {
@@ -127,6 +129,11 @@ SIGNATURES = {
     "ofl_scale_dev": (_ci, [_vp, _cd, _cd, _ci, _ci, _cs, _vp, _vp]),
     "ofl_pad_flow_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
     "ofl_crop_flow_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "ofl_stream_wait_external": (_ci, [_vp, _vp]),
+    "ofl_pointer_info": (_ci, [_vp, ctypes.POINTER(_ci), ctypes.POINTER(_ci)]),
+    "ofl_import_flow_dev": (_ci, [_vp, _ci, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "ofl_export_flow_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
+    "ofl_permute_image_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _ci, _vp]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

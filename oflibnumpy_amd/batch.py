@@ -79,6 +79,28 @@ class DeviceFlowBatch:
         nat.check(nat.load().ofl_memset(b.mask.ptr, 1, b.n * b.shape[0] * b.shape[1], None))
         return b
 
+    @classmethod
+    def from_external(cls, vecs, ref, masks=None, layout=None, dtype=None, stream=None, check_finite=True):
+        """n fields another framework holds in device memory -- a network's output -- in ONE launch and without crossing
+        PCIe: `vecs.__cuda_array_interface__` describes (N, H, W, 2) ('hwc') or (N, 2, H, W) ('chw'); element types, strides,
+        `layout`, `dtype`, `stream`, `check_finite` and the errors as in DeviceFlow.from_external.  `masks`: such an object
+        (N, H, W) of bool or uint8, a DeviceBuffer of N * H * W bytes, or None (all valid).  Always a copy."""
+        from .utils import get_valid_ref
+        ref = get_valid_ref(ref)
+        v, m, n, shape = dev.import_flow(vecs, masks, layout, dtype, stream, True, check_finite, batch=True)
+        b = cls.__new__(cls)
+        b.n, b.shape, b.ref, b.vecs, b.packed, b.bits, b._mask = n, shape, ref, v, False, None, m
+        return b
+
+    def export(self, layout='hwc', dtype='float32', copy=True):
+        """The vectors of all fields as ONE DeviceArray: (N, H, W, 2) for 'hwc', (N, 2, H, W) for 'chw', of float32, float16
+        or bfloat16 (as int16) -- see DeviceFlow.export, also for copy=False."""
+        return dev.export_flow(self.vecs, self.n, self.shape, layout, dtype, copy, self, batch=True)
+
+    def export_masks(self, copy=True):
+        """The masks as a DeviceArray of bool, (N, H, W); copy=False: a view of the batch's own masks, not to be written."""
+        return dev.export_mask(self.mask, (self.n,) + self.shape, copy, self)
+
     def to_flows(self):
         h, w = self.shape
         v = self.vecs.to_host((self.n, h, w, 2), np.float32)

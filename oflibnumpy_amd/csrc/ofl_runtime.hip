@@ -210,6 +210,43 @@ int ofl_stream_sync(void *stream)
     return OFL_OK;
 }
 
+// Orders `stream` after everything queued so far on another framework's stream, on the device: an event recorded there,
+// a wait enqueued here.  The library's streams are hipStreamNonBlocking, so nothing else orders them after foreign work --
+// not even after the legacy default stream.  Destroying the event straight away is allowed: the runtime releases it once
+// the wait has been served.  The host never blocks.
+int ofl_stream_wait_external(void *producer_stream, void *stream)
+{
+    OFL_TRY(need_device());
+    hipEvent_t ev;
+    OFL_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, (hipStream_t)producer_stream);            // NULL: the legacy default stream
+    if (e == hipSuccess) e = hipStreamWaitEvent(stream_of(stream), ev, 0);
+    (void)hipEventDestroy(ev);
+    if (e != hipSuccess) return hip_fail(e, "ofl_stream_wait_external");
+    return OFL_OK;
+}
+
+int ofl_pointer_info(const void *p, int *is_device, int *device)
+{
+    OFL_TRY(need_device());
+    if (!is_device || !device) return fail(OFL_E_INVALID, "ofl_pointer_info: NULL");
+    *is_device = 0;
+    *device = -1;
+    if (!p) return OFL_OK;
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof(attr));
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess) {               // an address the runtime has never seen (plain host memory): an answer, not a failure
+        (void)hipGetLastError();
+        return OFL_OK;
+    }
+    if (attr.type == hipMemoryTypeDevice) {
+        *is_device = 1;
+        *device = attr.device;
+    }
+    return OFL_OK;
+}
+
 int ofl_device_sync(void)
 {
     OFL_TRY(need_device());
