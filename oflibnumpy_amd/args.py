@@ -1,0 +1,220 @@
+"""Host halves of the resident layer: argument checks with the reference's exception types and messages, and the small pure
+tables and helpers the launch wrappers share.  Nothing here touches the device: the module imports -- and every function
+in it runs -- without the native library.
+"""
+import numpy as np
+
+from . import _native as nat
+
+DEFAULT_THRESHOLD = 1e-3          # src/oflibnumpy/utils.py:22
+_DT_CODE = {np.dtype('uint8'): nat.U8, np.dtype('int16'): nat.I16, np.dtype('uint16'): nat.U16,
+            np.dtype('float32'): nat.F32, np.dtype('float64'): nat.F64}
+_TRACK_DT = {np.dtype('float64'): nat.TRACK_F64, np.dtype('int32'): nat.TRACK_I32, np.dtype('int64'): nat.TRACK_I64}
+
+
+def remap_rules(dtype, masked):
+    """(arith, rule) of an image gather: how the kernel reproduces the dtype of the reference's "concatenated array", the
+    image with its mask appended as one more channel for cv2.remap (flow_class.py:615, :626, :644-650).  `masked`: a target
+    mask is given -- a bool mask concatenates to the image's own dtype, the default int8 one widens uint8 to int16 and would
+    widen uint16 to int32 (TypeError).  The ONE table behind DeviceFlow.apply_image, apply_image_rows and
+    DeviceFlowBatch.apply_images."""
+    dtype = np.dtype(dtype)
+    if dtype == np.uint8:
+        return (nat.ARITH_NATIVE, nat.RULE_GE_HALF) if masked else (nat.ARITH_FLOAT_RNE, nat.RULE_GT_HALF)
+    if dtype == np.int16 or (dtype == np.uint16 and masked):
+        return nat.ARITH_NATIVE, nat.RULE_GT_HALF
+    if dtype == np.uint16:
+        raise TypeError("uint16 image with the default int8 mask needs an int32 remap, which cv2.remap does not provide")
+    return nat.ARITH_NATIVE, nat.RULE_EQ1
+
+
+def mask_bytes(mask):
+    """A host mask -> contiguous uint8: bool is viewed, anything else cast."""
+    m = np.ascontiguousarray(mask)
+    return m.view(np.uint8) if m.dtype == np.bool_ else m.astype(np.uint8)
+
+
+def _points_array(arr):
+    """A host array of points, checked like track_pts (utils.py:571-574, :592) -> contiguous (n, 2) float64, int32 or int64.
+    Other float dtypes become float64; any other dtype -- the narrow integers, which NumPy would add to the float32 vectors
+    in float32, included -- is a TypeError (the reference raises it for ref 's' only)."""
+    if not isinstance(arr, np.ndarray):
+        raise TypeError("Error tracking points: Pts needs to be a numpy array")
+    if arr.ndim != 2 or arr.shape[1] != 2:
+        raise ValueError("Error tracking points: Pts needs to have shape N-2")
+    if np.issubdtype(arr.dtype, np.floating):
+        return np.ascontiguousarray(arr, np.float64)
+    if arr.dtype in _TRACK_DT:
+        return np.ascontiguousarray(arr)
+    raise TypeError("Error tracking points: Pts numpy array needs to have a float or int (int32, int64) dtype")
+
+
+_VIS_MODES = {'hsv': nat.VIS_HSV, 'rgb': nat.VIS_RGB, 'bgr': nat.VIS_BGR}
+
+
+def visualise_args(mode, show_mask=False, show_mask_borders=False, range_max=None):
+    """Validation of Flow.visualise's arguments (flow_class.py:887-892, 917-920, 948-951), on the host before any device
+    work: -> (mode code, OFL_VIS_* flags, float32 range or None for the per-field default).  `range_max` must be a
+    Python float or int (bool included, NumPy's float32 not), > 0 and -- beyond the reference -- finite."""
+    if not isinstance(show_mask, bool):
+        raise TypeError("Error visualising flow: show_mask must be a bool, got {}".format(type(show_mask).__name__))
+    if not isinstance(show_mask_borders, bool):
+        raise TypeError("Error visualising flow: show_mask_borders must be a bool, got {}".format(type(show_mask_borders).__name__))
+    rc = None
+    if range_max is not None:
+        if not isinstance(range_max, (float, int)):
+            raise TypeError("Error visualising flow: range_max must be a float or an int, got {}".format(type(range_max).__name__))
+        if range_max <= 0:
+            raise ValueError("Error visualising flow: range_max must be positive, got {}".format(range_max))
+        if isinstance(range_max, float) and not np.isfinite(range_max):
+            raise ValueError("Error visualising flow: range_max must be finite, got {}".format(range_max))
+        with np.errstate(over='ignore'):        # a finite value beyond float32 divides like NumPy's float32 inf
+            rc = np.float32(float(range_max)) if abs(range_max) < 1e300 else np.float32(np.inf)
+    if not isinstance(mode, str) or mode not in _VIS_MODES:
+        raise ValueError("Error visualising flow: mode must be 'rgb', 'bgr' or 'hsv', got {!r}".format(mode))
+    flags = (nat.VIS_SHOW_MASK if show_mask else 0) | (nat.VIS_MASK_BORDERS if show_mask_borders else 0)
+    return _VIS_MODES[mode], flags, rc
+
+
+def percentile_ranks(n, q=99):
+    """(lo, hi, gamma) of np.percentile(a, q) over n float32 values (NumPy 2.x, method 'linear'): the result is
+    _lerp(sorted[lo], sorted[hi], gamma).  NumPy works in the array's dtype: q / float32(100), the virtual index
+    (n - 1) * q and gamma are float32 (numpy/lib/_function_base_impl.py, percentile / _quantile / _get_indexes)."""
+    qq = np.asanyarray(np.true_divide(q, np.float32(100)))
+    vi = np.asanyarray((n - 1) * qq)
+    prev = np.asanyarray(np.floor(vi))
+    if vi >= n - 1:                                      # NumPy then takes the last element twice
+        prev = np.asanyarray(-1.0)
+    prev = prev.astype(np.intp)
+    gamma = np.asanyarray(vi - prev, dtype=vi.dtype)
+    lo = n - 1 if prev < 0 else int(prev)
+    return lo, min(lo + 1, n - 1) if prev >= 0 else lo, np.float32(gamma)
+
+
+# -- build / scale / pad / crop: the host halves of the DeviceFlow constructors and operators
+_PAD_MODES = {'constant': 0, 'edge': 1, 'symmetric': 2}
+_N_TRANSFORM_VALUES = {'translation': 2, 'rotation': 3, 'scaling': 3}
+
+
+def matrix_args(matrix, shape, ref):
+    """Validation of utils.from_matrix (utils.py:328-334) -> (the float64 matrix the kernel evaluates, sign, ref): the
+    matrix itself and +1 for 's', its pseudo-inverse and -1 for 't' (utils.py:335-344)."""
+    from .utils import validate_shape, get_valid_ref
+    validate_shape(shape)
+    if not isinstance(matrix, np.ndarray):
+        raise TypeError("Error creating flow from matrix: Matrix needs to be a numpy array")
+    if matrix.shape != (3, 3):
+        raise ValueError("Error creating flow from matrix: Matrix needs to be a numpy array of shape (3, 3)")
+    ref = get_valid_ref(ref)
+    m = matrix if ref == 's' else np.linalg.pinv(matrix)
+    return np.ascontiguousarray(m, np.float64), (1 if ref == 's' else -1), ref
+
+
+def validate_transforms(transform_list, shape):
+    """Validation of utils.from_transforms (utils.py:381-420)."""
+    from .utils import validate_shape
+    validate_shape(shape)
+    if not isinstance(transform_list, list):
+        raise TypeError("Error creating flow from transforms: Transform_list needs to be a list")
+    if not all(isinstance(t, list) for t in transform_list):
+        raise TypeError("Error creating flow from transforms: Transform_list needs to be a list of lists")
+    if not all(len(t) > 1 for t in transform_list):
+        raise ValueError("Error creating flow from transforms: Invalid transforms passed")
+    for t in transform_list:
+        if t[0] not in _N_TRANSFORM_VALUES:
+            raise ValueError("Error creating flow from transforms: Transform '{}' not recognised".format(t[0]))
+        if len(t) - 1 != _N_TRANSFORM_VALUES[t[0]]:
+            raise ValueError("Error creating flow from transforms: Not enough transform values passed for "
+                             "'{}' - expected {}, got {}".format(t[0], _N_TRANSFORM_VALUES[t[0]], len(t) - 1))
+        if not all(isinstance(v, (float, int)) for v in t[1:]):
+            raise ValueError("Error creating flow from transforms: "
+                             "Transform values for '{}' need to be integers or floats".format(t[0]))
+
+
+def valid_mask_array(mask, shape):
+    """A host array given as a constructor's `mask`, checked like the Flow.mask setter (flow_class.py:142-161) -> uint8 (H, W)."""
+    if not isinstance(mask, np.ndarray):
+        raise TypeError("Error setting flow mask: Input is not a numpy array")
+    if mask.ndim != 2:
+        raise ValueError("Error setting flow mask: Input not 2-dimensional")
+    if mask.shape != (shape[0], shape[1]):
+        raise ValueError("Error setting flow mask: Input has a different shape than the flow vectors")
+    if ((mask != 0) & (mask != 1)).any():
+        raise ValueError("Error setting flow mask: Values must be 0 or 1")
+    return np.ascontiguousarray(mask.astype(np.bool_)).view(np.uint8)
+
+
+def scale_operand(other, shape, verb, noun):
+    """The operand of DeviceFlow * and /, checked like Flow._broadcast_operand (flow_class.py:377-443) -> (k0, k1, wide):
+    the factors of the two channels and whether NumPy would compute in float64 (np.result_type of float32 and the operand:
+    a float64 or integer list / array) or in float32 (a number, which NumPy treats as a weak scalar, or a float32 array)."""
+    try:
+        k = float(other)
+        return k, k, 0
+    except TypeError:
+        pass
+    if isinstance(other, list):
+        if len(other) != 2:
+            raise ValueError("Error {} flow: {} list not length 2".format(verb, noun))
+        arr = np.array(other)
+    elif isinstance(other, np.ndarray):
+        if other.ndim == 1 and other.size == 2:
+            arr = other
+        elif (other.ndim == 2 and other.shape == tuple(shape)) or other.shape == tuple(shape) + (2,):
+            raise TypeError("Error {} flow: {} arrays of the shape of the flow are not supported on the device; "
+                            "use the host Flow (Flow.from_device)".format(verb, noun))
+        else:
+            raise ValueError("Error {} flow: {} array is not one of the following: size 2, shape of the "
+                             "flow object, shape of the flow vectors".format(verb, noun))
+    else:
+        raise TypeError("Error {} flow: {} cannot be converted to float, or isn't a list or numpy array"
+                        .format(verb, noun))
+    try:
+        res = np.result_type(np.float32, arr.dtype)
+    except TypeError:
+        res = None
+    if res not in (np.float32, np.float64):
+        raise TypeError("Error {} flow: {} of dtype {} does not combine with float32 vectors to float32 or float64"
+                        .format(verb, noun, arr.dtype))
+    return float(arr[0]), float(arr[1]), int(res == np.float64)
+
+
+def crop_args(item, shape):
+    """The index of DeviceFlow[...] -> ((row0, row_step, rows), (col0, col_step, cols)), normalised with slice.indices."""
+    if isinstance(item, slice):
+        item = (item,)
+    if not isinstance(item, tuple) or not 1 <= len(item) <= 2 or not all(isinstance(s, slice) for s in item):
+        raise TypeError("Error slicing flow: DeviceFlow takes a slice or a tuple of one or two slices (rows, columns); "
+                        "for any other index use the host Flow (Flow.from_device)")
+    out = []
+    for s, n in zip(item + (slice(None),) * (2 - len(item)), shape):
+        start, stop, step = s.indices(n)
+        count = len(range(start, stop, step))
+        if count == 0:
+            raise ValueError("Error slicing flow: the slices select no pixels of the {}x{} field".format(*shape))
+        out.append((start, step, count))
+    return tuple(out)
+
+
+def resize_scales(scale, error_string="Error resizing flow: "):
+    """Validation of resize_flow's `scale` (utils.py:505-518): returns (vertical, horizontal) factors."""
+    if isinstance(scale, (float, int)):
+        scale = [scale, scale]
+    elif isinstance(scale, (tuple, list)):
+        if len(scale) != 2:
+            raise ValueError(error_string + "Scale {} must have a length of 2".format(type(scale)))
+        if not all(isinstance(item, (float, int)) for item in scale):
+            raise ValueError(error_string + "Scale {} items must be integers or floats".format(type(scale)))
+    else:
+        raise TypeError(error_string + "Scale must be an integer, float, or list or tuple of integers or floats")
+    if any(s <= 0 for s in scale):
+        raise ValueError(error_string + "Scale values must be larger than 0")
+    return float(scale[0]), float(scale[1])
+
+
+def resized_shape(h, w, fy, fx):
+    """cv2.resize(dsize=None, fx, fy): dsize = (cvRound(W * fx), cvRound(H * fy)), round half to even."""
+    ho, wo = int(np.rint(h * fy)), int(np.rint(w * fx))
+    if ho <= 0 or wo <= 0:
+        raise ValueError("Error resizing flow: scale {} leaves no pixels of a {}x{} field".format((fy, fx), h, w))
+    return ho, wo

@@ -56,7 +56,7 @@ class DeviceFlowBatch:
         px = shape[0] * shape[1]
         lib = nat.load()
         for i, f in enumerate(flows):
-            m = np.ascontiguousarray(f.mask).view(np.uint8)
+            m = dev.mask_bytes(f.mask)
             v = np.ascontiguousarray(f.vecs, np.float32)       # Flow.vecs keeps the layout of its input (astype order 'K')
             nat.check(lib.ofl_upload(b.vecs.ptr + i * px * 8, v.ctypes.data, px * 8, None))
             nat.check(lib.ofl_upload(b.mask.ptr + i * px, m.ctypes.data, px, None))
@@ -129,20 +129,14 @@ class DeviceFlowBatch:
         (ref 't' batches; Flow.apply, flow_class.py:604-695 without padding).  `images`: a DeviceBuffer holding [n][H][W][C] of
         `dtype` back to back -- or ONE [H][W][C] image warped by every field when `shared`; `target_masks` uint8 [n][H][W] (one
         [H][W] when `shared_masks`) or None.  Returns (warped [n][H][W][C] DeviceBuffer, valid [n][H][W] DeviceBuffer), field
-        for field what DeviceFlow.apply_image gives (the dtype rules of the reference's concatenated array, device.apply_image).
+        for field what DeviceFlow.apply_image gives (the dtype rules of the reference's concatenated array, args.remap_rules).
         A field whose vectors are all below the 1e-3 threshold is warped like any other: under cv2's 1/32-px coordinate
         snapping that IS the identity of utils.py:215-216."""
         if self.ref != 't':
             raise ValueError("apply_images batches the gather ('t') warp; 's' fields go through DeviceFlow.apply_image one by one")
         dtype = np.dtype(dtype)
         h, w = self.shape
-        arith, rule = nat.ARITH_NATIVE, nat.RULE_EQ1
-        if dtype == np.uint8:      # concat dtype of the reference: bool mask -> uint8, default int8 -> int16
-            arith, rule = (nat.ARITH_NATIVE, nat.RULE_GE_HALF) if target_masks is not None else (nat.ARITH_FLOAT_RNE, nat.RULE_GT_HALF)
-        elif dtype == np.int16 or (dtype == np.uint16 and target_masks is not None):
-            rule = nat.RULE_GT_HALF
-        elif dtype == np.uint16:
-            raise TypeError("uint16 image with the default int8 mask needs an int32 remap, which cv2.remap does not provide")
+        arith, rule = dev.remap_rules(dtype, target_masks is not None)
         return dev.gather_bilinear_batch(images, dtype, channels, h, w, self.n, self.vecs, -1, smask=target_masks, fmask=self.mask,
                                          valid=True, shared_src=shared, shared_smask=shared_masks, quant=quant, arith=arith, rule=rule)
 
@@ -169,14 +163,11 @@ class DeviceFlowBatch:
 
     # -- point tracking (K10)
     def field(self, i):
-        """Field i as a DeviceFlow on this batch's memory (a view: it keeps the batch alive, nothing is copied)."""
+        """Field i as a DeviceFlow on this batch's memory (views: they keep the batch's buffers alive, nothing is copied)."""
         if not 0 <= i < self.n:
             raise IndexError("field {} of a batch of {}".format(i, self.n))
         px = self.shape[0] * self.shape[1]
-        f = dev.DeviceFlow(dev._BufferView(self.vecs.ptr + i * px * 8, px * 8), dev._BufferView(self.mask.ptr + i * px, px),
-                           self.shape, self.ref)
-        f._owner = self
-        return f
+        return dev.DeviceFlow(self.vecs.view(i * px * 8, px * 8), self.mask.view(i * px, px), self.shape, self.ref)
 
     def _stats_words(self):
         """uint32 [n] in HBM: the OFL_STAT_* word of every field, one launch of the statistics kernel per field and no
@@ -196,11 +187,9 @@ class DeviceFlowBatch:
         h, w = self.shape
         px = h * w
         maps = dev.DeviceBuffer(self.n * px)
-        lib = nat.load()
         for k in range(self.n):
-            nat.check(lib.ofl_gather_bilinear_dev(None, nat.U8, 0, h, w, self.vecs.ptr + k * px * 8, h, w, 0, 0, +1, None,
-                                                  self.mask.ptr + k * px, None, maps.ptr + k * px, nat.QUANT_OPENCV,
-                                                  nat.ARITH_NATIVE, nat.RULE_EQ1, None))
+            dev.gather_valid_only(h, w, self.vecs.view(k * px * 8, px * 8), self.shape, +1, fmask=self.mask.view(k * px, px),
+                                  valid=maps.view(k * px, px))
         return maps
 
     @staticmethod
@@ -286,16 +275,16 @@ class DeviceFlowBatch:
             nat.check(nat.load().ofl_copy_dev(path.buf.ptr, dp.buf.ptr, n * 16, None))
         for k in range(B):
             last = k == B - 1
-            vecs = dev._BufferView(self.vecs.ptr + k * px * 8, px * 8)
+            vecs = self.vecs.view(k * px * 8, px * 8)
             valid = self.field(k).valid_source() if status is not None else None
             vals, found = dev.scatter_query_resident(vecs, -1, vecs, h, w, query, n)
             nxt = None if last else dev.DeviceBuffer(n * 16)
             out_rc = None
             if path is not None:
-                out_rc = dev._BufferView(path.buf.ptr + (k + 1) * n * 16, n * 16)
+                out_rc = path.buf.view((k + 1) * n * 16, n * 16)
             elif last and not int_out:
                 out_rc = out.buf
-            dev.track_query_epilogue(query, vals, found, n, self.shape, dev._BufferView(words.ptr + 4 * k, 4), valid, k, status,
+            dev.track_query_epilogue(query, vals, found, n, self.shape, words.view(4 * k, 4), valid, k, status,
                                      out_rc=out_rc, out_int=out.buf if last and int_out else None, next_query=nxt, lost_at=lost_at)
             query = nxt
         if path is not None and not int_out:

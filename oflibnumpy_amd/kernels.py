@@ -1,0 +1,265 @@
+"""Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
+statistics, K7 visualise, K8 matrix fit, K9 build / resize and K10 tracking.  Each wrapper allocates what the entry needs,
+passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
+with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
+visualise_launch) stay next to that class in device.py.
+"""
+import numpy as np
+
+from . import _native as nat
+from .memory import DeviceBuffer, _BufferView, _lib, _ptr, _size_query
+from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, percentile_ranks, resize_scales, resized_shape, mask_bytes,
+                   valid_mask_array)
+
+
+# ------------------------------------------------------------------------------ K1: gather
+def gather_bilinear_batch(src, dtype, C, H, W, batch, flow, sign, smask=None, fmask=None, dst=None, valid=None,
+                          shared_src=False, shared_smask=False, flow_shape=None, pad=(0, 0),
+                          quant=nat.QUANT_OPENCV, arith=nat.ARITH_NATIVE, rule=nat.RULE_EQ1, stream=None):
+    """K1 over `batch` fields in ONE launch (ofl_gather_bilinear_batch_dev): buffers hold the fields back to back -- flow
+    [B][fH][fW][2], fmask [B][fH][fW], src [B][H][W][C] (or one [H][W][C] image for all with shared_src), smask likewise,
+    dst [B][H][W][C], valid [B][H][W].  dst / valid are allocated when not given (valid only if `valid is True`).
+    Returns (dst buffer, valid buffer or None)."""
+    dtype = np.dtype(dtype)
+    fH, fW = flow_shape if flow_shape is not None else (H, W)
+    if dst is None:
+        dst = DeviceBuffer(batch * H * W * C * dtype.itemsize)
+    if valid is True:
+        valid = DeviceBuffer(batch * H * W)
+    nat.check(_lib().ofl_gather_bilinear_batch_dev(
+        _ptr(src), 1 if shared_src else 0, _DT_CODE[dtype], C, H, W, batch, flow.ptr, fH, fW, pad[0], pad[1], sign,
+        _ptr(smask), 1 if shared_smask else 0, _ptr(fmask), _ptr(dst if C else None), _ptr(valid), quant, arith, rule, stream))
+    return dst, valid
+
+
+def gather_valid_only(H, W, flow_buf, flow_shape, sign, smask=None, fmask=None, pad=(0, 0),
+                      quant=nat.QUANT_OPENCV, rule=nat.RULE_EQ1, stream=None, valid=None):
+    """K1 without image channels: where does a warped all-ones (or smask) image stay == 1?
+    (valid_target 't' flow_class.py:1148-1150, valid_source 's' :1179-1183).  -> `valid`, allocated when not given."""
+    valid = DeviceBuffer(H * W) if valid is None else valid
+    nat.check(_lib().ofl_gather_bilinear_dev(
+        None, nat.U8, 0, H, W, flow_buf.ptr, flow_shape[0], flow_shape[1], pad[0], pad[1], sign,
+        _ptr(smask), _ptr(fmask), None, valid.ptr, quant, nat.ARITH_NATIVE, rule, stream))
+    return valid
+
+
+# ------------------------------------------------------------------------------ K4: statistics, K2: compose
+def flow_stats(vecs_buf, mask_buf, n_px, stream=None):
+    """K4: OFL_STAT_* bits of one field (utils.py:527-544, flow_class.py:1230-1245)."""
+    out = DeviceBuffer(16)
+    nat.check(_lib().ofl_flow_stats_dev(vecs_buf.ptr, _ptr(mask_buf), n_px, np.float32(DEFAULT_THRESHOLD), out.ptr, stream))
+    return int(out.to_host((1,), np.uint32, stream)[0])
+
+
+def compose3_launch(fa, fb, sign, out, stats_buf=None, stats_offset=0, batch=1, quant=nat.QUANT_OPENCV,
+                    stream=None):
+    """K2 launch on raw DeviceFlow-like triples; asynchronous.  stats_buf: uint32[batch][8] words."""
+    H, W = fa.shape
+    sp = None if stats_buf is None else stats_buf.ptr + stats_offset
+    nat.check(_lib().ofl_compose3_dev(fa.vecs.ptr, fa.mask.ptr, fb.vecs.ptr, fb.mask.ptr, sign, H, W, batch,
+                                      out.vecs.ptr, out.mask.ptr, sp, quant, stream))
+
+
+def mask_bits_bytes(h, w, batch=1):
+    return _size_query(_lib().ofl_mask_bits_bytes, h, w, batch)
+
+
+def mask_pack(mask_buf, h, w, batch=1, stream=None):
+    """uint8 masks [batch][H][W] -> packed bit planes [batch][H][(W + 31) / 32] uint32 (ofl_mask_pack_dev)"""
+    bits = DeviceBuffer(mask_bits_bytes(h, w, batch))
+    nat.check(_lib().ofl_mask_pack_dev(mask_buf.ptr, h, w, batch, bits.ptr, stream))
+    return bits
+
+
+def mask_unpack(bits_buf, h, w, batch=1, stream=None):
+    mask = DeviceBuffer(batch * h * w)
+    nat.check(_lib().ofl_mask_unpack_dev(bits_buf.ptr, h, w, batch, mask.ptr, stream))
+    return mask
+
+
+def compose3_bits_launch(fa_vecs, fa_bits, fb_vecs, fb_bits, sign, shape, out_vecs, out_bits, stats_buf=None, stats_offset=0, batch=1, stream=None):
+    """K2 on packed mask planes (ofl_compose3_bits_dev); asynchronous."""
+    sp = None if stats_buf is None else stats_buf.ptr + stats_offset
+    nat.check(_lib().ofl_compose3_bits_dev(fa_vecs.ptr, fa_bits.ptr, fb_vecs.ptr, fb_bits.ptr, sign, shape[0], shape[1], batch,
+                                           out_vecs.ptr, out_bits.ptr, sp, stream))
+
+
+# ------------------------------------------------------------------------------ K7: visualise, K8: matrix fit
+def visualise_range_launch(vecs, h, w, batch, out, stream=None):
+    """K7 range select: out (float32[batch] on the device) <- the default range_max of every field, flow_class.py:910-916.
+    Asynchronous."""
+    lo, hi, gamma = percentile_ranks(h * w)
+    ws = DeviceBuffer(_size_query(_lib().ofl_visualise_workspace_bytes, h, w, batch))
+    nat.check(_lib().ofl_visualise_range_dev(vecs.ptr, h, w, batch, np.float32(DEFAULT_THRESHOLD), lo, hi, gamma,
+                                             ws.ptr, ws.nbytes, out.ptr, stream))
+
+
+class FitField:
+    """The K8 passes over one HBM-resident field (csrc/ofl_fit.hip), as the object matrix_fit.fit drives: each method
+    enqueues one entry of include/ofl.h and reads its few numbers back.  mask: DeviceBuffer or None (every pixel counts);
+    gate: None or (3x3 model, float32 squared threshold)."""
+
+    def __init__(self, vecs, mask, shape, sign, stream=None):
+        self.vecs, self.mask, self.sign, self.stream = vecs, mask, sign, stream
+        self.h, self.w = int(shape[0]), int(shape[1])
+        self.origin = ((self.w - 1) / 2.0, (self.h - 1) / 2.0)            # the grid centre
+        self.ws = DeviceBuffer(_size_query(_lib().ofl_fit_workspace_bytes, self.h, self.w))
+        self.out = DeviceBuffer(1024)
+
+    def _field(self):
+        return (self.vecs.ptr, _ptr(self.mask), self.h, self.w)
+
+    @staticmethod
+    def _doubles(values):
+        a = np.ascontiguousarray(values, np.float64)
+        return a, a.ctypes.data
+
+    def _gate(self, gate):
+        if gate is None:
+            return None, None, np.float32(0)
+        keep, ptr = self._doubles(gate[0])
+        return keep, ptr, np.float32(gate[1])
+
+    def _sums(self, entry, count, gate, *params):
+        keep, gptr, thr = self._gate(gate)
+        held = [self._doubles(p) for p in params]
+        nat.check(entry(*self._field(), self.sign, *[p for _, p in held], gptr, thr, self.ws.ptr, self.ws.nbytes,
+                        self.out.ptr, self.stream))
+        return self.out.to_host((count,), np.float64, self.stream)
+
+    def moments(self, gate=None):
+        return self._sums(_lib().ofl_fit_moments_dev, 16, gate, self.origin)
+
+    def dlt(self, norm, gate=None):
+        return self._sums(_lib().ofl_fit_dlt_dev, 47, gate, norm)
+
+    def gn(self, norm, model, gate=None):
+        return self._sums(_lib().ofl_fit_gn_dev, 47, gate, norm, model)
+
+    def score(self, models, thr):
+        m, ptr = self._doubles(models)
+        k = m.size // 9
+        nat.check(_lib().ofl_fit_score_dev(*self._field(), self.sign, ptr, k, np.float32(thr), self.out.ptr, self.stream))
+        return self.out.to_host((k,), np.uint32, self.stream)
+
+    def median(self, models, rank_lo, rank_hi):
+        m, ptr = self._doubles(models)
+        k = m.size // 9
+        out = self.out if k * 8 <= self.out.nbytes else DeviceBuffer(k * 8)
+        nat.check(_lib().ofl_fit_median_dev(*self._field(), self.sign, ptr, k, rank_lo, rank_hi, self.ws.ptr, self.ws.nbytes,
+                                            out.ptr, self.stream))
+        return out.to_host((k, 2), np.uint32, self.stream)
+
+    def index(self):
+        nat.check(_lib().ofl_fit_index_dev(*self._field(), self.ws.ptr, self.ws.nbytes, self.stream))
+
+    def pick(self, ranks):
+        """pixel indices and gathered records (count, 4) uint32 of the ranks-th valid pixels (after index())"""
+        ranks = np.ascontiguousarray(ranks, np.uint32)
+        n = ranks.size
+        rbuf = DeviceBuffer.from_host(ranks, self.stream)
+        idx, rec = DeviceBuffer(n * 4), DeviceBuffer(n * 16)
+        nat.check(_lib().ofl_fit_pick_dev(*self._field(), self.ws.ptr, self.ws.nbytes, rbuf.ptr, n, idx.ptr, self.stream))
+        nat.check(_lib().ofl_fit_gather_dev(*self._field(), idx.ptr, n, rec.ptr, self.stream))
+        return rec.to_host((n, 4), np.uint32, self.stream)
+
+    def sample(self, ranks):
+        """-> (src, dst): (count, 2) float64 correspondences of the ranks-th valid pixels"""
+        rec = self.pick(ranks)
+        idx = rec[:, 0].astype(np.int64)
+        grid = np.stack([idx % self.w, idx // self.w], axis=-1).astype(np.float64)
+        v = np.ascontiguousarray(rec[:, 1:3]).view(np.float32).astype(np.float64)
+        return (grid, grid + v) if self.sign > 0 else (grid - v, grid)
+
+
+# ------------------------------------------------------------------------------ K9: build / resize, small helpers
+def _valid_mask(mask, shape):
+    """A constructor's `mask` argument: None, a DeviceBuffer of at least H * W bytes (0 / 1, taken as it is), or a host array
+    checked like the Flow.mask setter (args.valid_mask_array) -> None, the buffer, or uint8 (H, W)."""
+    if mask is None:
+        return None
+    if isinstance(mask, (DeviceBuffer, _BufferView)):
+        if mask.nbytes < int(shape[0]) * int(shape[1]):
+            raise ValueError("Error setting flow mask: Input has a different shape than the flow vectors")
+        return mask
+    return valid_mask_array(mask, shape)
+
+
+def _mask_buffer(mask, shape):
+    """What _valid_mask returned -> the field's mask buffer: all ones for None, an upload for a host array."""
+    if mask is None:
+        buf = DeviceBuffer(int(shape[0]) * int(shape[1]))
+        nat.check(_lib().ofl_memset(buf.ptr, 1, int(shape[0]) * int(shape[1]), None))
+        return buf
+    return DeviceBuffer.from_host(mask) if isinstance(mask, np.ndarray) else mask
+
+
+def flow_from_matrix_launch(mats, n, sign, shape, out, stream=None):
+    """K9 constructor: `n` fields [n][H][W][2] into `out` from `mats`, n x 9 float64 on the device.  Asynchronous."""
+    nat.check(_lib().ofl_flow_from_matrix_dev(mats.ptr, n, sign, shape[0], shape[1], out.ptr, stream))
+
+
+def _mask_and(a, b, out, n):
+    """out = a & b for uint8 masks (flow_class.py:643)."""
+    nat.check(_lib().ofl_mask_and_dev(a.ptr, b.ptr, out.ptr, n, None))
+
+
+def resize_host(vecs, mask, scale):
+    """resize_flow / Flow.resize for host arrays through ofl_resize_flow (upload, one launch, download)."""
+    fy, fx = resize_scales(scale)
+    vecs = np.ascontiguousarray(vecs, np.float32)
+    h, w = vecs.shape[:2]
+    ho, wo = resized_shape(h, w, fy, fx)
+    out = np.empty((ho, wo, 2), np.float32)
+    m = None if mask is None else mask_bytes(mask)
+    mout = None if mask is None else np.empty((ho, wo), np.uint8)
+    hp = lambda a: None if a is None else a.ctypes.data
+    nat.check(_lib().ofl_resize_flow(hp(vecs), hp(m), h, w, ho, wo, 1.0 / fy, 1.0 / fx,
+                                     float(np.float32(fx)), float(np.float32(fy)), hp(out), hp(mout)))
+    return out, (None if mout is None else mout.astype(bool))
+
+
+def grid_minus(vecs, out, h, w):
+    """out = float32(grid - vecs): the query positions of mode 2 / ref 't' (flow_class.py:1404-1406)."""
+    nat.check(_lib().ofl_grid_offset_dev(vecs.ptr, -1, h, w, out.ptr, None))
+
+
+def sample_points(flow_buf, h, w, pts_rc):
+    """Bilinear flow samples (v, u) at float64 points (row, col): utils.py:161-196 / :605."""
+    pts = np.ascontiguousarray(pts_rc, np.float64)
+    n = pts.shape[0]
+    dp = DeviceBuffer.from_host(pts)
+    out = DeviceBuffer(max(n, 1) * 16)
+    nat.check(_lib().ofl_sample_points_dev(flow_buf.ptr, h, w, dp.ptr, n, out.ptr, None))
+    return out.to_host((n, 2), np.float64)
+
+
+# ------------------------------------------------------------------------------ K10: tracking with resident points
+def stats_word_launch(vecs_ptr, mask_ptr, n_px, out_ptr, stream=None):
+    """K4 into a device uint32 at out_ptr, asynchronous: the OFL_STAT_* word of one field, left in HBM for a kernel to read."""
+    nat.check(_lib().ofl_flow_stats_dev(vecs_ptr, mask_ptr, n_px, np.float32(DEFAULT_THRESHOLD), out_ptr, stream))
+
+
+def track_bilinear_launch(flows_ptr, n_fields, shape, chain, pts, stats, valid, int_out, out, status, outside=None,
+                          lost_at=None, path=None, stream=None):
+    """K10, ref 's' with bilinear sampling (ofl_track_bilinear_dev); asynchronous.  pts: float64 DevicePoints."""
+    if pts.dtype != np.float64:
+        raise TypeError("Error tracking points: the bilinear tracking kernel takes float64 points, got {}".format(pts.dtype))
+    nat.check(_lib().ofl_track_bilinear_dev(flows_ptr, n_fields, shape[0], shape[1], 1 if chain else 0, pts.buf.ptr, pts.n,
+                                            _ptr(stats), _ptr(valid), int(bool(int_out)), out.ptr, _ptr(status),
+                                            _ptr(outside), _ptr(lost_at), _ptr(path), stream))
+
+
+def track_query_points(pts, stream=None):
+    """DevicePoints (row, col) -> DeviceBuffer of float64 (x, y) queries for the scatter kernel; asynchronous."""
+    query = DeviceBuffer(pts.n * 16)
+    nat.check(_lib().ofl_track_query_points_dev(pts.buf.ptr, _TRACK_DT[pts.dtype], pts.n, query.ptr, stream))
+    return query
+
+
+def track_query_epilogue(query, vals, found, n, shape, stats, valid, step, status, out_rc=None, out_int=None, next_query=None,
+                         lost_at=None, stream=None):
+    """K10 tail of the query paths (ofl_track_query_epilogue_dev); asynchronous."""
+    nat.check(_lib().ofl_track_query_epilogue_dev(query.ptr, vals.ptr, found.ptr, n, shape[0], shape[1], _ptr(stats), _ptr(valid),
+                                                  step, _ptr(out_rc), _ptr(out_int), _ptr(next_query), _ptr(status),
+                                                  _ptr(lost_at), stream))

@@ -410,3 +410,46 @@ def test_png_reader_all_filter_types_native_equals_python(tmp_path):
             of.load_kitti(p2)
         with pytest.raises((ValueError, IndexError)):
             _png._unfilter_py(data, h, stride, bpp)
+
+
+def test_remap_rules_table():
+    """The dtype rules of the reference's "concatenated array" (image + mask channel in one cv2.remap) exist once, in
+    args.remap_rules, for DeviceFlow.apply_image, apply_image_rows and DeviceFlowBatch.apply_images: image dtype x "a target
+    mask is given" -> (arith, rule)."""
+    from oflibnumpy_amd import args, batch, device
+    want = {('uint8', True): (nat.ARITH_NATIVE, nat.RULE_GE_HALF), ('uint8', False): (nat.ARITH_FLOAT_RNE, nat.RULE_GT_HALF),
+            ('int16', True): (nat.ARITH_NATIVE, nat.RULE_GT_HALF), ('int16', False): (nat.ARITH_NATIVE, nat.RULE_GT_HALF),
+            ('uint16', True): (nat.ARITH_NATIVE, nat.RULE_GT_HALF),
+            ('float32', True): (nat.ARITH_NATIVE, nat.RULE_EQ1), ('float32', False): (nat.ARITH_NATIVE, nat.RULE_EQ1),
+            ('float64', True): (nat.ARITH_NATIVE, nat.RULE_EQ1), ('float64', False): (nat.ARITH_NATIVE, nat.RULE_EQ1)}
+    for (name, masked), rules in want.items():
+        for dtype in (name, np.dtype(name), np.dtype(name).type):
+            assert args.remap_rules(dtype, masked) == rules, (name, masked)
+    with pytest.raises(TypeError, match="uint16 image with the default int8 mask needs an int32 remap"):
+        args.remap_rules(np.uint16, False)
+    assert device.remap_rules is args.remap_rules
+    # the table is not written out a second time where it used to be
+    pkg = os.path.join(ROOT, "oflibnumpy_amd")
+    for fn in ("device.py", "batch.py"):
+        src = open(os.path.join(pkg, fn)).read()
+        assert "remap_rules(" in src and "RULE_GE_HALF" not in src and "ARITH_FLOAT_RNE" not in src, fn
+
+
+def test_device_namespace_is_stable():
+    """oflibnumpy_amd.device stays the public namespace of the resident layer: what bench.py and the package's __init__ take
+    from it is the very object of the module it now lives in.  The host-only half (args) imports without the native library
+    being loaded."""
+    import subprocess
+    import sys
+    from oflibnumpy_amd import device, memory, kernels, interop
+    homes = {"DeviceBuffer": memory, "empty_cache": memory, "compose3_launch": kernels, "DeviceArray": interop,
+             "external_args": interop, "DeviceFlow": device, "DeviceImage": device, "DevicePoints": device}
+    for name, home in homes.items():
+        assert getattr(device, name) is getattr(home, name), name
+        assert getattr(home, name).__module__ == home.__name__, name
+    for name in ("DeviceFlow", "DeviceImage", "DeviceBuffer", "DevicePoints", "DeviceArray", "external_args"):
+        assert getattr(of, name) is getattr(device, name), name
+    code = ("import sys; sys.path.insert(0, {!r}); import oflibnumpy_amd.args; import oflibnumpy_amd._native as n; "
+            "assert n._lib is None and n._device is None; print('args imported, library not loaded')".format(ROOT))
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "library not loaded" in p.stdout, p.stderr[-2000:]

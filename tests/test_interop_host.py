@@ -176,5 +176,5 @@ def test_the_package_imports_no_framework():
     for path in glob.glob(os.path.join(here, "*.py")):
         text = open(path).read()
         assert not re.search(r"^(import|from)\s+(torch|cupy|jax|numba)\b", text, flags=re.M), path
-        if os.path.basename(path) in ("device.py", "batch.py", "_native.py", "__init__.py"):
+        if os.path.basename(path) in ("device.py", "interop.py", "memory.py", "batch.py", "_native.py", "__init__.py"):
             assert not re.search(r"^\s*(import|from)\s+(torch|cupy|jax|numba)\b", text, flags=re.M), path
