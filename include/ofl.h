@@ -636,6 +636,36 @@ int ofl_export_flow_dev(const float *vecs, int n, int H, int W, int elem, int pl
 int ofl_permute_image_dev(const void *src, void *dst, int elem_bytes, int C, int H, int W,
                           int64_t s_chan, int64_t s_row, int64_t s_col, int to_hwc, void *stream);
 
+/* ------------------------------------------------------------------ K12: warping many-channel float tensors
+ * Flow.apply with reference 't' (utils.py:231-236, flow_class.py:604-695, without padding) for the feature maps of a
+ * network: N items of C channels, contiguous (N, C, H, W) or (N, H, W, C), of OFL_EL_F32, OFL_EL_F16 or OFL_EL_BF16
+ * (OFL_EL_F64 and anything else: OFL_E_INVALID).  src and dst share one layout; N and C in [1, 65535], H and W as K1
+ * allows; every element offset is 64-bit (N * C * H * W may exceed 2^31).  Asynchronous; a bad argument returns
+ * OFL_E_INVALID before any launch.
+ *
+ *   ofl_gather_tensor_dev   dst[n, c, y, x] = B(src[n, c]; (x, y) + sign * flow[y, x]) for every channel from ONE set of
+ *                           taps per pixel -- K1's coordinates, taps and blend, operation for operation; taps outside the
+ *                           frame read 0.  16-bit elements are widened to float32 (exact), blended in float32 and rounded
+ *                           once to the storage type, to nearest even with overflow to +-inf (ofl_export_flow_dev's
+ *                           rounding); a float32 tensor equals ofl_gather_bilinear_dev channel for channel, bit for bit.
+ *                           flow [H][W][2] and fmask [H][W] warp all N items when flow_shared != 0, else N fields and masks
+ *                           lie back to back.  valid (NULL: skipped) [N][H][W] = fmask & [interpolated smask == 1]
+ *                           (OFL_RULE_EQ1), one mask per item; smask [H][W] when smask_shared != 0, else [N][H][W], NULL: all
+ *                           ones.  With a shared field and a shared (or no) smask every item's mask is the same: valid is
+ *                           then ONE [H][W] mask.  valid needs fmask.
+ *   ofl_tensor_import_dev   a strided view -- element strides (item, channel, row, column) >= 0, elements of 2 or 4 bytes
+ *                           that move unchanged -- into a contiguous dst of `layout`.
+ *   ofl_tensor_permute_dev  contiguous (N, C, H, W) -> (N, H, W, C) with to_nhwc != 0, else the way back; any C.
+ */
+enum { OFL_TENSOR_NCHW = 0, OFL_TENSOR_NHWC = 1 };
+int ofl_gather_tensor_dev(const void *src, int elem, int layout, int N, int C, int H, int W,
+                          const float *flow, int flow_shared, int sign,
+                          const uint8_t *smask, int smask_shared, const uint8_t *fmask,
+                          void *dst, uint8_t *valid, int quant, void *stream);
+int ofl_tensor_import_dev(const void *src, int elem_bytes, int64_t s_item, int64_t s_chan, int64_t s_row, int64_t s_col,
+                          int layout, int N, int C, int H, int W, void *dst, void *stream);
+int ofl_tensor_permute_dev(const void *src, void *dst, int elem_bytes, int N, int C, int H, int W, int to_nhwc, void *stream);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

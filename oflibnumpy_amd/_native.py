@@ -23,6 +23,7 @@ VIS_HSV, VIS_RGB, VIS_BGR = 0, 1, 2
 VIS_SHOW_MASK, VIS_MASK_BORDERS = 1, 2
 TRACK_F64, TRACK_I32, TRACK_I64 = 0, 1, 2
 EL_F16, EL_BF16, EL_F32, EL_F64 = 0, 1, 2, 3
+TENSOR_NCHW, TENSOR_NHWC = 0, 1
 
 
 class MeshCert(ctypes.Structure):
@@ -134,6 +135,9 @@ SIGNATURES = {
     "ofl_import_flow_dev": (_ci, [_vp, _ci, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "ofl_export_flow_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
     "ofl_permute_image_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _ci, _vp]),
+    "ofl_gather_tensor_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _ci, _vp]),
+    "ofl_tensor_import_dev": (_ci, [_vp, _ci, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
+    "ofl_tensor_permute_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

@@ -10,6 +10,8 @@ DEFAULT_THRESHOLD = 1e-3          # src/oflibnumpy/utils.py:22
 _DT_CODE = {np.dtype('uint8'): nat.U8, np.dtype('int16'): nat.I16, np.dtype('uint16'): nat.U16,
             np.dtype('float32'): nat.F32, np.dtype('float64'): nat.F64}
 _TRACK_DT = {np.dtype('float64'): nat.TRACK_F64, np.dtype('int32'): nat.TRACK_I32, np.dtype('int64'): nat.TRACK_I64}
+_TENSOR_EL = {'float32': nat.EL_F32, 'float16': nat.EL_F16, 'bfloat16': nat.EL_BF16}
+_TENSOR_LAYOUT = {'chw': nat.TENSOR_NCHW, 'hwc': nat.TENSOR_NHWC}
 
 
 def remap_rules(dtype, masked):
@@ -218,3 +220,65 @@ def resized_shape(h, w, fy, fx):
     if ho <= 0 or wo <= 0:
         raise ValueError("Error resizing flow: scale {} leaves no pixels of a {}x{} field".format((fy, fx), h, w))
     return ho, wo
+
+
+# -- many-channel float tensors (K12)
+def tensor_dtype(array_dtype, dtype=None):
+    """The element type of a tensor -> 'float32', 'float16' or 'bfloat16'.  `array_dtype`: the dtype of the array that holds
+    it (a NumPy dtype, or the string 'bfloat16'); `dtype`: what the caller says it is, or None.  bfloat16, which NumPy does
+    not have, is a 2-byte integer array with dtype='bfloat16' (as in interop.external_args); anything but the three is a
+    TypeError."""
+    if str(array_dtype) == 'bfloat16':
+        return 'bfloat16'
+    array_dtype = np.dtype(array_dtype)
+    if dtype is not None and str(dtype) == 'bfloat16':
+        if array_dtype not in (np.int16, np.uint16):
+            raise TypeError("Error taking a tensor: dtype='bfloat16' reinterprets a 2-byte integer array, got {}".format(array_dtype))
+        return 'bfloat16'
+    if dtype is not None and np.dtype(dtype) != array_dtype:
+        raise TypeError("Error taking a tensor: the array is {}, not {}".format(array_dtype, np.dtype(dtype)))
+    if array_dtype.name not in ('float32', 'float16'):
+        raise TypeError("Error taking a tensor: tensors are float32, float16 or (a 2-byte integer array with dtype='bfloat16') "
+                        "bfloat16, got {}".format(array_dtype))
+    return array_dtype.name
+
+
+def tensor_args(shape, layout, dtype, field_shape=None):
+    """Checks of a tensor's description, on the host -> (n, c, h, w, batched).  `shape`: the LOGICAL shape (C, H, W) or
+    (N, C, H, W), whatever the memory order; `layout`: 'chw' or 'hwc', the memory order; `dtype`: one of the three names
+    (tensor_dtype); `field_shape`: the (H, W) of the field that is to warp it, or None."""
+    if layout not in _TENSOR_LAYOUT:
+        raise ValueError("Error taking a tensor: layout must be 'chw' or 'hwc', got {!r}".format(layout))
+    if dtype not in _TENSOR_EL:
+        raise TypeError("Error taking a tensor: dtype must be float32, float16 or bfloat16, got {}".format(dtype))
+    shape = tuple(int(v) for v in shape)
+    if len(shape) not in (3, 4):
+        raise ValueError("Error taking a tensor: shape {} is not (C, H, W) or (N, C, H, W)".format(shape))
+    batched = len(shape) == 4
+    n = shape[0] if batched else 1
+    c, h, w = shape[-3:]
+    if not 1 <= n <= 65535 or not 1 <= c <= 65535:
+        raise ValueError("Error taking a tensor: items and channels must be in [1, 65535], got {} and {}".format(n, c))
+    if not (1 <= h <= 32766 and 1 <= w <= 32766):
+        raise ValueError("Error taking a tensor: height and width must be in [1, 32766], got {} x {}".format(h, w))
+    if field_shape is not None and (h, w) != tuple(field_shape):
+        raise ValueError("tensor and flow need the same height and width, got {} and {}".format((h, w), tuple(field_shape)))
+    return n, c, h, w, batched
+
+
+def tensor_mem_shape(shape, layout):
+    """The logical shape (C, H, W) / (N, C, H, W) -> the shape of the array in memory order."""
+    shape = tuple(shape)
+    return shape if layout == 'chw' else shape[:-3] + (shape[-2], shape[-1], shape[-3])
+
+
+def tensor_logical_shape(mem_shape, layout):
+    """The shape of an array in memory order -- (C, H, W) / (N, C, H, W) for 'chw', (H, W, C) / (N, H, W, C) for 'hwc' -> the
+    logical shape.  Checks the layout string and the rank."""
+    if layout not in _TENSOR_LAYOUT:
+        raise ValueError("Error taking a tensor: layout must be 'chw' or 'hwc', got {!r}".format(layout))
+    mem_shape = tuple(int(v) for v in mem_shape)
+    if len(mem_shape) not in (3, 4):
+        raise ValueError("Error taking a tensor: shape {} is not {}".format(
+            mem_shape, "(C, H, W) or (N, C, H, W)" if layout == 'chw' else "(H, W, C) or (N, H, W, C)"))
+    return mem_shape if layout == 'chw' else mem_shape[:-3] + (mem_shape[-1], mem_shape[-3], mem_shape[-2])

@@ -140,6 +140,26 @@ class DeviceFlowBatch:
         return dev.gather_bilinear_batch(images, dtype, channels, h, w, self.n, self.vecs, -1, smask=target_masks, fmask=self.mask,
                                          valid=True, shared_src=shared, shared_smask=shared_masks, quant=quant, arith=arith, rule=rule)
 
+    def apply_tensors(self, tensor, target_masks=None, shared_masks=False, quant=nat.QUANT_OPENCV):
+        """self[i].apply_tensor(item i of `tensor`, target_mask_i) for every i in ONE launch of K12 (ref 't' batches):
+        `tensor` a DeviceTensor (n, C, H, W) in either layout, `target_masks` uint8 [n][H][W] (one [H][W] when
+        `shared_masks`) or None.  Returns (DeviceTensor, valid [n][H][W] DeviceBuffer).  Like apply_images this takes no
+        zero-flow short cut -- a field below the 1e-3 threshold is warped like any other, which under cv2's 1/32-px coordinate
+        snapping IS the identity of utils.py:215-216, value for value (a -0.0 comes back as +0.0, as from the image gather) -- and so only `quant=QUANT_OPENCV` is accepted: without the snapping
+        the warp of such a field would not be the identity the single call returns."""
+        if self.ref != 't':
+            raise ValueError("apply_tensors batches the gather ('t') warp: 's'-reference (scatter) warps of tensors are not supported")
+        if quant != nat.QUANT_OPENCV:
+            raise ValueError("apply_tensors takes no zero-flow short cut and is the reference's warp under quant=QUANT_OPENCV only; "
+                             "use DeviceFlow.apply_tensor field by field (field(i)) for QUANT_EXACT")
+        n, c, h, w, batched = dev.tensor_args(tensor.shape, tensor.layout, tensor.dtype, self.shape)
+        if not batched or n != self.n:
+            raise ValueError("apply_tensors needs a tensor of shape (n, C, H, W) with one item per field, got {} for {} fields"
+                             .format(tensor.shape, self.n))
+        dst, valid = dev.gather_tensor(tensor.buf, tensor.dtype, tensor.layout, n, c, h, w, self.vecs, False, -1,
+                                       smask=target_masks, smask_shared=shared_masks, fmask=self.mask, want_valid=True, quant=quant)
+        return dev.DeviceTensor(dst, tensor.shape, tensor.dtype, tensor.layout), valid
+
     def visualise(self, mode, show_mask=False, show_mask_borders=False, range_max=None):
         """self[i].visualise(...) for every i -> DeviceImage uint8 (n, H, W, 3): ONE range select (each field gets its own
         99th percentile unless `range_max` fixes one scale for all) and ONE render launch, asynchronous."""

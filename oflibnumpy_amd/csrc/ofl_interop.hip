@@ -3,6 +3,7 @@
 // of one row; every access is as wide as the ADDRESS it meets allows (decided per address, not per call: a view whose base
 // is one element off still takes the scalar path and is correct), the row tail W % 4 goes element by element.
 #include "ofl_common.h"
+#include "ofl_elem.h"
 
 #pragma clang fp contract(off)
 
@@ -96,37 +97,6 @@ __device__ __forceinline__ void store4(T *p, int64_t stride, int cnt, const T *v
             if (k < cnt) p[k * stride] = v[k];
     }
 }
-
-// ---------------------------------------------------------------------------------------------- element types of fields
-template <int E> struct Elem;
-
-template <> struct Elem<OFL_EL_F16> {
-    typedef uint16_t T;
-    static __device__ __forceinline__ float to_f32(T v) { return (float)__builtin_bit_cast(_Float16, v); }                // exact
-    static __device__ __forceinline__ T from_f32(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }           // nearest even, overflow -> inf
-};
-
-template <> struct Elem<OFL_EL_BF16> {
-    typedef uint16_t T;
-    static __device__ __forceinline__ float to_f32(T v) { return __uint_as_float((uint32_t)v << 16); }                    // exact
-    static __device__ __forceinline__ T from_f32(float f)       // nearest even on the bit pattern; every NaN becomes 0x7fc0
-    {
-        const uint32_t u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (T)0x7fc0;
-        return (T)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    }
-};
-
-template <> struct Elem<OFL_EL_F32> {
-    typedef float T;
-    static __device__ __forceinline__ float to_f32(T v) { return v; }
-    static __device__ __forceinline__ T from_f32(float f) { return f; }
-};
-
-template <> struct Elem<OFL_EL_F64> {
-    typedef double T;
-    static __device__ __forceinline__ float to_f32(T v) { return (float)v; }                                              // nearest even
-};
 
 __device__ __forceinline__ bool not_finite(float f) { return (__float_as_uint(f) & 0x7f800000u) == 0x7f800000u; }
 

@@ -7,7 +7,7 @@ keeps vectors and mask in GPU memory between operations, so chains such as combi
 (1 scatter + 2 gathers, flow_class.py:1369-1370) never cross PCIe.  The host `Flow` class is a thin
 upload -> DeviceFlow op -> download wrapper around this module.
 
-This module holds the three resident classes and the .flo I/O, and it is the public namespace of the whole resident layer:
+This module holds the four resident classes and the .flo I/O, and it is the public namespace of the whole resident layer:
 what the classes are built from is imported below and stays reachable as `device.X`.  It lives in memory.py (the HBM
 recycling pool, DeviceBuffer, views, the pinned-host pool), args.py (host-only argument checks and tables), kernels.py
 (launch wrappers of the gather, compose, statistics, visualise, fit, build and tracking kernels), scatter.py (the scatter
@@ -30,11 +30,12 @@ from .memory import (_lib, _ptr, _size_query, _Pool, _PinnedPool, empty_cache, D
                      PinnedArray, sync)
 from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rules, mask_bytes, _points_array, visualise_args,
                    percentile_ranks, matrix_args, validate_transforms, valid_mask_array, scale_operand, crop_args,
-                   resize_scales, resized_shape)
+                   resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
-                      track_bilinear_launch, track_query_points, track_query_epilogue)
+                      track_bilinear_launch, track_query_points, track_query_epilogue, gather_tensor, tensor_import_launch,
+                      tensor_permute_launch)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -178,6 +179,90 @@ class DevicePoints:
         """-> DeviceArray of this object's shape ((n, 2), or (fields, n, 2) from the batch calls): a device copy or, with
         copy=False, a view of the points' own memory that the consumer must not write."""
         return export_buffer(self.buf, self.shape, self.dtype.str, copy, self)
+
+
+_TENSOR_NP = {'float32': np.dtype('<f4'), 'float16': np.dtype('<f2'), 'bfloat16': np.dtype('<u2')}     # what to_host hands back
+_TENSOR_TYPESTR = {'float32': '<f4', 'float16': '<f2', 'bfloat16': '<i2'}                               # what export hands out
+
+
+class DeviceTensor:
+    """A many-channel float warp target in HBM -- a network's feature maps: `shape` is the logical (C, H, W) or (N, C, H, W),
+    `layout` the memory order, 'chw' (planar, [N][C][H][W]) or 'hwc' (channels last, [N][H][W][C]), `dtype` 'float32',
+    'float16' or 'bfloat16'.  Warped by DeviceFlow.apply_tensor and DeviceFlowBatch.apply_tensors (K12)."""
+
+    def __init__(self, buf, shape, dtype, layout):
+        self.n, self.channels, self.h, self.w, self.batched = tensor_args(shape, layout, dtype)
+        self.buf, self.shape, self.dtype, self.layout = buf, tuple(int(v) for v in shape), dtype, layout
+
+    @property
+    def itemsize(self):
+        return 4 if self.dtype == 'float32' else 2
+
+    @property
+    def nbytes(self):
+        return self.n * self.channels * self.h * self.w * self.itemsize
+
+    @classmethod
+    def from_host(cls, arr, layout='chw', dtype=None):
+        """A host array in the memory order of `layout` -- (C, H, W) / (N, C, H, W) for 'chw', (H, W, C) / (N, H, W, C) for
+        'hwc' -- of float32 or float16, or a 2-byte integer array with dtype='bfloat16'."""
+        arr = np.asarray(arr)
+        shape = tensor_logical_shape(arr.shape, layout)
+        name = tensor_dtype(arr.dtype, dtype)
+        tensor_args(shape, layout, name)
+        return cls(DeviceBuffer.from_host(np.ascontiguousarray(arr)), shape, name, layout)
+
+    def to_host(self):
+        """-> the array in memory order; bfloat16 comes back as uint16 bit patterns."""
+        return self.buf.to_host(tensor_mem_shape(self.shape, self.layout), _TENSOR_NP[self.dtype])
+
+    @classmethod
+    def from_external(cls, obj, layout=None, dtype=None, stream=None, copy=True):
+        """A tensor another framework holds in device memory (`obj.__cuda_array_interface__`, see external_args), in the
+        memory order of `layout` ('chw', also the default: (C, H, W) / (N, C, H, W); 'hwc': (H, W, C) / (N, H, W, C)), of
+        float32 or float16 -- or bfloat16, handed over as a 2-byte integer array with dtype='bfloat16'.  A contiguous source
+        is one device copy -- or, with copy=False, adopted: the DeviceTensor then IS the producer's memory, its buffer view
+        keeps `obj` alive and must not be written by the producer afterwards.  A strided source (a channel slice, a crop)
+        goes through the import kernel; copy=False is then a ValueError.  The library's stream first waits for the
+        producer's (`stream`: see external_args).  Asynchronous, like DeviceImage.from_external."""
+        layout = 'chw' if layout is None else layout
+        ext = external_args(obj, dtype, stream)
+        shape = tensor_logical_shape(ext.shape, layout)
+        name = tensor_dtype(ext.dtype)
+        n, c, h, w, batched = tensor_args(shape, layout, name)
+        contiguous = _contiguous(ext.shape, ext.strides)
+        if not copy and not contiguous:
+            raise ValueError("Error taking an external tensor: copy=False needs a C-contiguous array in the layout '{}'".format(layout))
+        _check_device_memory(ext)
+        _wait_for(ext.stream)
+        nbytes = n * c * h * w * ext.itemsize
+        if contiguous and not copy:
+            return cls(_BufferView(ext.ptr, nbytes, owner=obj), shape, name, layout)
+        if contiguous:
+            buf = DeviceBuffer(nbytes)
+            nat.check(_lib().ofl_copy_dev(buf.ptr, ext.ptr, nbytes, None))
+        else:
+            st = ext.strides if batched else (0,) + ext.strides
+            st = st if layout == 'chw' else (st[0], st[3], st[1], st[2])        # -> (item, channel, row, column)
+            buf = tensor_import_launch(ext.ptr, name, st, layout, n, c, h, w)
+        return cls(buf, shape, name, layout)
+
+    def export(self, layout=None, copy=True):
+        """-> DeviceArray (`__cuda_array_interface__`; torch.as_tensor(a, device='cuda')) in the memory order of `layout`
+        (None: the tensor's own).  bfloat16 goes out as int16 ('<i2'), like DeviceFlow.export.  The tensor's own layout is a
+        device copy or, with copy=False, a view of its memory that the consumer must not write; the other layout goes
+        through the permute kernel."""
+        layout = self.layout if layout is None else layout
+        if layout not in ('chw', 'hwc'):
+            raise ValueError("Error exporting tensor: layout must be 'chw' or 'hwc', got {!r}".format(layout))
+        out_shape = tensor_mem_shape(self.shape, layout)
+        if layout == self.layout:
+            return export_buffer(self.buf, out_shape, _TENSOR_TYPESTR[self.dtype], copy, self)
+        if not copy:
+            raise ValueError("Error exporting tensor: copy=False hands out the tensor's own '{}' memory; '{}' is a conversion"
+                             .format(self.layout, layout))
+        buf = tensor_permute_launch(self.buf, self.dtype, self.n, self.channels, self.h, self.w, layout == 'hwc')
+        return DeviceArray(buf, out_shape, _TENSOR_TYPESTR[self.dtype])
 
 
 # ------------------------------------------------------------------------------ the launch wrappers that hand back a DeviceImage
@@ -532,6 +617,28 @@ class DeviceFlow:
         scatter_linear(self.vecs, +1, pm, image.buf, C, vmask, h, w, None, out.buf, valid, 0,
                        cert=self.mesh_cert(+1) if pm is None else None, drops_points=pm is not None)
         return out, valid
+
+    def apply_tensor(self, tensor, target_mask=None, quant=nat.QUANT_OPENCV):
+        """Warp an HBM-resident DeviceTensor -- (C, H, W) or (N, C, H, W), either layout, float32 / float16 / bfloat16 -- and
+        propagate validity: every channel is Flow.apply of that plane (flow_class.py:604-695, without padding) from ONE set
+        of taps per pixel, one launch of K12; 16-bit tensors are blended in float32 and rounded once.  This one field warps
+        every item of a batched tensor.  -> (DeviceTensor, valid-area DeviceBuffer [H][W]).  `target_mask`: uint8
+        DeviceBuffer [H][W] or None (all valid).  Reference 't' only: 's'-reference (scatter) warps of tensors are not
+        supported."""
+        if self.ref != 't':
+            raise ValueError("apply_tensor warps with 't'-reference fields only: 's'-reference (scatter) warps of tensors are "
+                             "not supported")
+        n, c, h, w, _ = tensor_args(tensor.shape, tensor.layout, tensor.dtype, self.shape)
+        if self.is_zero(thresholded=True, masked=False):        # identity short cut, utils.py:215-216
+            valid = DeviceBuffer(self.n_px)
+            if target_mask is None:
+                nat.check(_lib().ofl_copy_dev(valid.ptr, self.mask.ptr, self.n_px, None))
+            else:
+                _mask_and(self.mask, target_mask, valid, self.n_px)
+            return tensor, valid
+        dst, valid = gather_tensor(tensor.buf, tensor.dtype, tensor.layout, n, c, h, w, self.vecs, True, -1, smask=target_mask,
+                                   smask_shared=True, fmask=self.mask, want_valid=True, quant=quant)
+        return DeviceTensor(dst, tensor.shape, tensor.dtype, tensor.layout), valid
 
     def apply_image_rows(self, image, rank, world, target_mask=None, consider_mask=True, quant=nat.QUANT_OPENCV,
                          gather=None, align=8):

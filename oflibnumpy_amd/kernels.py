@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize and K10 tracking.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking and K12 tensor warps.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -8,8 +8,8 @@ import numpy as np
 
 from . import _native as nat
 from .memory import DeviceBuffer, _BufferView, _lib, _ptr, _size_query
-from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, percentile_ranks, resize_scales, resized_shape, mask_bytes,
-                   valid_mask_array)
+from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _TENSOR_EL, _TENSOR_LAYOUT, percentile_ranks, resize_scales,
+                   resized_shape, mask_bytes, valid_mask_array)
 
 
 # ------------------------------------------------------------------------------ K1: gather
@@ -263,3 +263,37 @@ def track_query_epilogue(query, vals, found, n, shape, stats, valid, step, statu
     nat.check(_lib().ofl_track_query_epilogue_dev(query.ptr, vals.ptr, found.ptr, n, shape[0], shape[1], _ptr(stats), _ptr(valid),
                                                   step, _ptr(out_rc), _ptr(out_int), _ptr(next_query), _ptr(status),
                                                   _ptr(lost_at), stream))
+
+
+# ------------------------------------------------------------------------------ K12: many-channel float tensors
+def _tensor_bytes(dtype):
+    return 4 if dtype == 'float32' else 2
+
+
+def gather_tensor(src, dtype, layout, n, c, h, w, flow, flow_shared, sign, smask=None, smask_shared=False, fmask=None,
+                  want_valid=False, quant=nat.QUANT_OPENCV, stream=None):
+    """K12 (ofl_gather_tensor_dev) on `n` items of `c` channels in `layout` ('chw' / 'hwc'); asynchronous.  -> (dst buffer,
+    valid buffer or None): valid is [n][H][W], or ONE [H][W] mask when the field and the target mask are shared."""
+    dst = DeviceBuffer(n * c * h * w * _tensor_bytes(dtype))
+    valid = None
+    if want_valid:
+        valid = DeviceBuffer(h * w * (1 if flow_shared and (smask is None or smask_shared) else n))
+    nat.check(_lib().ofl_gather_tensor_dev(src.ptr, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, h, w, flow.ptr,
+                                           1 if flow_shared else 0, sign, _ptr(smask), 1 if smask_shared else 0, _ptr(fmask),
+                                           dst.ptr, _ptr(valid), quant, stream))
+    return dst, valid
+
+
+def tensor_import_launch(src_ptr, dtype, strides, layout, n, c, h, w, stream=None):
+    """ofl_tensor_import_dev: a strided foreign view, element strides (item, channel, row, column) -> a contiguous buffer."""
+    dst = DeviceBuffer(n * c * h * w * _tensor_bytes(dtype))
+    nat.check(_lib().ofl_tensor_import_dev(src_ptr, _tensor_bytes(dtype), strides[0], strides[1], strides[2], strides[3],
+                                           _TENSOR_LAYOUT[layout], n, c, h, w, dst.ptr, stream))
+    return dst
+
+
+def tensor_permute_launch(src, dtype, n, c, h, w, to_hwc, stream=None):
+    """ofl_tensor_permute_dev: contiguous 'chw' -> 'hwc' (to_hwc) or back, into a fresh buffer."""
+    dst = DeviceBuffer(n * c * h * w * _tensor_bytes(dtype))
+    nat.check(_lib().ofl_tensor_permute_dev(src.ptr, dst.ptr, _tensor_bytes(dtype), n, c, h, w, 1 if to_hwc else 0, stream))
+    return dst
