@@ -666,6 +666,42 @@ int ofl_tensor_import_dev(const void *src, int elem_bytes, int64_t s_item, int64
                           int layout, int N, int C, int H, int W, void *dst, void *stream);
 int ofl_tensor_permute_dev(const void *src, void *dst, int elem_bytes, int N, int C, int H, int W, int to_nhwc, void *stream);
 
+/* ------------------------------------------------------------------ K13: forward-backward consistency of two fields
+ * The check between "two fields come out of a network" and "warp with them": sample the backward field b where the
+ * forward field f points, add the two vectors, and call the pixel inconsistent (occluded) when the sum is larger than a
+ * bound that grows with the two magnitudes.  f and b have one shape and ONE reference; sign = +1 for 's', -1 for 't' --
+ * the pairing of ofl_compose3_dev with fb = f, fa = b.  Per pixel (x, y), every operation float32 and rounded once:
+ *     tap        = the bilinear tap of (x, y) + sign * f[y][x]          (map_coord / make_tap, `quant` as in K1 / K2)
+ *     bu, bv     = b's four taps blended (0 outside the frame);  am = bm's four taps blended as 0.0f / 1.0f
+ *     covered    = fm & (am == 1.0f)                                    == ofl_compose3_dev's mout, bit for bit
+ *     ru, rv     = f.u + bu, f.v + bv                                   == ofl_compose3_dev's out, bit for bit
+ *     r2         = ru*ru + rv*rv
+ *     s2         = (f.u*f.u + f.v*f.v) + (bu*bu + bv*bv)
+ *     lim        = alpha*s2 + beta
+ *     consistent = covered & (r2 <= lim)
+ *     residual   = covered ? sqrtf(r2) : 0.0f                           (the correctly rounded square root)
+ * This is not a function of the reference and the formula is its definition: there is NO zero-flow short cut in either
+ * `quant` mode (under OFL_QUANT_EXACT a sub-threshold f therefore differs from f + f.apply(b); it equals K2 always).
+ * batch pairs are stored back to back ([batch][H][W][..]), batch in [1, 65535], H and W in [1, 32766].  consistent is
+ * required; covered and residual may be NULL (not written).  counts (device, uint32[batch][2] = {covered, consistent}
+ * pixels per pair, or NULL) is ADDED to: the caller zeroes it; each workgroup reduces its pixels and issues at most one
+ * atomic add per counter (integer adds: the result does not depend on their order), and with counts == NULL the launch
+ * issues no atomics at all.  Outputs must not alias inputs.  f and b must be 8-byte aligned.
+ * Bytes per pixel: reads 8 (f, streamed) + 8 (b, gathered) + 2 (masks); writes 1 (consistent) + 1 (covered) + 4 (residual)
+ * -- 2 where ofl_compose3_dev writes 9, or 6 with the residual.
+ * A bad argument -- a NULL f / fm / b / bm / consistent, sizes or batch out of range, sign not +-1, alpha or beta negative
+ * or not finite, an unknown quant -- returns OFL_E_INVALID with a message before any launch.  The _dev entry is
+ * asynchronous; the host entry uploads, launches once, downloads (counts_host: host uint32[batch][2] or NULL) and
+ * synchronises.
+ */
+int ofl_consistency_dev(const float *f, const uint8_t *fm, const float *b, const uint8_t *bm, int sign,
+                        int H, int W, int batch, float alpha, float beta,
+                        uint8_t *consistent, uint8_t *covered, float *residual, uint32_t *counts,
+                        int quant, void *stream);
+int ofl_consistency(const float *f, const uint8_t *fm, const float *b, const uint8_t *bm, int sign,
+                    int H, int W, int batch, float alpha, float beta,
+                    uint8_t *consistent, uint8_t *covered, float *residual, uint32_t *counts_host, int quant);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

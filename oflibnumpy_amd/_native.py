@@ -138,6 +138,8 @@ SIGNATURES = {
     "ofl_gather_tensor_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _ci, _vp]),
     "ofl_tensor_import_dev": (_ci, [_vp, _ci, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
     "ofl_tensor_permute_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "ofl_consistency_dev": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp, _ci, _vp]),
+    "ofl_consistency": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp, _ci]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

@@ -222,6 +222,28 @@ def resized_shape(h, w, fy, fx):
     return ho, wo
 
 
+# -- forward-backward consistency (K13)
+CONSISTENCY_ALPHA, CONSISTENCY_BETA = 0.01, 0.5        # the usual constants of the check; the caller's to set
+
+
+def consistency_args(alpha=None, beta=None):
+    """Validation of the bound of the forward-backward check, |f + b(x + f)|^2 <= alpha * (|f|^2 + |b|^2) + beta, on the
+    host before any device work -> (alpha, beta) as float32, what the kernel computes with.  None gives the defaults 0.01
+    and 0.5; a bool or a non-number is a TypeError, a negative or non-finite value (as given, or once rounded to float32)
+    a ValueError."""
+    out = []
+    for name, value, default in (("alpha", alpha, CONSISTENCY_ALPHA), ("beta", beta, CONSISTENCY_BETA)):
+        value = default if value is None else value
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise TypeError("Error checking flow consistency: {} must be a number, got {}".format(name, type(value).__name__))
+        with np.errstate(over='ignore'):
+            v32 = np.float32(float(value)) if abs(value) < 1e300 else np.float32(np.inf if value > 0 else -np.inf)
+        if value != value or value < 0 or not np.isfinite(v32):
+            raise ValueError("Error checking flow consistency: {} must be finite and not negative, got {}".format(name, value))
+        out.append(v32)
+    return out[0], out[1]
+
+
 # -- many-channel float tensors (K12)
 def tensor_dtype(array_dtype, dtype=None):
     """The element type of a tensor -> 'float32', 'float16' or 'bfloat16'.  `array_dtype`: the dtype of the array that holds

@@ -123,6 +123,22 @@ class DeviceFlowBatch:
             dev.compose3_launch(fa, fb, sign, out, words, batch=self.n, quant=quant)
         return out, words.to_host((self.n, 8), np.uint32), (fa, fb)
 
+    def consistency(self, backward, alpha=None, beta=None, return_residual=False, return_counts=False, quant=nat.QUANT_OPENCV):
+        """self[i].consistency(backward[i], ...) for every i in ONE launch of K13 (DeviceFlow.consistency): `backward` a batch
+        of the same length, shape and reference.  -> (consistent, covered) as uint8 DeviceBuffers [n][H][W]; return_residual
+        appends the float32 DeviceBuffer [n][H][W], return_counts an (n, 2) uint32 array of (covered, consistent) pixels per
+        pair -- the only option that synchronises.  A packed batch is read through its byte masks (`.mask` unpacks on
+        demand)."""
+        alpha, beta = dev.consistency_args(alpha, beta)
+        if not isinstance(backward, DeviceFlowBatch):
+            raise TypeError("Error checking flow consistency: backward needs to be a DeviceFlowBatch, got {}".format(type(backward).__name__))
+        if (self.n, self.shape, self.ref) != (backward.n, backward.shape, backward.ref):
+            raise ValueError("batches need the same length, shape and reference")
+        consistent, covered, residual, counts = dev.consistency_launch(
+            self.vecs, self.mask, backward.vecs, backward.mask, 1 if self.ref == 's' else -1, self.shape, alpha, beta,
+            batch=self.n, want_residual=return_residual, want_counts=return_counts, quant=quant)
+        res = (consistent, covered) + ((residual,) if return_residual else ())
+        return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
 
     def apply_images(self, images, dtype, channels, shared=False, target_masks=None, shared_masks=False, quant=nat.QUANT_OPENCV):
         """self[i].apply(image_i, target_mask_i, return_valid_area=True) for every i in ONE launch of the gather kernel

@@ -30,12 +30,13 @@ from .memory import (_lib, _ptr, _size_query, _Pool, _PinnedPool, empty_cache, D
                      PinnedArray, sync)
 from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rules, mask_bytes, _points_array, visualise_args,
                    percentile_ranks, matrix_args, validate_transforms, valid_mask_array, scale_operand, crop_args,
-                   resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape)
+                   resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
+                   consistency_args)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
                       track_bilinear_launch, track_query_points, track_query_epilogue, gather_tensor, tensor_import_launch,
-                      tensor_permute_launch)
+                      tensor_permute_launch, consistency_launch, consistency_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -563,6 +564,37 @@ class DeviceFlow:
         out = DeviceFlow.empty(self.shape, self.ref)
         compose3_launch(sampled, self, sign, out, quant=quant)
         return out
+
+    def consistency(self, backward, alpha=None, beta=None, return_residual=False, return_counts=False, quant=nat.QUANT_OPENCV):
+        """The forward-backward check of this (forward) field against `backward`, a DeviceFlow of the same shape and the SAME
+        reference, in ONE launch of K13 (include/ofl.h): the backward field is sampled where this one points -- at
+        x + self for 's', x - self for 't', the taps and blend of the compose kernel -- and per pixel
+            covered    = self.mask & [the interpolated backward mask == 1]      (the mask of self + sampled backward)
+            consistent = covered & (|self + sampled|^2 <= alpha * (|self|^2 + |sampled|^2) + beta)
+            residual   = |self + sampled| where covered, else 0
+        in float32 with one rounding per operation.  alpha, beta: None for the usual 0.01 and 0.5 (args.consistency_args).
+        This is not a function of the reference and the formula is its definition: there is NO zero-flow short cut in either
+        `quant` mode, so under QUANT_EXACT a field below the 1e-3 threshold differs from self + self.apply(backward), while
+        covered and the residual's vector equal the fused compose kernel's result always, bit for bit.
+        -> (consistent, covered) as uint8 DeviceBuffers [H][W]; return_residual appends the float32 DeviceBuffer [H][W],
+        return_counts appends (n_covered, n_consistent) as Python ints -- the only option that synchronises; everything else is
+        asynchronous.  The inputs are not modified."""
+        alpha, beta = consistency_args(alpha, beta)
+        if not isinstance(backward, DeviceFlow):
+            raise TypeError("Error checking flow consistency: backward needs to be a DeviceFlow, got {}".format(type(backward).__name__))
+        if backward.shape != self.shape:
+            raise ValueError("Error checking flow consistency: the fields need the same shape, got {} and {}".format(self.shape, backward.shape))
+        if backward.ref != self.ref:
+            raise ValueError("Error checking flow consistency: the fields need the same reference, got '{}' and '{}'"
+                             .format(self.ref, backward.ref))
+        consistent, covered, residual, counts = consistency_launch(
+            self.vecs, self.mask, backward.vecs, backward.mask, 1 if self.ref == 's' else -1, self.shape, alpha, beta,
+            want_residual=return_residual, want_counts=return_counts, quant=quant)
+        res = (consistent, covered) + ((residual,) if return_residual else ())
+        if return_counts:
+            n = counts.to_host((2,), np.uint32)
+            res += ((int(n[0]), int(n[1])),)
+        return res
 
     # -- warping
     def apply(self, target, consider_mask=True, quant=nat.QUANT_OPENCV, target_mask=None):

@@ -428,6 +428,29 @@ class Flow(object):
         dof, method, masked, _ = matrix_fit.matrix_args(dof, method, masked)
         return self.to_device().matrix(dof, method, masked)
 
+    def consistency(self, backward: FlowAlias, alpha: float = None, beta: float = None,
+                    return_residual: bool = None) -> Tuple[np.ndarray, ...]:
+        """Forward-backward check of this (forward) flow against `backward`, a flow of the same shape and reference:
+        the backward flow is sampled where this one points, and a pixel is `covered` where that sample and this vector
+        are valid, `consistent` where it is covered and |self + sampled|^2 <= alpha * (|self|^2 + |sampled|^2) + beta
+        (defaults 0.01 and 0.5).  -> (consistent, covered) as bool (H, W) arrays, plus the float32 (H, W) residual
+        |self + sampled| (0 where not covered) with `return_residual`.  Not a function of the reference; the definition,
+        which takes no zero-flow short cut, is DeviceFlow.consistency's.  One upload, one launch, one download."""
+        alpha, beta = dev.consistency_args(alpha, beta)
+        return_residual = False if return_residual is None else return_residual
+        if not isinstance(return_residual, bool):
+            raise TypeError("Error checking flow consistency: Return_residual needs to be a boolean")
+        if not isinstance(backward, Flow):
+            raise TypeError("Error checking flow consistency: Backward needs to be of type 'Flow'")
+        if self.shape != backward.shape:
+            raise ValueError("Error checking flow consistency: Flow fields need to have the same shape, got {} and {}"
+                             .format(self.shape, backward.shape))
+        if self.ref != backward.ref:
+            raise ValueError("Error checking flow consistency: Flow fields need to have the same reference, got '{}' and '{}'"
+                             .format(self.ref, backward.ref))
+        return dev.consistency_host(self._vecs, self._mask, backward._vecs, backward._mask, 1 if self._ref == 's' else -1,
+                                    alpha, beta, return_residual)
+
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
         """flow_1 (+) flow_2 = flow_3: mode k returns flow_k from the other two (`self` comes first in
         that formula among the two given).  Reference flow_class.py:1247-1424."""

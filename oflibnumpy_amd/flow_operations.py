@@ -10,7 +10,7 @@ from .flow_class import Flow
 
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
-           'get_flow_matrix', 'visualise_flow']
+           'get_flow_matrix', 'visualise_flow', 'flow_consistency']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -60,3 +60,8 @@ def get_flow_matrix(flow: nd, ref: str, dof: int = None, method: str = None) -> 
 def visualise_flow(flow: nd, mode: str, range_max: float = None) -> nd:
     """uint8 (H, W, 3) 'rgb' / 'bgr' / 'hsv' image of a flow array (reference flow_operations.py:274-284)."""
     return Flow(flow).visualise(mode=mode, range_max=range_max)
+
+
+def flow_consistency(forward: nd, backward: nd, ref: str, alpha: float = None, beta: float = None) -> tuple:
+    """(consistent, covered) bool (H, W) masks of the forward-backward check of two flow arrays (Flow.consistency)."""
+    return Flow(forward, ref).consistency(Flow(backward, ref), alpha=alpha, beta=beta)

@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking and K12 tensor warps.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps and K13 consistency.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -82,6 +82,36 @@ def compose3_bits_launch(fa_vecs, fa_bits, fb_vecs, fb_bits, sign, shape, out_ve
     sp = None if stats_buf is None else stats_buf.ptr + stats_offset
     nat.check(_lib().ofl_compose3_bits_dev(fa_vecs.ptr, fa_bits.ptr, fb_vecs.ptr, fb_bits.ptr, sign, shape[0], shape[1], batch,
                                            out_vecs.ptr, out_bits.ptr, sp, stream))
+
+
+# ------------------------------------------------------------------------------ K13: forward-backward consistency
+def consistency_launch(f_vecs, f_mask, b_vecs, b_mask, sign, shape, alpha, beta, batch=1, want_residual=False,
+                       want_counts=False, quant=nat.QUANT_OPENCV, stream=None):
+    """K13 (ofl_consistency_dev) on `batch` pairs stored back to back; asynchronous.  alpha, beta: float32, from
+    args.consistency_args.  -> (consistent, covered, residual or None, counts or None): uint8 [batch][H][W] twice, float32
+    [batch][H][W], and the zeroed-then-added uint32 [batch][2] = {covered, consistent} words, all still in HBM."""
+    n = batch * shape[0] * shape[1]
+    consistent, covered = DeviceBuffer(n), DeviceBuffer(n)
+    residual = DeviceBuffer(n * 4) if want_residual else None
+    counts = DeviceBuffer.zeros(batch * 8, stream) if want_counts else None
+    nat.check(_lib().ofl_consistency_dev(f_vecs.ptr, f_mask.ptr, b_vecs.ptr, b_mask.ptr, sign, shape[0], shape[1], batch,
+                                         alpha, beta, consistent.ptr, covered.ptr, _ptr(residual), _ptr(counts), quant, stream))
+    return consistent, covered, residual, counts
+
+
+def consistency_host(f_vecs, f_mask, b_vecs, b_mask, sign, alpha, beta, want_residual=False, quant=nat.QUANT_OPENCV):
+    """K13 for host arrays through ofl_consistency (upload, one launch, download) -> (consistent, covered[, residual]):
+    bool (H, W) twice and float32 (H, W)."""
+    f_vecs, b_vecs = np.ascontiguousarray(f_vecs, np.float32), np.ascontiguousarray(b_vecs, np.float32)
+    fm, bm = mask_bytes(f_mask), mask_bytes(b_mask)
+    h, w = f_vecs.shape[:2]
+    consistent, covered = np.empty((h, w), np.uint8), np.empty((h, w), np.uint8)
+    residual = np.empty((h, w), np.float32) if want_residual else None
+    nat.check(_lib().ofl_consistency(f_vecs.ctypes.data, fm.ctypes.data, b_vecs.ctypes.data, bm.ctypes.data, sign, h, w, 1,
+                                     alpha, beta, consistent.ctypes.data, covered.ctypes.data,
+                                     None if residual is None else residual.ctypes.data, None, quant))
+    res = (consistent.view(np.bool_), covered.view(np.bool_))
+    return res + (residual,) if want_residual else res
 
 
 # ------------------------------------------------------------------------------ K7: visualise, K8: matrix fit
