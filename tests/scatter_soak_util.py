@@ -1,6 +1,11 @@
 """One random case of the scattered -> grid path against SciPy (tools/soak_scatter.py runs them by the thousand; the seeds that
-once failed are replayed by tests/test_gpu_scatter_exact.py::test_soak_regressions)."""
+once failed are replayed by tests/test_gpu_scatter_exact.py::test_soak_regressions).  one_case and one_query_case return
+(nodes compared, mismatching nodes, message, inadmissible nodes, nodes not judged, nodes inside the hull): outside SciPy's non-unique simplices a node
+must equal SciPy's, inside them it must equal SciPy's or be one of the admissible alternatives (scatter_admissible); the
+inadmissible ones count as mismatches, the ones whose alternatives could not be enumerated are reported and not compared."""
 import numpy as np
+
+import scatter_admissible as sa
 
 
 def make_case(seed, hmax, wmax):
@@ -80,17 +85,18 @@ def one_case(dev, O, nonunique_nodes, hull_band, seed, hmax, wmax):
         try:
             O.scatter_griddata(sign * vecs, np.concatenate([vals, vm[..., None].astype(np.float32)], -1), pm)
         except Exception:
-            return 0, 0, None
-        return 0, 1, "refused by the library, accepted by SciPy: " + str(e)[:120]
+            return 0, 0, None, 0, 0, 0
+        return 0, 1, "refused by the library, accepted by SciPy: " + str(e)[:120], 0, 0, 0
     got, gv = out.to_host((h, w, C), np.float32), valid.to_host((h, w), np.uint8).astype(bool)
     try:
         want = O.scatter_griddata(sign * vecs, np.concatenate([vals, vm[..., None].astype(np.float32)], -1), pm)
     except Exception as e:
-        return 0, 1, "accepted by the library, refused by SciPy: " + str(e)[:120]
+        return 0, 1, "accepted by the library, refused by SciPy: " + str(e)[:120], 0, 0, 0
     keep = np.ones((h, w), bool) if pm is None else pm
     pts = np.stack([(xx + sign * vecs[..., 0].astype(np.float64)).ravel(), (yy + sign * vecs[..., 1].astype(np.float64)).ravel()], 1)[keep.ravel()]
     # (Qhull's own roundoff grows with the coordinates: what counts as "the fourth site lies on the circle" scales with them)
-    amb, inside = nonunique_nodes(pts, (h, w), tol=max(1e-9, 2.5e-11 * float(np.abs(pts).max())))
+    tol = max(1e-9, 2.5e-11 * float(np.abs(pts).max()))
+    amb, inside = nonunique_nodes(pts, (h, w), tol=tol)
     try:
         band = hull_band(pts, (h, w))
     except Exception:
@@ -98,12 +104,19 @@ def one_case(dev, O, nonunique_nodes, hull_band, seed, hmax, wmax):
     sel = ~amb & ~band
     bad_v = (gv != (want[..., -1] == 1)) & sel
     bad = ~np.isclose(got, want[..., :C], rtol=1e-4, atol=2e-5).all(-1) & sel
-    n_bad = int(bad_v.sum() + bad.sum())
+    rows = np.concatenate([vals, vm[..., None].astype(np.float32)], -1).reshape(h * w, C + 1)[keep.ravel()]
+    equal, status, counts = sa.equal_or_admissible(pts, rows, (h, w), got, want[..., :C], amb, gv, want[..., -1] == 1, sa.rule_eq1, tol=tol,
+                                                   rtol=1e-4, atol=2e-5)
+    # (neither equal nor admissible, as assert_equal_or_admissible counts them: a differing node outside the hull is one too)
+    inadm = amb & ~band & ~equal & ((status == sa.INADMISSIBLE) | (status == sa.OUTSIDE))
+    unjudged = amb & ~band & (status == sa.NOT_JUDGED)
+    n_bad = int(bad_v.sum() + bad.sum() + inadm.sum())
     msg = None
     if n_bad:
-        msg = "kind {} {}x{} sign {} mask {}: {} validity, {} value nodes, first {}".format(
-            kind, h, w, sign, pm is not None, int(bad_v.sum()), int(bad.sum()), np.argwhere(bad_v | bad)[:3].tolist())
-    return int(sel.sum()), n_bad, msg
+        msg = "kind {} {}x{} sign {} mask {}: {} validity, {} value nodes, {} inadmissible of {} non-unique, first {}".format(
+            kind, h, w, sign, pm is not None, int(bad_v.sum()), int(bad.sum()), int(inadm.sum()), int((amb & ~band).sum()),
+            np.argwhere(bad_v | bad | inadm)[:3].tolist())
+    return int((~band).sum() - unjudged.sum()), n_bad, msg, int(inadm.sum()), int(unjudged.sum()), counts['inside']
 
 
 def one_query_case(dev, O, nonunique_nodes, hull_band, seed, hmax, wmax):
@@ -124,17 +137,18 @@ def one_query_case(dev, O, nonunique_nodes, hull_band, seed, hmax, wmax):
         try:
             O._mode2_t_resample(O.OFlow(f1, 't', m1), O.OFlow(f3, 't'))
         except Exception:
-            return 0, 0, None
-        return 0, 1, "refused by the library, accepted by SciPy: " + str(e)[:120]
+            return 0, 0, None, 0, 0, 0
+        return 0, 1, "refused by the library, accepted by SciPy: " + str(e)[:120], 0, 0, 0
     try:
         want = O._mode2_t_resample(O.OFlow(f1, 't', m1), O.OFlow(f3, 't'))
     except Exception as e:
-        return 0, 1, "accepted by the library, refused by SciPy: " + str(e)[:120]
+        return 0, 1, "accepted by the library, refused by SciPy: " + str(e)[:120], 0, 0, 0
     # the points and the positions as the reference builds them: float32 arrays (flow_class.py:1398-1406)
     c1 = np.copy(-f1); c1[:, :, 0] += np.arange(w); c1[:, :, 1] += np.arange(h)[:, None]
     c3 = np.copy(-f3); c3[:, :, 0] += np.arange(w); c3[:, :, 1] += np.arange(h)[:, None]
     pts, q = c1.reshape(-1, 2).astype(np.float64), c3.reshape(-1, 2).astype(np.float64)
-    amb, inside = nonunique_nodes(pts, (h, w), queries=q, tol=max(1e-9, 2.5e-11 * float(np.abs(pts).max())))
+    tol = max(1e-9, 2.5e-11 * float(np.abs(pts).max()))
+    amb, inside = nonunique_nodes(pts, (h, w), queries=q, tol=tol)
     try:
         band = hull_band(pts, (h, w), queries=q)
     except Exception:
@@ -142,12 +156,17 @@ def one_query_case(dev, O, nonunique_nodes, hull_band, seed, hmax, wmax):
     sel = ~amb & ~band
     bad = ~np.isclose(gv, want.vecs, rtol=1e-4, atol=2e-5).all(-1) & sel
     bad_m = (gm != want.mask) & sel
-    n_bad = int(bad.sum() + bad_m.sum())
+    rows = np.concatenate([f1, np.asarray(m1, np.float32)[..., None]], -1).reshape(h * w, 3)
+    equal, status, counts = sa.equal_or_admissible(pts, rows, (h, w), gv, want.vecs, amb, gm, want.mask, sa.rule_gt099, q, tol=tol, rtol=1e-4,
+                                                   atol=2e-5)
+    inadm = amb & ~band & ~equal & ((status == sa.INADMISSIBLE) | (status == sa.OUTSIDE))
+    unjudged = amb & ~band & (status == sa.NOT_JUDGED)
+    n_bad = int(bad.sum() + bad_m.sum() + inadm.sum())
     msg = None
     if n_bad:
-        msg = "query kind {} {}x{}: {} mask, {} value positions, first {}".format(kind, h, w, int(bad_m.sum()), int(bad.sum()),
-                                                                                   np.argwhere(bad | bad_m)[:3].tolist())
-    return int(sel.sum()), n_bad, msg
+        msg = "query kind {} {}x{}: {} mask, {} value positions, {} inadmissible of {} non-unique, first {}".format(
+            kind, h, w, int(bad_m.sum()), int(bad.sum()), int(inadm.sum()), int((amb & ~band).sum()), np.argwhere(bad | bad_m | inadm)[:3].tolist())
+    return int((~band).sum() - unjudged.sum()), n_bad, msg, int(inadm.sum()), int(unjudged.sum()), counts['inside']
 
 
 def one_track_case(of, O, seed, hmax, wmax):

@@ -48,3 +48,57 @@ def hull_band(points, shape, queries=None, width=1e-5):
     q = np.stack([xx.ravel(), yy.ravel()], 1).astype(np.float64) if queries is None else np.asarray(queries, np.float64)
     d = (q @ hull.equations[:, :2].T + hull.equations[:, 2]).max(1)          # signed distance to the nearest facet, < 0 inside
     return (np.abs(d) < width).reshape(shape)
+
+
+def reference_case(g, tag):
+    """What SciPy received and what the reference returned for one image- or flow-valued case of the two fixture files
+    (tests/golden/make_golden.py), as scatter_admissible wants it: dict(points [N][2], values [N][K], shape, out, out_valid,
+    rule, levels, queries).  `tag` of ref_delaunay_cases.npz: '<name>/apply' or '<name>/invert'."""
+    import scatter_admissible as sa
+    parts = tag.split('/')
+    op, levels, queries, rule = parts[0], False, None, sa.rule_eq1
+    if tag + '/in_vecs' not in g.files:                                   # ref_delaunay_cases.npz
+        name, op = parts
+        vecs, mask = g[name + '/in_vecs'], g[name + '/in_mask']
+        if op == 'apply':
+            rows, out, out_valid = g[name + '/img'], g[name + '/apply'], g[name + '/apply_valid']
+        else:
+            rows, out, out_valid = -vecs, g[name + '/invert_vecs'], g[name + '/invert_mask']
+        pts, keep, vm = warped_points(vecs), mask, mask
+    else:
+        vecs, mask = g[tag + '/in_vecs'], g[tag + '/in_mask']
+        ref = str(g[tag + '/in_ref'])
+        sign = 1 if ref == 's' else -1
+        pts, keep, vm = warped_points(vecs, None, sign), mask, mask
+        if op in ('apply_img', 'apply_img_nomask', 'disc_apply'):
+            rows = g['disc/' + parts[1] + '/img'] if op == 'disc_apply' else g['img_f32']
+            out, out_valid = g[tag + '/out'], g[tag + '/out_valid']
+            if op == 'apply_img_nomask':
+                keep = np.ones_like(mask)
+        elif op.startswith(('valid_', 'k7', 'disc_valid')):               # flow_class.py:1113-1195: the mask alone is warped
+            nomask = parts[-1].endswith('nomask') or op.endswith('nomask')
+            rows, out, out_valid = np.zeros(mask.shape + (0,)), None, g[tag + '/out']
+            if nomask:
+                keep = np.ones_like(mask)
+        elif op == 'apply_u8':
+            rows, out, out_valid, rule, levels = g['img_u8'], g[tag + '/out'], None, None, True
+        elif op in ('invert', 'disc_invert', 'switch_ref'):               # flow_class.py:697-753
+            rows, out, out_valid = (vecs if op == 'switch_ref' else -vecs), g[tag + '/out_vecs'], g[tag + '/out_mask']
+        elif op.startswith('combine2') and ref == 's':                    # self.apply(flow - self), flow_class.py:1390
+            rows, vm = g[tag + '/in2_vecs'] - vecs, mask & g[tag + '/in2_mask']
+            out, out_valid = g[tag + '/out_vecs'], g[tag + '/out_mask']
+        elif op.startswith('combine2'):                                   # flow - resampled f1, flow_class.py:1398-1410: float32 positions
+            h, w = vecs.shape[:2]
+            f3 = g[tag + '/in2_vecs']
+            assert g[tag + '/in2_mask'].all()
+            c1 = np.copy(-vecs); c1[:, :, 0] += np.arange(w); c1[:, :, 1] += np.arange(h)[:, None]
+            c3 = np.copy(-f3); c3[:, :, 0] += np.arange(w); c3[:, :, 1] += np.arange(h)[:, None]
+            pts, queries, keep = c1.reshape(-1, 2).astype(np.float64), c3.reshape(-1, 2).astype(np.float64), np.ones_like(mask)
+            rows, out, out_valid, rule = vecs, f3 - g[tag + '/out_vecs'], g[tag + '/out_mask'], sa.rule_gt099
+        else:
+            raise KeyError(tag)
+    k = keep.ravel()
+    values = rows.reshape(len(k), -1).astype(np.float64)
+    if rule is not None:
+        values = np.concatenate([values, vm.reshape(-1, 1).astype(np.float64)], 1)
+    return dict(points=pts[k], values=values[k], shape=vecs.shape[:2], out=out, out_valid=out_valid, rule=rule, levels=levels, queries=queries)

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from scatter_util import nonunique_nodes, warped_points, hull_band
+import scatter_admissible as sa
 
 pytestmark = pytest.mark.gpu
 
@@ -121,6 +122,24 @@ def scatter_ambiguity(op, sign, xs, shape):
         return nonunique_nodes(pts, shape, queries=q)[0], hull_band(pts, shape, q)
     pts = warped_points(v, None if m.all() else m, sign)
     return nonunique_nodes(pts, shape)[0], hull_band(pts, shape)
+
+
+def scatter_status(op, sign, xs, result, shape, only):
+    """scatter_admissible's verdict on the nodes `only` of one scatter stage's result, from the stage's OWN operand triples xs:
+    is the value there one of the alternatives SciPy's non-unique simplices allow (values and validity from one triangle)?
+    Returns (status, inside the hull)."""
+    v, _, m = xs[0]
+    if op == 'resample':            # value rows f1 | mask of every point, validity = interpolated mask > 0.99 (flow_class.py:1398-1410)
+        yy, xx = np.mgrid[:shape[0], :shape[1]].astype(np.float32)
+        pts = np.stack([(xx - v[..., 0]).ravel(), (yy - v[..., 1]).ravel()], 1).astype(np.float64)
+        q3 = xs[1][0]
+        q = np.stack([(xx - q3[..., 0]).ravel(), (yy - q3[..., 1]).ravel()], 1).astype(np.float64)
+        rows = np.concatenate([v, m[..., None]], -1).reshape(-1, 3)
+        return sa.admissible_nodes(pts, rows, shape, result[0], result[2], sa.rule_gt099, q, rtol=RTOL, atol=ATOL, only=only, with_inside=True)
+    tv, _, tm = xs[-1]              # switch_ref warps the flow itself, apply its second operand; the masks are and-ed (flow_class.py:643)
+    rows = np.concatenate([tv, (m & tm)[..., None]], -1).reshape(-1, 3)[m.ravel()]
+    return sa.admissible_nodes(warped_points(v, m, sign), rows, shape, result[0], result[2], sa.rule_eq1, rtol=RTOL, atol=ATOL, only=only,
+                               with_inside=True)
 
 
 def close(got, want):
@@ -239,14 +258,20 @@ def test_chain_stage_by_stage(gpu, oracle, case, kind, ref):
             reason = "1/32-px snap flips at {} nodes".format(int(flip.sum()))
         else:
             amb, band = ambs[name]
-            amb = amb | band
             src = dev[args[0]].copy()
             for kk in args[1:]:
                 src |= dev[kk]
-            ok = amb | scatter_reach(src, xs_w[0][0], sign, shape, 3)
+            ok = band | scatter_reach(src, xs_w[0][0], sign, shape, 3)
             if op == 'resample':
                 ok |= dev[args[1]]
-            reason = "{} non-unique or hull-border nodes".format(int(amb.sum()))
+            # a non-unique simplex explains a deviation only if the value IS one of its alternatives
+            ask = d & amb & ~ok
+            st, inside = scatter_status(op, sign, xs_g, got[name], shape, ask)
+            unjudged = st == sa.NOT_JUDGED                           # counted, bounded by 0.1 % of the nodes inside the hull
+            assert unjudged.sum() <= 1e-3 * inside.sum(), (name, op, int(unjudged.sum()), int(inside.sum()))
+            ok |= ask & ((st == sa.ADMISSIBLE) | unjudged)
+            reason = "{} non-unique, {} of them admissible, {} not judged; {} hull-border nodes".format(
+                int(amb.sum()), int((st == sa.ADMISSIBLE).sum()), int(unjudged.sum()), int(band.sum()))
         unexplained = d & ~ok
         if d.any():
             why.append("  stage '{}' ({}): {} nodes beyond tolerance ({}), first {}".format(

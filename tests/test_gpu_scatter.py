@@ -9,7 +9,8 @@ Bars: validity masks bit-exact; interpolated float32 values within 1e-4 relative
 practice ~1e-6 -- wherever SciPy's own Delaunay triangulation is unique (scatter_util.nonunique_nodes marks the
 simplices with a fourth site on their circumcircle: exact squares of translations / axis-aligned scalings and the
 ~13 % of cells of a similarity transform whose float32 rounding is identical at all four corners; Qhull's choice
-there is arbitrary).  Holes of the point mask, curved borders, folds and sheared cells are triangulated exactly
+there is arbitrary -- inside them a node must equal the reference's output or be one of the admissible alternatives,
+values and validity from one triangle: check_admissible / scatter_admissible.py).  Holes of the point mask, curved borders, folds and sheared cells are triangulated exactly
 like SciPy does (round 2: certified mesh path + Delaunay path, see test_gpu_scatter_exact.py).
 """
 import numpy as np
@@ -17,7 +18,8 @@ import pytest
 
 from test_oracle import (golden_tags, k7_flows, K7_VALID_TARGET_S, K7_VALID_SOURCE_T,
                          K7_VALID_TARGET_S_MASKED, K7_VALID_SOURCE_T_MASKED)
-from scatter_util import ambiguous_for
+from scatter_util import ambiguous_for, nonunique_nodes, reference_case, warped_points
+import scatter_admissible as sa
 
 pytestmark = pytest.mark.gpu
 
@@ -98,9 +100,30 @@ def case_ambiguity(golden, tag):
     return ambiguous_for(golden[tag + '/in_vecs'], keep, sign)
 
 
+def check_admissible(golden, tag, r, amb):
+    """Inside the non-unique simplices, where the comparisons of check_case stop: the product's output equals the
+    reference's or is one of the admissible alternatives (scatter_admissible), values and validity from one triangle."""
+    c = reference_case(golden, tag)
+    if c['queries'] is not None:            # mode 2 / 't': float32 points, scattered query positions
+        amb = nonunique_nodes(c['points'], c['shape'], c['queries'])[0]
+    if hasattr(r, 'vecs'):
+        got, gv = r.vecs, r.mask
+        if c['queries'] is not None:        # the stage that is interpolated: f3 - result
+            got = golden[tag + '/in2_vecs'] - r.vecs
+    elif isinstance(r, tuple):
+        got, gv = r
+    elif r.dtype == bool:
+        got, gv = None, r
+    else:
+        got, gv = r, None
+    return sa.assert_equal_or_admissible(tag, c['points'], c['values'], c['shape'], got, c['out'], amb, gv, c['out_valid'], c['rule'],
+                                         c['queries'], rtol=RTOL, atol=ATOL, levels=c['levels'])
+
+
 def check_case(of, golden, tag):
     r = run_product(of, golden, tag)
     amb = case_ambiguity(golden, tag)
+    check_admissible(golden, tag, r, amb)
     speckled = not golden[tag + '/in_mask'].all()      # the mask VALUES are interpolated: which triangle covers a node matters
     if isinstance(r, of.Flow):
         assert r.ref == str(golden[tag + '/out_ref']), tag
@@ -394,10 +417,13 @@ def test_discontinuous_fields_vs_reference(gpu, golden):
             w, v = f.apply(golden['disc/' + name + '/img'], return_valid_area=True)
             np.testing.assert_array_equal(v, golden[tag + '/out_valid'], err_msg=tag)
             np.testing.assert_allclose(w[~amb], golden[tag + '/out'][~amb], rtol=RTOL, atol=ATOL, err_msg=tag)
+            n = check_admissible(golden, tag, (w, v), amb)
+            assert n['judged'] >= amb.sum() > 1900 and n['not_judged'] == 0      # the lattice background: nearly every node is judged here
         elif op == 'disc_invert':
             r = f.invert()
             np.testing.assert_array_equal(r.mask, golden[tag + '/out_mask'], err_msg=tag)
             np.testing.assert_allclose(r.vecs[~amb], golden[tag + '/out_vecs'][~amb], rtol=RTOL, atol=1e-5, err_msg=tag)
+            check_admissible(golden, tag, r, amb)
         else:
             np.testing.assert_array_equal(f.valid_target(), golden[tag + '/out'], err_msg=tag)
 
@@ -702,6 +728,10 @@ def test_integer_targets_valid_area_s(gpu, oracle):
             np.testing.assert_array_equal(valid[~amb_kept], wvalid[~amb_kept], err_msg=str((dt, tmask is None)))
             d = np.abs(got.astype(int) - want.astype(int)).max(-1)[~amb_kept & wvalid]
             assert (d <= 1).all() and (d > 0).mean() < 1e-3, (dt, tmask is None)       # a value within 1e-6 of x.5 may round the other way
+            both = fm if tmask is None else fm & tmask
+            rows = np.concatenate([img, both[..., None]], -1).reshape(-1, 4)[fm.ravel()]
+            sa.assert_equal_or_admissible(str((dt, tmask is None)), warped_points(vecs, fm), rows, shape, got, want, amb_kept, valid, wvalid,
+                                          sa.rule_eq1_rounded, rtol=RTOL, atol=ATOL, levels=True)
         # the rounding rule really is looser than the float rule along the outline -- and the kernel follows it node for node
         w_int = o.apply(img, tm, return_valid_area=True)[1]
         w_flt = o.apply(img.astype(np.float32), tm, return_valid_area=True)[1]
@@ -713,6 +743,8 @@ def test_integer_targets_valid_area_s(gpu, oracle):
         inner = of.Flow(vecs, 's').valid_target() & ~amb_all
         d = np.abs(got.astype(int) - want.astype(int)).max(-1)
         assert (d[inner] <= 1).all() and (d[inner] > 0).mean() < 1e-3
+        sa.assert_equal_or_admissible(str(dt), warped_points(vecs), np.concatenate([img, tm[..., None]], -1).reshape(-1, 4), shape, got, want,
+                                      amb_all, valid, wvalid, sa.rule_eq1_rounded, rtol=RTOL, atol=ATOL, levels=True)
 
 
 def test_track_pts_t_positions_outside_the_image(gpu, oracle):

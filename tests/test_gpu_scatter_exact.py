@@ -6,8 +6,12 @@
 
 Expected values come from the oracle (which calls the same scipy.interpolate.griddata as the reference,
 src/oflibnumpy/utils.py:253) and from outputs of the real reference in tests/golden/.  Bars: validity masks
-bit-exact, values within 1e-4 relative wherever the Delaunay triangulation is unique (co-circular cells -- exact
-squares of translations / axis-aligned scalings -- are the only exemption: Qhull itself is arbitrary there).
+bit-exact, values within 1e-4 relative wherever the Delaunay triangulation is unique.  Where it is not (co-circular cells --
+exact squares of translations / axis-aligned scalings --, duplicated sites) Qhull's pick is arbitrary, and a node must equal the
+reference's output OR be one of the admissible alternatives: the interpolation on one of the triangles of the co-circular sites
+that hold the node, with one of the duplicates per corner, values and validity from the same one (tests/scatter_admissible.py,
+pinned on the CPU by tests/test_scatter_admissible_host.py).  No node may be inadmissible; at most 0.1 % of the nodes inside the
+hull may be left unjudged (more than 8 co-circular sites).
 """
 import ctypes
 import os
@@ -142,6 +146,9 @@ def test_certified_walk_matches_scipy(gpu, oracle):
         np.testing.assert_array_equal(gv[~amb], (want[..., -1] == 1)[~amb], err_msg=str(tr))
         bad = ~np.isclose(got, want[..., :C], rtol=RTOL, atol=ATOL).all(-1)
         assert not (bad & ~amb).any(), (tr, int((bad & ~amb).sum()))
+        n = sa.assert_equal_or_admissible(str(tr), warped_points(vecs, None, sign), rows_with_mask(vals, vm), shape, got, want[..., :C], amb,
+                                          gv, want[..., -1] == 1, sa.rule_eq1, rtol=RTOL, atol=ATOL)
+        assert unique or n['judged'] > 100
         # the generic entry takes the same path and gives the same bits; so do row bands
         out2, valid2 = dev.DeviceBuffer(h * w * C * 4), dev.DeviceBuffer(h * w)
         dev.scatter_linear(f, sign, None, dv, C, dm, h, w, None, out2, valid2, 0)
@@ -251,7 +258,15 @@ def test_certified_walk_first_estimate_affine_and_not(gpu, oracle):
 
 
 # ---------------------------------------------------------------------------------------------- exact path
-from scatter_util import nonunique_nodes, warped_points      # noqa: E402
+from scatter_util import nonunique_nodes, warped_points, reference_case      # noqa: E402
+import scatter_admissible as sa      # noqa: E402
+
+
+def rows_with_mask(vals, vm, keep=None):
+    """the value rows SciPy received: the values and, last, the value mask -- of the kept points"""
+    h, w = vals.shape[:2]
+    r = np.concatenate([vals.reshape(h * w, -1), np.asarray(vm, np.float32).reshape(h * w, 1)], 1)
+    return r if keep is None else r[np.asarray(keep, bool).ravel()]
 
 
 def fixture_case(g, tag):
@@ -286,8 +301,18 @@ def test_exact_path_matches_reference_outputs(gpu, golden2, tag, near2_always):
     np.testing.assert_array_equal(r.mask, g[tag + '/invert_mask'], err_msg=tag)
     badv = ~np.isclose(r.vecs, g[tag + '/invert_vecs'], rtol=RTOL, atol=ATOL).all(-1)
     assert not (badv & ~amb).any(), (tag, int((badv & ~amb).sum()))
+    # inside the non-unique simplices (sintel4x4: two thirds of the nodes, duplicated sites; hole_img: the lattice around the
+    # hole): equal to the reference's output, or one of the admissible alternatives
+    for op, got, gvalid in (('apply', w, v), ('invert', r.vecs, r.mask)):
+        c = reference_case(g, tag + '/' + op)
+        n = sa.assert_equal_or_admissible(tag + '/' + op, c['points'], c['values'], c['shape'], got, c['out'], amb, gvalid, c['out_valid'],
+                                          c['rule'], rtol=RTOL, atol=ATOL)
+        assert n['judged'] >= amb.sum()
+    # The direct comparison above is not vacuous: few nodes are exempt from it.  sintel4x4 (66 % non-unique) and hole_img (13 %)
+    # cannot meet this bound by their geometry; their non-unique nodes are covered by the admissibility loop above, which judged
+    # every one of them (judged >= amb.sum()) and found none inadmissible.
     if tag not in ("sintel4x4", "hole_img"):
-        assert amb.mean() < 0.12, (tag, amb.mean())           # the comparison above is not vacuous
+        assert amb.mean() < 0.12, (tag, amb.mean())
 
 
 def test_exact_path_bands_and_determinism(gpu, golden2, near2_always):
@@ -393,6 +418,8 @@ def test_notch_open_to_the_border(gpu, oracle, near2_always):
     np.testing.assert_array_equal(gv[~amb], (want[..., -1] == 1)[~amb])
     bad = ~np.isclose(got, want[..., :2], rtol=RTOL, atol=ATOL).all(-1)
     assert not (bad & ~amb).any(), (int((bad & ~amb).sum()), np.argwhere(bad & ~amb)[:4].tolist())
+    sa.assert_equal_or_admissible("notch", pts, rows_with_mask(vals, vm, pm), (h, w), got, want[..., :2], amb, gv, want[..., -1] == 1,
+                                  sa.rule_eq1, rtol=RTOL, atol=ATOL)
     assert gv[20:90, 100:230].mean() > 0.5                                   # the notch is triangulated across (inside the hull)
 
 
@@ -504,6 +531,10 @@ def test_block_collapsed_onto_one_pixel_matches_scipy(gpu, oracle):
     assert 0.2 < amb.mean() < 0.5 and (inside & ~amb).mean() > 0.3    # the fan around the collapsed vertex fills the block's old place; the rest is unique
     bad = ~np.isclose(got, want, rtol=RTOL, atol=ATOL).all(-1)
     assert not (bad & ~amb).any(), (int((bad & ~amb).sum()), np.argwhere(bad & ~amb)[:5].tolist())
+    # the fan around the collapsed vertex: it carries the value of ONE of its 4 900 duplicates, whichever
+    n = sa.assert_equal_or_admissible("collapsed block", warped_points(vecs), rows_with_mask(img, np.ones(shape)), shape, got, want, amb, valid,
+                                      wvalid, sa.rule_eq1, rtol=RTOL, atol=ATOL)
+    assert n['judged'] >= amb.sum() and n['not_judged'] == 0
     # a second, smaller collapse (below the hash-table threshold: pairwise dedupe) next to it, and determinism
     vecs[82:92, 100:112, 0] = 108.5 - xx[82:92, 100:112]
     vecs[82:92, 100:112, 1] = 88.25 - yy[82:92, 100:112]
@@ -550,6 +581,8 @@ def test_dense_clusters_of_distinct_sites_match_scipy(gpu, oracle, factor):
         assert (inside & ~amb).mean() > 0.5
         bad = ~np.isclose(got, want, rtol=RTOL, atol=ATOL).all(-1) & ~amb
         assert not bad.any(), (factor, pm is not None, int(bad.sum()), np.argwhere(bad)[:5].tolist())
+        sa.assert_equal_or_admissible(str((factor, pm is not None)), warped_points(vecs, keep), rows_with_mask(img, np.ones(shape), keep), shape, got,
+                                      want, amb, valid, wvalid, sa.rule_eq1, rtol=RTOL, atol=ATOL)
         np.testing.assert_array_equal(f.apply(img), got)
     # the nodes INSIDE the cluster are covered by its tiny triangles: the warped image there is the block's content, shrunk
     cy, cx = 47.7, 61.3
@@ -652,6 +685,8 @@ def test_exact_path_medium_field_against_scipy(gpu, oracle, near2_always):
     np.testing.assert_array_equal(gv[~amb], (want[..., -1] == 1)[~amb])
     bad = ~np.isclose(got, want[..., :2], rtol=RTOL, atol=ATOL).all(-1)
     assert not (bad & ~amb).any(), (int((bad & ~amb).sum()), np.argwhere(bad & ~amb)[:4].tolist())
+    sa.assert_equal_or_admissible("medium", pts, rows_with_mask(vals, vm, pm), (h, w), got, want[..., :2], amb, gv, want[..., -1] == 1,
+                                  sa.rule_eq1, rtol=RTOL, atol=ATOL)
 
 
 def test_wavy_border_against_scipy(gpu, oracle):
@@ -682,6 +717,8 @@ def test_wavy_border_against_scipy(gpu, oracle):
     np.testing.assert_array_equal(gv[~amb], (want[..., -1] == 1)[~amb])
     bad = ~np.isclose(got, want[..., :2], rtol=RTOL, atol=ATOL).all(-1)
     assert not (bad & ~amb).any(), (int((bad & ~amb).sum()), np.argwhere(bad & ~amb)[:4].tolist())
+    sa.assert_equal_or_admissible("wavy", pts, rows_with_mask(vals, np.ones((h, w)), pm), (h, w), got, want[..., :2], amb, gv, want[..., -1] == 1,
+                                  sa.rule_eq1, rtol=RTOL, atol=ATOL)
 
 
 def test_exact_path_random_fields_against_scipy(gpu, oracle, near2_always):
@@ -724,6 +761,8 @@ def test_exact_path_random_fields_against_scipy(gpu, oracle, near2_always):
         np.testing.assert_array_equal(gv[~amb], (want[..., -1] == 1)[~amb], err_msg=str((it, h, w)))
         bad = ~np.isclose(got, want[..., :C], rtol=RTOL, atol=ATOL).all(-1)
         assert not (bad & ~amb).any(), (it, h, w, int((bad & ~amb).sum()), np.argwhere(bad & ~amb)[:4].tolist())
+        sa.assert_equal_or_admissible(str((it, h, w)), pts, rows_with_mask(vals, vm, pm), (h, w), got, want[..., :C], amb, gv, want[..., -1] == 1,
+                                      sa.rule_eq1, rtol=RTOL, atol=ATOL)
         assert amb.mean() < 0.2, (it, amb.mean())
 
 
@@ -823,6 +862,8 @@ def test_random_collapses_against_scipy(gpu, oracle):
         amb, inside = nonunique_nodes(warped_points(vecs), shape)
         bad = ~np.isclose(got, want, rtol=RTOL, atol=ATOL).all(-1)
         assert not (bad & ~amb).any(), (it, int((bad & ~amb).sum()), np.argwhere(bad & ~amb)[:5].tolist())
+        sa.assert_equal_or_admissible("round {}".format(it), warped_points(vecs), rows_with_mask(img, np.ones(shape)), shape, got, want, amb,
+                                      valid, wvalid, sa.rule_eq1, rtol=RTOL, atol=ATOL)
 
 
 def test_soak_regressions(gpu, oracle):
@@ -836,14 +877,16 @@ def test_soak_regressions(gpu, oracle):
     from scatter_util import nonunique_nodes, hull_band
     total = 0
     for seed in (1000020, 1000058, 1000112, 1000200, 1000212, 1000344, 1000485, 1000492):
-        n, bad, msg = one_case(dev, oracle, nonunique_nodes, hull_band, seed, 160, 240)
-        assert bad == 0, msg
+        n, bad, msg, inadmissible, nj, inside = one_case(dev, oracle, nonunique_nodes, hull_band, seed, 160, 240)
+        assert bad == 0 and inadmissible == 0, msg
+        assert nj <= 1e-3 * inside, (seed, nj, inside)              # per case: not judged <= 0.1 % of the nodes inside the hull
         total += n
     # larger fields: sites that are EXACTLY co-circular must be a tie for all four stars that ask (incircle_origin_filtered;
     # seed 3000265), and Qhull's own tolerance grows with the coordinates (seed 3000143: scatter_util.nonunique_nodes)
     for seed in (3000143, 3000265):
-        n, bad, msg = one_case(dev, oracle, nonunique_nodes, hull_band, seed, 320, 420)
-        assert bad == 0, msg
+        n, bad, msg, inadmissible, nj, inside = one_case(dev, oracle, nonunique_nodes, hull_band, seed, 320, 420)
+        assert bad == 0 and inadmissible == 0, msg
+        assert nj <= 1e-3 * inside, (seed, nj, inside)
         total += n
     assert total > 150_000
 
@@ -860,8 +903,71 @@ def test_query_soak_regressions(gpu, oracle):
     from scatter_util import nonunique_nodes, hull_band
     total = 0
     for seed in (5000011, 5000017, 5000022, 5000030, 5000043, 5000078):
-        n, bad, msg = one_query_case(dev, oracle, nonunique_nodes, hull_band, seed, 160, 240)
-        assert bad == 0, msg
+        n, bad, msg, inadmissible, nj, inside = one_query_case(dev, oracle, nonunique_nodes, hull_band, seed, 160, 240)
+        assert bad == 0 and inadmissible == 0, msg
+        assert nj <= 1e-3 * inside, (seed, nj, inside)              # per case: not judged <= 0.1 % of the positions inside the hull
         total += n
     assert total > 20_000
 
+
+
+# ------------------------------------------------------------------ fields whose EVERY simplex is non-unique: the checker alone
+def lattice_translation():
+    """24 x 40, every point moved by (2.25, -1.5): every cell an exact square, no node on a site; random 3-channel values and
+    a speckled value mask"""
+    rng = np.random.default_rng(61)
+    shape = (24, 40)
+    vecs = np.broadcast_to(np.float32([2.25, -1.5]), shape + (2,)).copy()
+    return shape, vecs, rng.random(shape + (3,), dtype=np.float32), rng.random(shape) > 0.2
+
+
+def four_fold():
+    """16 x 24: the 2 x 2 blocks of the left 16 columns fold onto their own centres -- 64 positions that four sites share, with four
+    distinct value rows each, on a lattice of spacing 2 (every cell co-circular) -- next to 8 columns that stay where they are"""
+    rng = np.random.default_rng(62)
+    shape = (16, 24)
+    yy, xx = np.mgrid[:shape[0], :shape[1]].astype(np.float32)
+    vecs = np.zeros(shape + (2,), np.float32)
+    vecs[:, :16, 0] = (2 * (xx // 2) + 0.5 - xx)[:, :16]
+    vecs[:, :16, 1] = (2 * (yy // 2) + 0.5 - yy)[:, :16]
+    return shape, vecs, rng.random(shape + (3,), dtype=np.float32), rng.random(shape) > 0.2
+
+
+@pytest.mark.parametrize("make", [lattice_translation, four_fold])
+def test_every_simplex_non_unique(gpu, oracle, make):
+    """No node of these two fields lies in a uniquely Delaunay simplex with unduplicated sites, so the comparison with SciPy's
+    output alone would check next to nothing: every node inside the hull must be ADMISSIBLE -- the interpolation on one of the
+    triangles of the co-circular sites that hold it, with one of the duplicates per corner, values and validity of the
+    speckled value mask from the same one -- and every node outside must be SciPy's.  Through the C entry (the route it chooses
+    and the Delaunay path), Flow.apply and Flow.invert."""
+    of, O = gpu, oracle
+    from oflibnumpy_amd import device as dev
+    shape, vecs, vals, vm = make()
+    h, w = shape
+    every = np.ones(shape, bool)
+    pts = warped_points(vecs)
+    amb, inside = nonunique_nodes(pts, shape)
+    assert (amb == inside).all() and 0.6 < inside.mean() < 1
+    f, dv, dm = (dev.DeviceBuffer.from_host(a) for a in (vecs, vals, vm.astype(np.uint8)))
+    want = O.scatter_griddata(vecs, np.concatenate([vals, vm[..., None].astype(np.float32)], -1), None)
+    for flags in (0, of.native.SCATTER_UNCERTIFIED):
+        out, valid = dev.DeviceBuffer(h * w * 12), dev.DeviceBuffer(h * w)
+        dev.scatter_linear(f, +1, None, dv, 3, dm, h, w, None, out, valid, flags)
+        got, gv = out.to_host((h, w, 3), np.float32), valid.to_host((h, w), np.uint8).astype(bool)
+        n = sa.assert_equal_or_admissible("{} flags {}".format(make.__name__, flags), pts, rows_with_mask(vals, vm), shape, got, want[..., :3],
+                                          every, gv, want[..., -1] == 1, sa.rule_eq1, rtol=RTOL, atol=ATOL)
+        assert n['judged'] == n['inside'] == inside.sum() and n['not_judged'] == 0
+        assert 0.2 < gv[inside].mean() < 0.8                                    # the speckle decides: neither all valid nor none
+    # Flow.apply: the flow's mask as the value mask, every point kept
+    fl, o = of.Flow(vecs, 's', vm), O.OFlow(vecs, 's', vm)
+    gw, gv = fl.apply(vals, return_valid_area=True, consider_mask=False)
+    ow, ov = o.apply(vals, return_valid_area=True, consider_mask=False)
+    n = sa.assert_equal_or_admissible(make.__name__ + " apply", pts, rows_with_mask(vals, vm), shape, gw, ow, every, gv, ov, sa.rule_eq1,
+                                      rtol=RTOL, atol=ATOL)
+    assert n['judged'] == n['inside'] and n['not_judged'] == 0
+    # Flow.invert: the masked-out points are dropped (holes in the lattice: larger empty circles), the rows are the negated vectors
+    gi, oi = fl.invert(), o.invert()
+    kept = warped_points(vecs, vm)
+    n = sa.assert_equal_or_admissible(make.__name__ + " invert", kept, rows_with_mask(-vecs, vm, vm), shape, gi.vecs, oi.vecs, every, gi.mask,
+                                      oi.mask, sa.rule_eq1, rtol=RTOL, atol=ATOL)
+    assert n['judged'] == n['inside'] > 0.5 * h * w

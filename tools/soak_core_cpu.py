@@ -2,9 +2,11 @@
 """Soak of the geometry core on the CPU (no GPU needed): tests/native/dl_core_cpu.cpp compiles the very header the kernels use
 (ofl_delaunay_core.h: mesh cells, mesh fans, clip pass, second per-thread pass; its far pass is a plain sequential clip) and
 builds all stars of a random field of tests/scatter_soak_util.py; every simplex of scipy.spatial.Delaunay that is uniquely
-Delaunay must be among the triangles the stars list.
+Delaunay must be among the triangles the stars list, and no triangle they list may hold a site inside its circumcircle by more
+than 5e-8 of the radius (float64 rounding is 1e-15; two float32 roundings of one position are at least 6e-8 apart).
 
     python tools/soak_core_cpu.py [--seconds 600] [--seed 0] [--jobs 8] [--max 140 200]
+    python tools/soak_core_cpu.py --only 13000117          (one case, e.g. the one INTEGRATION.md 3 describes)
 """
 import argparse
 import ctypes
@@ -65,10 +67,21 @@ def work(job):
     want = {tuple(sorted(int(idx[v]) for v in t)) for t, u in zip(d.simplices, uniq) if u}
     got = {tuple(sorted(int(v) for v in t)) for t in tri}
     miss = want - got
+    # nothing but Delaunay triangles (slivers between near-duplicate sites aside, as above)
+    from scipy.spatial import cKDTree
+    t = np.array(sorted(got), np.int64).reshape(-1, 3)
+    cen, r, _ = T.circum(P, t)
+    a, b, c = P[t[:, 0]], P[t[:, 1]], P[t[:, 2]]
+    area = 0.5 * np.abs((b[:, 0] - a[:, 0]) * (c[:, 1] - a[:, 1]) - (b[:, 1] - a[:, 1]) * (c[:, 0] - a[:, 0]))
+    edge = np.minimum(np.minimum(np.hypot(*(b - a).T), np.hypot(*(c - b).T)), np.hypot(*(a - c).T))
+    good = np.isfinite(r) & (r < 1e6) & (area > 1e-6) & (edge > 1e-4)
+    nearest = cKDTree(P[idx]).query(cen[good])[0]
+    intruded = t[good][nearest < r[good] * (1 - 5e-8) - 1e-9]
     msg = None
-    if miss:
-        msg = "kind {} {}x{} sign {} mask {}: {} of {} unique simplices missing, e.g. {}".format(kind, h, w, sign, pm is not None, len(miss), len(want), sorted(miss)[:2])
-    return seed, len(want), len(miss), msg
+    if miss or len(intruded):
+        msg = "kind {} {}x{} sign {} mask {}: {} of {} unique simplices missing, e.g. {}; {} listed triangles with a site inside their circle, e.g. {}".format(
+            kind, h, w, sign, pm is not None, len(miss), len(want), sorted(miss)[:2], len(intruded), intruded[:2].tolist())
+    return seed, len(want), len(miss) + len(intruded), msg
 
 
 def main():
@@ -77,9 +90,16 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--max", type=int, nargs=2, default=[140, 200])
+    ap.add_argument("--only", type=int, default=None, help="run this one seed")
     args = ap.parse_args()
     so = os.path.join(tempfile.mkdtemp(), "libdlcore.so")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "native", "dl_core_cpu.cpp")])
+    if args.only is not None:
+        init(so)
+        s, n, b, msg = work((args.only, args.max[0], args.max[1]))
+        print(json.dumps({"soak": "geometry core on the CPU vs scipy.spatial.Delaunay", "seed": s, "unique_simplices_checked": n,
+                          "missing_or_not_delaunay": b, "details": [msg] if msg else []}))
+        return
     t0, cases, simplices, bad, msgs = time.time(), 0, 0, 0, []
     seed = args.seed * 1_000_000
     with Pool(args.jobs, initializer=init, initargs=(so,)) as pool:
@@ -91,7 +111,7 @@ def main():
                 if msg:
                     msgs.append("seed {}: {}".format(s, msg))
     print(json.dumps({"soak": "geometry core on the CPU vs scipy.spatial.Delaunay", "seed_base": args.seed * 1_000_000, "cases": cases,
-                      "unique_simplices_checked": simplices, "missing": bad, "details": msgs[:16]}))
+                      "unique_simplices_checked": simplices, "missing_or_not_delaunay": bad, "details": msgs[:16]}))
 
 
 if __name__ == "__main__":
