@@ -702,6 +702,65 @@ int ofl_consistency(const float *f, const uint8_t *fm, const float *b, const uin
                     int H, int W, int batch, float alpha, float beta,
                     uint8_t *consistent, uint8_t *covered, float *residual, uint32_t *counts_host, int quant);
 
+/* ------------------------------------------------------------------ K14: an estimated field against a ground truth
+ * How far `est` is from `gt`: end-point error, threshold and outlier counts, and the error by speed of the ground truth --
+ * Sintel's EPE by speed bins (edges 10, 40) and KITTI's "Fl" rule (3 px and 5 %) with its validity mask are two settings
+ * of it.  est and gt have one shape and one reference; the reference does not enter the arithmetic.  Per pixel, every
+ * operation float32 and rounded once (sqrtf is the correctly rounded square root):
+ *     du = est.u - gt.u;  dv = est.v - gt.v
+ *     epe  = sqrtf(du*du + dv*dv)
+ *     g    = sqrtf(gt.u*gt.u + gt.v*gt.v)
+ *     eval = gt.mask & (est_mask given ? est.mask : 1)
+ *     bad  = eval & !isfinite(epe)            NaN / Inf in either field, or an overflow of du*du + dv*dv: one rule
+ *     ok   = eval &  isfinite(epe)
+ *     over[k] = ok & (epe > thr[k])           k < 4, strict; an unused slot is +inf
+ *     outlier = ok & (epe > out_abs) & (epe > out_rel * g)        a product: no division by 0 where gt = 0
+ *     bin     = the number of edges[j] (j < 3, ascending, unused = +inf) with g >= edges[j]
+ * (g = +inf, a ground truth whose square overflows, is >= every edge, the unused ones included: such a pixel is in bin 3.)
+ * Per pair one record; the uint32 part comes first so that the doubles are 8-byte aligned; 96 bytes:
+ */
+struct ofl_flow_error {
+    uint32_t n;               /* ok pixels: every count and sum below runs over these */
+    uint32_t n_nonfinite;     /* bad pixels */
+    uint32_t n_over[4];       /* epe > thr[k] */
+    uint32_t n_outlier;
+    uint32_t n_bin[4];
+    uint32_t max_epe_bits;    /* the float32 bit pattern of the largest ok epe (non-negative floats sort as uint32), 0 if n = 0 */
+    double   sum_epe;
+    double   sum_epe2;        /* terms double(epe) * double(epe): exact */
+    double   sum_bin_epe[4];
+};
+/* Optional per-pixel outputs, written when the pointer is not NULL: epe_map float32 [batch][H][W] = epe where ok, else 0;
+ * outlier_map uint8 [batch][H][W] = the outlier bit.
+ * A pure stream: 18 B/px read (two 8-byte vectors, two mask bytes; 17 without est_mask), nothing written per pixel without
+ * a map, no LDS staging of data and no atomics.  A workgroup takes one chunk of 4096 consecutive pixels of one pair;
+ * thread t of chunk c owns pixels c*4096 + s*1024 + 4*t + j (s, j < 4) on every load path, so the order of additions is a
+ * function of H * W alone: the doubles of a record do not depend on alignment, on the load path or on batch.  A thread
+ * adds its terms in pixel order, a wave reduces by a six-level xor butterfly, the four wave values are added in order, and a
+ * finishing kernel (one workgroup of 256 threads per pair) gives thread t the chunk partials t, t + 256, ... in order, then
+ * butterfly, then waves in order.  The longest chain of additions a term passes through is
+ *     depth(H*W) = 16 + 6 + 3 + ceil(chunks / 256) + 6 + 3,        chunks = ceil(H*W / 4096)
+ * so every float64 sum (its terms are >= 0) is within depth * 2^-53 * sum of the exact sum.  Counts and the maximum are
+ * integer operations and exact.
+ * Out of scope: the angular error (it needs atan2, which cannot be pinned bit for bit against NumPy here), and the median or
+ * a percentile of the EPE (it would need a third copy of the radix select of K7 / K8).
+ * thr, edges: HOST pointers, passed on as kernel arguments.  workspace: device memory of at least
+ * ofl_flow_error_workspace_bytes(H, W, batch) bytes, 8-byte aligned; it needs no initialisation (the kernels write every
+ * word they read).  est, gt 8-byte, epe_map 4-byte, records 8-byte aligned.  Outputs must not alias inputs.
+ * A bad argument -- a NULL est / gt / gt_mask / thr / edges / workspace / records, H or W < 1, H*W >= 2^31, batch outside
+ * [1, 65535], a NaN or negative threshold, bound or edge, edges not ascending, a short workspace -- returns OFL_E_INVALID
+ * with a message before any launch.  The _dev entry is asynchronous; the host entry takes host pointers (est_mask,
+ * epe_map, outlier_map optional), uploads, launches, downloads and synchronises.
+ */
+int ofl_flow_error_workspace_bytes(int H, int W, int batch, size_t *bytes);
+int ofl_flow_error_dev(const float *est, const uint8_t *est_mask, const float *gt, const uint8_t *gt_mask,
+                       int H, int W, int batch, const float thr[4], float out_abs, float out_rel, const float edges[3],
+                       void *workspace, size_t workspace_bytes, struct ofl_flow_error *records,
+                       float *epe_map, uint8_t *outlier_map, void *stream);
+int ofl_flow_error(const float *est, const uint8_t *est_mask, const float *gt, const uint8_t *gt_mask,
+                   int H, int W, int batch, const float thr[4], float out_abs, float out_rel, const float edges[3],
+                   struct ofl_flow_error *records_host, float *epe_map, uint8_t *outlier_map);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

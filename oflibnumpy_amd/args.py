@@ -244,6 +244,56 @@ def consistency_args(alpha=None, beta=None):
     return out[0], out[1]
 
 
+# -- an estimate against a ground truth (K14)
+ERROR_THRESHOLDS, ERROR_OUTLIER, ERROR_SPEED_EDGES = (1, 3, 5), (3, 0.05), (10, 40)     # px; KITTI's Fl rule; Sintel's speed bins
+
+
+def _error_value(name, value):
+    """one threshold, bound or edge -> float32; a bool or a non-number is a TypeError, NaN or a negative value a ValueError"""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise TypeError("Error evaluating flow error: {} must be numbers, got {}".format(name, type(value).__name__))
+    if value != value or value < 0:
+        raise ValueError("Error evaluating flow error: {} must not be NaN or negative, got {}".format(name, value))
+    with np.errstate(over='ignore'):
+        return np.float32(float(value)) if value < 1e300 else np.float32(np.inf)
+
+
+def _error_list(name, values, default, most):
+    values = default if values is None else values
+    if isinstance(values, (int, float, np.integer, np.floating)) and not isinstance(values, (bool, np.bool_)):
+        values = (values,)
+    if isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list, np.ndarray)):
+        raise TypeError("Error evaluating flow error: {} must be a number or a tuple or list of numbers, got {}"
+                        .format(name, type(values).__name__))
+    if isinstance(values, np.ndarray) and values.ndim != 1:
+        raise ValueError("Error evaluating flow error: {} must be one-dimensional".format(name))
+    values = [_error_value(name, v.item() if isinstance(v, np.generic) and not isinstance(v, np.bool_) else v) for v in values]
+    if len(values) > most:
+        raise ValueError("Error evaluating flow error: at most {} {}, got {}".format(most, name, len(values)))
+    return values
+
+
+def error_args(thresholds=None, outlier=None, speed_edges=None):
+    """Validation of the settings of the flow-error evaluation (K14) on the host before any device work ->
+    (thr float32[4], (out_abs, out_rel) as float32, edges float32[3], n_thresholds, n_edges).  thresholds: up to 4 EPE
+    thresholds in px (default 1, 3, 5); outlier: (absolute px, relative share of the ground truth's magnitude), both of
+    which an outlier exceeds (default KITTI's 3 px and 5 %); speed_edges: up to 3 ascending magnitudes of the ground truth
+    that separate the speed bins (default Sintel's 10, 40).  Unused slots are +inf.  A bool, a string or another non-number
+    is a TypeError; NaN, a negative value, too many entries and descending edges are a ValueError."""
+    thr = _error_list("thresholds", thresholds, ERROR_THRESHOLDS, 4)
+    edges = _error_list("speed_edges", speed_edges, ERROR_SPEED_EDGES, 3)
+    out = ERROR_OUTLIER if outlier is None else outlier
+    if isinstance(out, (str, bytes)) or not isinstance(out, (tuple, list, np.ndarray)):
+        raise TypeError("Error evaluating flow error: outlier must be a pair (absolute, relative), got {}".format(type(out).__name__))
+    if len(out) != 2:
+        raise ValueError("Error evaluating flow error: outlier must be a pair (absolute, relative), got {} values".format(len(out)))
+    out = _error_list("outlier", out, None, 2)
+    if any(b < a for a, b in zip(edges, edges[1:])):
+        raise ValueError("Error evaluating flow error: speed_edges must be ascending, got {}".format([float(e) for e in edges]))
+    pad = lambda v, n: np.array(v + [np.inf] * (n - len(v)), np.float32)
+    return pad(thr, 4), (out[0], out[1]), pad(edges, 3), len(thr), len(edges)
+
+
 # -- many-channel float tensors (K12)
 def tensor_dtype(array_dtype, dtype=None):
     """The element type of a tensor -> 'float32', 'float16' or 'bfloat16'.  `array_dtype`: the dtype of the array that holds

@@ -140,6 +140,19 @@ class DeviceFlowBatch:
         res = (consistent, covered) + ((residual,) if return_residual else ())
         return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
 
+    def error(self, gt, thresholds=None, outlier=None, speed_edges=None, use_est_mask=True, return_map=False, return_outliers=False):
+        """self[i].error(gt[i], ...) for every i in ONE launch of K14 (DeviceFlow.error): `gt` a batch of the same length,
+        shape and reference.  -> a DeviceFlowError whose read() gives a list of n FlowErrorStats (the one read-back, 96 bytes
+        per pair) and whose maps, if asked for, are [n][H][W].  A packed batch is read through its byte masks."""
+        thr, out, edges, n_thr, n_edges = dev.error_args(thresholds, outlier, speed_edges)
+        if not isinstance(gt, DeviceFlowBatch):
+            raise TypeError("Error evaluating flow error: gt needs to be a DeviceFlowBatch, got {}".format(type(gt).__name__))
+        if (self.n, self.shape, self.ref) != (gt.n, gt.shape, gt.ref):
+            raise ValueError("batches need the same length, shape and reference")
+        records, epe_map, outlier_map = dev.error_launch(self.vecs, self.mask if use_est_mask else None, gt.vecs, gt.mask, self.shape,
+                                                         thr, out, edges, batch=self.n, want_map=return_map, want_outliers=return_outliers)
+        return dev.DeviceFlowError(records, self.n, n_thr, n_edges, epe_map, outlier_map)
+
     def apply_images(self, images, dtype, channels, shared=False, target_masks=None, shared_masks=False, quant=nat.QUANT_OPENCV):
         """self[i].apply(image_i, target_mask_i, return_valid_area=True) for every i in ONE launch of the gather kernel
         (ref 't' batches; Flow.apply, flow_class.py:604-695 without padding).  `images`: a DeviceBuffer holding [n][H][W][C] of

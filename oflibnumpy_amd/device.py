@@ -31,12 +31,13 @@ from .memory import (_lib, _ptr, _size_query, _Pool, _PinnedPool, empty_cache, D
 from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rules, mask_bytes, _points_array, visualise_args,
                    percentile_ranks, matrix_args, validate_transforms, valid_mask_array, scale_operand, crop_args,
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
-                   consistency_args)
+                   consistency_args, error_args)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
                       track_bilinear_launch, track_query_points, track_query_epilogue, gather_tensor, tensor_import_launch,
-                      tensor_permute_launch, consistency_launch, consistency_host)
+                      tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
+                      FlowErrorStats)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -327,6 +328,24 @@ def track_args(pts, int_out=None, get_valid_status=None, s_exact_mode=None):
 _STATS_KNOW_MASK = 1 << 30        # private flag in DeviceFlow._stats: STAT_MASK_HAS_ZERO has been evaluated
 
 
+class DeviceFlowError:
+    """The result of DeviceFlow.error / DeviceFlowBatch.error while it is still on the device: `records` (96 bytes per
+    pair, struct ofl_flow_error), and the optional `epe_map` / `outlier_map` DeviceBuffers ([n][H][W] for a batch).
+    `read()` is the one read-back: a FlowErrorStats, or a list of n of them for a batch."""
+
+    def __init__(self, records, n, n_thresholds, n_edges, epe_map=None, outlier_map=None):
+        self.records, self.n, self.epe_map, self.outlier_map = records, n, epe_map, outlier_map
+        self._n_thresholds, self._n_edges = n_thresholds, n_edges
+
+    def read_records(self):
+        """the raw records as a NumPy array of kernels.ERROR_RECORD, one per pair (synchronises)"""
+        return self.records.to_host((1 if self.n is None else self.n,), ERROR_RECORD)
+
+    def read(self):
+        stats = [FlowErrorStats(r, self._n_thresholds, self._n_edges) for r in self.read_records()]
+        return stats[0] if self.n is None else stats
+
+
 class DeviceFlow:
     """(vecs, mask, ref) resident in HBM.  Buffers are immutable once wrapped."""
 
@@ -595,6 +614,28 @@ class DeviceFlow:
             n = counts.to_host((2,), np.uint32)
             res += ((int(n[0]), int(n[1])),)
         return res
+
+    def error(self, gt, thresholds=None, outlier=None, speed_edges=None, use_est_mask=True, return_map=False, return_outliers=False):
+        """How far this (estimated) field is from the ground truth `gt`, a DeviceFlow of the same shape and reference, in one
+        launch of K14 (include/ofl.h) and without leaving HBM: per pixel epe = |self - gt| in float32 with one rounding per
+        operation, evaluated where gt.mask (and, with use_est_mask, self.mask) is set and the error is finite.  thresholds: up
+        to 4 EPE thresholds (default 1, 3, 5 px); outlier: (absolute, relative) -- a pixel is an outlier when its error exceeds
+        both the absolute bound and the relative share of |gt| (default KITTI's 3 px and 5 %); speed_edges: up to 3 ascending
+        magnitudes of gt that separate the speed bins (default Sintel's 10, 40); see args.error_args.
+        -> a DeviceFlowError: the 96-byte record on the device plus, with return_map / return_outliers, `.epe_map` (float32
+        [H][W], the error where evaluated, else 0) and `.outlier_map` (uint8 [H][W]) as DeviceBuffers.  Nothing synchronises
+        until `.read()` -> FlowErrorStats.  Not a function of the reference: no angular error, no median.  The inputs are not
+        modified."""
+        thr, out, edges, n_thr, n_edges = error_args(thresholds, outlier, speed_edges)
+        if not isinstance(gt, DeviceFlow):
+            raise TypeError("Error evaluating flow error: gt needs to be a DeviceFlow, got {}".format(type(gt).__name__))
+        if gt.shape != self.shape:
+            raise ValueError("Error evaluating flow error: the fields need the same shape, got {} and {}".format(self.shape, gt.shape))
+        if gt.ref != self.ref:
+            raise ValueError("Error evaluating flow error: the fields need the same reference, got '{}' and '{}'".format(self.ref, gt.ref))
+        records, epe_map, outlier_map = error_launch(self.vecs, self.mask if use_est_mask else None, gt.vecs, gt.mask, self.shape,
+                                                     thr, out, edges, want_map=return_map, want_outliers=return_outliers)
+        return DeviceFlowError(records, None, n_thr, n_edges, epe_map, outlier_map)
 
     # -- warping
     def apply(self, target, consider_mask=True, quant=nat.QUANT_OPENCV, target_mask=None):

@@ -451,6 +451,35 @@ class Flow(object):
         return dev.consistency_host(self._vecs, self._mask, backward._vecs, backward._mask, 1 if self._ref == 's' else -1,
                                     alpha, beta, return_residual)
 
+    def error(self, gt: FlowAlias, thresholds=None, outlier=None, speed_edges=None, use_est_mask: bool = None,
+              return_map: bool = None):
+        """How far this (estimated) flow is from the ground truth `gt`, a flow of the same shape and reference: the
+        end-point error |self - gt| over the pixels where gt.mask (and, unless use_est_mask is False, self.mask) is set and the
+        error is finite.  -> FlowErrorStats with n, n_nonfinite, epe (mean), rmse, max, over (share above each of up to 4
+        `thresholds`, default 1, 3, 5 px), outlier (share above both bounds of `outlier`, default KITTI's 3 px and 5 % of
+        |gt|) and bins ((n, mean epe) per speed bin of gt, `speed_edges` default Sintel's 10, 40); with `return_map` also the
+        float32 (H, W) error (0 where not evaluated).  Not a function of the reference; the definition is DeviceFlow.error's.
+        One upload, one launch, one download."""
+        thr, out, edges, n_thr, n_edges = dev.error_args(thresholds, outlier, speed_edges)
+        use_est_mask = True if use_est_mask is None else use_est_mask
+        return_map = False if return_map is None else return_map
+        if not isinstance(use_est_mask, bool):
+            raise TypeError("Error evaluating flow error: Use_est_mask needs to be a boolean")
+        if not isinstance(return_map, bool):
+            raise TypeError("Error evaluating flow error: Return_map needs to be a boolean")
+        if not isinstance(gt, Flow):
+            raise TypeError("Error evaluating flow error: Gt needs to be of type 'Flow'")
+        if self.shape != gt.shape:
+            raise ValueError("Error evaluating flow error: Flow fields need to have the same shape, got {} and {}"
+                             .format(self.shape, gt.shape))
+        if self.ref != gt.ref:
+            raise ValueError("Error evaluating flow error: Flow fields need to have the same reference, got '{}' and '{}'"
+                             .format(self.ref, gt.ref))
+        record, epe_map, _ = dev.error_host(self._vecs, self._mask if use_est_mask else None, gt._vecs, gt._mask, thr, out, edges,
+                                            want_map=return_map)
+        stats = dev.FlowErrorStats(record, n_thr, n_edges)
+        return (stats, epe_map) if return_map else stats
+
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
         """flow_1 (+) flow_2 = flow_3: mode k returns flow_k from the other two (`self` comes first in
         that formula among the two given).  Reference flow_class.py:1247-1424."""

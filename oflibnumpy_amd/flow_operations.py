@@ -10,7 +10,7 @@ from .flow_class import Flow
 
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
-           'get_flow_matrix', 'visualise_flow', 'flow_consistency']
+           'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -65,3 +65,11 @@ def visualise_flow(flow: nd, mode: str, range_max: float = None) -> nd:
 def flow_consistency(forward: nd, backward: nd, ref: str, alpha: float = None, beta: float = None) -> tuple:
     """(consistent, covered) bool (H, W) masks of the forward-backward check of two flow arrays (Flow.consistency)."""
     return Flow(forward, ref).consistency(Flow(backward, ref), alpha=alpha, beta=beta)
+
+
+def flow_error(est: nd, gt: nd, ref: str, gt_mask: nd = None, thresholds=None, outlier=None, speed_edges=None,
+               return_map: bool = None):
+    """FlowErrorStats of the estimated flow array `est` against the ground-truth array `gt` with its validity mask
+    `gt_mask` (None: all valid) -- Flow.error; with `return_map` also the float32 (H, W) end-point error."""
+    return Flow(est, ref).error(Flow(gt, ref, gt_mask), thresholds=thresholds, outlier=outlier, speed_edges=speed_edges,
+                                return_map=return_map)

@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps and K13 consistency.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency and K14 flow error.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -112,6 +112,78 @@ def consistency_host(f_vecs, f_mask, b_vecs, b_mask, sign, alpha, beta, want_res
                                      None if residual is None else residual.ctypes.data, None, quant))
     res = (consistent.view(np.bool_), covered.view(np.bool_))
     return res + (residual,) if want_residual else res
+
+
+# ------------------------------------------------------------------------------ K14: an estimate against a ground truth
+ERROR_RECORD = np.dtype([("n", np.uint32), ("n_nonfinite", np.uint32), ("n_over", np.uint32, 4), ("n_outlier", np.uint32),
+                         ("n_bin", np.uint32, 4), ("max_epe_bits", np.uint32), ("sum_epe", np.float64), ("sum_epe2", np.float64),
+                         ("sum_bin_epe", np.float64, 4)])          # struct ofl_flow_error of include/ofl.h, 96 bytes
+assert ERROR_RECORD.itemsize == 96
+
+
+class FlowErrorStats:
+    """What one record of K14 says: `n` evaluated pixels and `n_nonfinite` pixels left out for a NaN / Inf (or an
+    overflowing) error, `epe` (the mean end-point error), `rmse`, `max`, `over` (the share of pixels above each threshold
+    given), `outlier` (the share that exceeds both outlier bounds: KITTI's Fl) and `bins` ((n, mean epe) per speed bin of the
+    ground truth: one more than edges given).  A mean over zero pixels is nan."""
+
+    __slots__ = ("n", "n_nonfinite", "epe", "rmse", "max", "over", "outlier", "bins")
+
+    def __init__(self, record, n_thresholds=3, n_edges=2):
+        n = int(record["n"])
+        mean = lambda total, count: float(total) / count if count else float('nan')
+        self.n, self.n_nonfinite = n, int(record["n_nonfinite"])
+        self.epe = mean(record["sum_epe"], n)
+        self.rmse = float(np.sqrt(mean(record["sum_epe2"], n)))
+        self.max = float(np.array(record["max_epe_bits"], np.uint32).view(np.float32)) if n else float('nan')
+        self.over = tuple(mean(int(c), n) for c in record["n_over"][:n_thresholds])
+        self.outlier = mean(int(record["n_outlier"]), n)
+        self.bins = tuple((int(c), mean(t, int(c))) for c, t in zip(record["n_bin"][:n_edges + 1], record["sum_bin_epe"][:n_edges + 1]))
+
+    def _key(self):
+        return (self.n, self.n_nonfinite, self.epe, self.rmse, self.max, self.over, self.outlier, self.bins)
+
+    def __eq__(self, other):
+        """equal field by field, nan equal to nan (the statistics of an empty evaluation set)"""
+        return isinstance(other, FlowErrorStats) and repr(self._key()) == repr(other._key())
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "FlowErrorStats(n={}, n_nonfinite={}, epe={!r}, rmse={!r}, max={!r}, over={!r}, outlier={!r}, bins={!r})".format(*self._key())
+
+
+def error_launch(est_vecs, est_mask, gt_vecs, gt_mask, shape, thr, outlier, edges, batch=1, want_map=False, want_outliers=False,
+                 stream=None):
+    """K14 (ofl_flow_error_dev) on `batch` pairs stored back to back; asynchronous.  thr, outlier, edges: from
+    args.error_args; est_mask None: only the ground truth's mask selects.  The workspace comes from the buffer pool and goes
+    back to it on return (one stream).  -> (records, epe_map or None, outlier_map or None): 96 bytes per pair, float32
+    [batch][H][W], uint8 [batch][H][W], all still in HBM."""
+    lib, n = _lib(), batch * shape[0] * shape[1]
+    nbytes = _size_query(lib.ofl_flow_error_workspace_bytes, shape[0], shape[1], batch)
+    work, records = DeviceBuffer(nbytes), DeviceBuffer(batch * ERROR_RECORD.itemsize)
+    epe_map = DeviceBuffer(n * 4) if want_map else None
+    outlier_map = DeviceBuffer(n) if want_outliers else None
+    nat.check(lib.ofl_flow_error_dev(est_vecs.ptr, _ptr(est_mask), gt_vecs.ptr, gt_mask.ptr, shape[0], shape[1], batch,
+                                     thr.ctypes.data, outlier[0], outlier[1], edges.ctypes.data, work.ptr, nbytes, records.ptr,
+                                     _ptr(epe_map), _ptr(outlier_map), stream))
+    return records, epe_map, outlier_map
+
+
+def error_host(est_vecs, est_mask, gt_vecs, gt_mask, thr, outlier, edges, want_map=False, want_outliers=False):
+    """K14 for host arrays through ofl_flow_error (upload, launch, download) -> (record, epe_map or None, outlier_map or
+    None): one ERROR_RECORD element, float32 (H, W), bool (H, W).  est_mask None: only the ground truth's mask selects."""
+    est_vecs, gt_vecs = np.ascontiguousarray(est_vecs, np.float32), np.ascontiguousarray(gt_vecs, np.float32)
+    em, gm = (None if est_mask is None else mask_bytes(est_mask)), mask_bytes(gt_mask)
+    h, w = est_vecs.shape[:2]
+    record = np.zeros(1, ERROR_RECORD)
+    epe_map = np.empty((h, w), np.float32) if want_map else None
+    outlier_map = np.empty((h, w), np.uint8) if want_outliers else None
+    nat.check(_lib().ofl_flow_error(est_vecs.ctypes.data, None if em is None else em.ctypes.data, gt_vecs.ctypes.data, gm.ctypes.data,
+                                    h, w, 1, thr.ctypes.data, outlier[0], outlier[1], edges.ctypes.data, record.ctypes.data,
+                                    None if epe_map is None else epe_map.ctypes.data,
+                                    None if outlier_map is None else outlier_map.ctypes.data))
+    return record[0], epe_map, None if outlier_map is None else outlier_map.view(np.bool_)
 
 
 # ------------------------------------------------------------------------------ K7: visualise, K8: matrix fit
