@@ -761,6 +761,44 @@ int ofl_flow_error(const float *est, const uint8_t *est_mask, const float *gt, c
                    int H, int W, int batch, const float thr[4], float out_abs, float out_rel, const float edges[3],
                    struct ofl_flow_error *records_host, float *epe_map, uint8_t *outlier_map);
 
+/* ------------------------------------------------------------------ K15: masked-out vectors from the nearest valid pixel
+ * The step after a consistency check, a sparse ground truth or a scatter with holes: every pixel takes the vector of the
+ * nearest valid pixel.  Exact integer arithmetic; the reference of the field does not enter.  Per field:
+ *     vecs   float32 [H][W][2]        mask  uint8 [H][W]        valid  uint8 [H][W] or NULL        max_d2  int, -1 = no limit
+ *     source(q)  = (mask[q] & (valid ? valid[q] : 0xFF)) != 0
+ *     d2(p, q)   = (x - qx)^2 + (y - qy)^2                      p = (x, y), q = (qx, qy); an exact integer, < 2^31
+ *     near(p)    = the source that minimises d2(p, .); among equals the smaller qy, then the smaller qx -- the smallest
+ *                  linear index qy * W + qx among the nearest.  A source is its own nearest.
+ *     filled(p)  = a source exists and (max_d2 < 0 or d2(p, near(p)) <= max_d2)
+ *     out_vecs[p] = the 8 bytes of vecs[near(p)] where filled, the 8 bytes of vecs[p] where not: copied, never recomputed
+ *                   (NaN payloads and -0.0 survive)
+ *     out_mask[p] = filled ? 1 : 0
+ *     index[p]    = filled ? qy * W + qx of near(p) : -1              int32, optional
+ *     d2[p]       = filled ? d2(p, near(p)) : 0xFFFFFFFF              uint32, optional
+ * vecs and out_vecs may both be NULL -- the distance transform of a mask alone --, and then index or d2 is required; with
+ * vectors, out_mask, index and d2 are each optional.  `batch` fields lie back to back, offsets are size_t.
+ * Two launches.  The row pass (one workgroup per row; a ballot of 64 source bits per wave and step, the nearest set bit on
+ * either side by clz / ffs, the carry across 64-pixel words by a scan in LDS) writes for every pixel the signed column offset
+ * to the nearest source of its own row -- a tie goes to the smaller column -- as int16 into the workspace; offsets reach
+ * +-32765, -32768 says "no source in this row, or none within max_d2".  The column pass (lanes along x) minimises
+ * (y - y')^2 + off(x, y')^2 over the rows y' by scanning outward, y -+ 1, y -+ 2, ...: a row above wins a tie against
+ * everything found so far, a row below wins only when strictly nearer, and the scan stops at the first k with
+ * k^2 > min(best, max_d2).  Its cost grows with the distance to the nearest source; max_d2 bounds it.  No atomics.
+ *     ofl_fill_workspace_bytes = batch * H * W * 2
+ * workspace: device memory, 2-byte aligned, needs no initialisation.  vecs / out_vecs 8-byte, index / d2 4-byte aligned;
+ * the masks may sit at any address.  Outputs must not alias inputs.
+ * A bad argument -- a NULL mask, only one of vecs / out_vecs, nothing to write (without vectors neither index nor d2),
+ * H or W outside [1, 32766], batch outside [1, 65535], max_d2 < -1, an output that is an input, a missing, short or
+ * misaligned workspace -- returns OFL_E_INVALID with a message before any launch.  The _dev entry is asynchronous; the host
+ * entry takes host pointers, uploads, launches, downloads and synchronises.
+ */
+int ofl_fill_workspace_bytes(int H, int W, int batch, size_t *bytes);
+int ofl_fill_dev(const float *vecs, const uint8_t *mask, const uint8_t *valid, int H, int W, int batch, int max_d2,
+                 void *workspace, size_t workspace_bytes, float *out_vecs, uint8_t *out_mask, int32_t *index, uint32_t *d2,
+                 void *stream);
+int ofl_fill(const float *vecs, const uint8_t *mask, const uint8_t *valid, int H, int W, int batch, int max_d2,
+             float *out_vecs, uint8_t *out_mask, int32_t *index, uint32_t *d2);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

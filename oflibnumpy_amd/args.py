@@ -294,6 +294,41 @@ def error_args(thresholds=None, outlier=None, speed_edges=None):
     return pad(thr, 4), (out[0], out[1]), pad(edges, 3), len(thr), len(edges)
 
 
+# -- masked-out vectors from the nearest valid pixel (K15)
+FILL_MAX_D2 = 2 ** 31 - 1
+
+
+def fill_args(max_dist=None):
+    """Validation of the reach of a fill (K15) on the host before any device work -> max_d2, the largest squared distance in
+    px^2 a vector may be copied over, as a Python int: None -> -1 (no limit), otherwise min(floor(max_dist^2), 2^31 - 1)
+    computed in float64.  A bool or a non-number is a TypeError, a negative or non-finite value a ValueError."""
+    if max_dist is None:
+        return -1
+    if isinstance(max_dist, (bool, np.bool_)) or not isinstance(max_dist, (int, float, np.integer, np.floating)):
+        raise TypeError("Error filling flow: max_dist must be a number or None, got {}".format(type(max_dist).__name__))
+    try:
+        d = np.float64(float(max_dist))
+    except OverflowError:                                   # a Python int beyond the float64 range
+        d = np.float64(1e300 if max_dist > 0 else -1e300)
+    if not np.isfinite(d) or d < 0:
+        raise ValueError("Error filling flow: max_dist must be finite and not negative, got {}".format(max_dist))
+    with np.errstate(over='ignore'):
+        return int(min(np.floor(d * d), np.float64(FILL_MAX_D2)))
+
+
+def fill_valid_array(valid, shape):
+    """A host array given as the `valid` of Flow.fill / fill_flow -> contiguous uint8 (H, W): a NumPy array of bool or uint8
+    with the shape of the flow (TypeError for another type or dtype, ValueError for another shape)."""
+    if not isinstance(valid, np.ndarray):
+        raise TypeError("Error filling flow: valid needs to be a numpy array, got {}".format(type(valid).__name__))
+    if valid.dtype != np.bool_ and valid.dtype != np.uint8:
+        raise TypeError("Error filling flow: valid needs to have dtype bool or uint8, got {}".format(valid.dtype))
+    if valid.shape != (shape[0], shape[1]):
+        raise ValueError("Error filling flow: valid needs to have the shape of the flow, got {} and {}"
+                         .format(valid.shape, (shape[0], shape[1])))
+    return mask_bytes(valid)
+
+
 # -- many-channel float tensors (K12)
 def tensor_dtype(array_dtype, dtype=None):
     """The element type of a tensor -> 'float32', 'float16' or 'bfloat16'.  `array_dtype`: the dtype of the array that holds

@@ -153,6 +153,20 @@ class DeviceFlowBatch:
                                                          thr, out, edges, batch=self.n, want_map=return_map, want_outliers=return_outliers)
         return dev.DeviceFlowError(records, self.n, n_thr, n_edges, epe_map, outlier_map)
 
+    def fill(self, valid=None, max_dist=None, return_index=False, return_d2=False):
+        """self[i].fill(valid[i], ...) for every i in ONE pair of launches of K15 (DeviceFlow.fill): `valid` a uint8
+        DeviceBuffer of n * H * W bytes or None.  -> an unpacked DeviceFlowBatch of the same length, shape and reference,
+        plus, on request, the int32 index and the uint32 squared distance as DeviceBuffers [n][H][W]; an index counts
+        within its own field.  A packed batch is read through its byte masks.  Nothing synchronises."""
+        max_d2 = dev.fill_args(max_dist)
+        valid = dev.fill_valid_buffer(valid, self.n * self.shape[0] * self.shape[1])
+        out_vecs, out_mask, index, d2 = dev.fill_launch(self.vecs, self.mask, valid, self.shape, max_d2, batch=self.n,
+                                                        want_index=bool(return_index), want_d2=bool(return_d2))
+        b = DeviceFlowBatch.__new__(DeviceFlowBatch)
+        b.n, b.shape, b.ref, b.vecs, b.packed, b.bits, b._mask = self.n, self.shape, self.ref, out_vecs, False, None, out_mask
+        extra = ((index,) if return_index else ()) + ((d2,) if return_d2 else ())
+        return (b,) + extra if extra else b
+
     def apply_images(self, images, dtype, channels, shared=False, target_masks=None, shared_masks=False, quant=nat.QUANT_OPENCV):
         """self[i].apply(image_i, target_mask_i, return_valid_area=True) for every i in ONE launch of the gather kernel
         (ref 't' batches; Flow.apply, flow_class.py:604-695 without padding).  `images`: a DeviceBuffer holding [n][H][W][C] of

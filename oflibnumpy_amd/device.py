@@ -31,13 +31,13 @@ from .memory import (_lib, _ptr, _size_query, _Pool, _PinnedPool, empty_cache, D
 from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rules, mask_bytes, _points_array, visualise_args,
                    percentile_ranks, matrix_args, validate_transforms, valid_mask_array, scale_operand, crop_args,
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
-                   consistency_args, error_args)
+                   consistency_args, error_args, fill_args, fill_valid_array)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
                       track_bilinear_launch, track_query_points, track_query_epilogue, gather_tensor, tensor_import_launch,
                       tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
-                      FlowErrorStats)
+                      FlowErrorStats, fill_launch, fill_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -346,6 +346,34 @@ class DeviceFlowError:
         return stats[0] if self.n is None else stats
 
 
+def fill_valid_buffer(valid, n_bytes):
+    """The `valid` of DeviceFlow.fill / DeviceFlowBatch.fill: None, or a uint8 buffer (DeviceBuffer or a view) of at least
+    n_bytes bytes -- e.g. `consistent` out of a consistency check."""
+    if valid is not None and not isinstance(valid, (DeviceBuffer, _BufferView)):
+        raise TypeError("Error filling flow: valid needs to be a DeviceBuffer of uint8 or None, got {}".format(type(valid).__name__))
+    if valid is not None and valid.nbytes < n_bytes:
+        raise ValueError("Error filling flow: valid needs to hold {} bytes, got {}".format(n_bytes, valid.nbytes))
+    return valid
+
+
+def mask_distance(mask_buf, shape, batch=1, max_dist=None):
+    """The distance transform of `batch` uint8 masks [batch][H][W] in HBM (K15 without vectors, include/ofl.h): -> (index,
+    d2) as DeviceBuffers, int32 [batch][H][W] = the linear index qy * W + qx of the nearest non-zero pixel of the same mask
+    (among equals the smallest index), -1 where there is none within max_dist, and uint32 [batch][H][W] = its squared
+    distance, 0xFFFFFFFF where there is none.  Exact integers; asynchronous."""
+    max_d2 = fill_args(max_dist)
+    shape = (int(shape[0]), int(shape[1]))
+    if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+        raise ValueError("Error filling flow: batch must be a positive integer, got {}".format(batch))
+    if not isinstance(mask_buf, (DeviceBuffer, _BufferView)):
+        raise TypeError("Error filling flow: mask needs to be a DeviceBuffer of uint8, got {}".format(type(mask_buf).__name__))
+    if shape[0] < 1 or shape[1] < 1 or mask_buf.nbytes < batch * shape[0] * shape[1]:
+        raise ValueError("Error filling flow: mask needs to hold batch * H * W = {} bytes, got {}"
+                         .format(batch * shape[0] * shape[1], mask_buf.nbytes))
+    _, _, index, d2 = fill_launch(None, mask_buf, None, shape, max_d2, batch=int(batch), want_mask=False, want_index=True, want_d2=True)
+    return index, d2
+
+
 class DeviceFlow:
     """(vecs, mask, ref) resident in HBM.  Buffers are immutable once wrapped."""
 
@@ -636,6 +664,24 @@ class DeviceFlow:
         records, epe_map, outlier_map = error_launch(self.vecs, self.mask if use_est_mask else None, gt.vecs, gt.mask, self.shape,
                                                      thr, out, edges, want_map=return_map, want_outliers=return_outliers)
         return DeviceFlowError(records, None, n_thr, n_edges, epe_map, outlier_map)
+
+    def fill(self, valid=None, max_dist=None, return_index=False, return_d2=False):
+        """The vectors of masked-out pixels replaced by the vector of the nearest valid pixel, in two launches of K15
+        (include/ofl.h) and without leaving HBM.  A pixel is a source where self.mask -- and `valid`, a uint8 DeviceBuffer of
+        H * W bytes such as `consistent` out of DeviceFlow.consistency, if given -- is set; every pixel takes the 8 bytes of
+        the vector of its nearest source (squared Euclidean pixel distance, an exact integer; among equally near sources the
+        one with the smallest linear index), provided that one lies within `max_dist` px (None: no limit; args.fill_args).
+        A pixel that is not filled keeps its vector.  -> a DeviceFlow of the same shape and reference whose mask is 1 where a
+        pixel was filled (sources included); return_index appends the int32 DeviceBuffer [H][W] of the nearest source's
+        linear index (-1: none), return_d2 the uint32 DeviceBuffer [H][W] of its squared distance (0xFFFFFFFF: none).
+        Not a function of the reference.  Nothing synchronises; the inputs are not modified."""
+        max_d2 = fill_args(max_dist)
+        valid = fill_valid_buffer(valid, self.n_px)
+        out_vecs, out_mask, index, d2 = fill_launch(self.vecs, self.mask, valid, self.shape, max_d2,
+                                                    want_index=bool(return_index), want_d2=bool(return_d2))
+        res = DeviceFlow(out_vecs, out_mask, self.shape, self.ref)
+        extra = ((index,) if return_index else ()) + ((d2,) if return_d2 else ())
+        return (res,) + extra if extra else res
 
     # -- warping
     def apply(self, target, consider_mask=True, quant=nat.QUANT_OPENCV, target_mask=None):

@@ -480,6 +480,27 @@ class Flow(object):
         stats = dev.FlowErrorStats(record, n_thr, n_edges)
         return (stats, epe_map) if return_map else stats
 
+    def fill(self, valid: np.ndarray = None, max_dist: float = None, return_index: bool = None, return_d2: bool = None):
+        """This flow with the vectors of masked-out pixels replaced by the vector of the nearest valid pixel: a pixel is a
+        source where the mask -- and `valid`, a bool or uint8 (H, W) array, if given -- is set, every pixel takes the vector
+        of its nearest source (Euclidean pixel distance; among equally near sources the first in row-major order) if that
+        one lies within `max_dist` px (None: no limit), and keeps its own otherwise.  -> a Flow of the same reference whose
+        mask is True where a pixel was filled; with `return_index` also the int32 (H, W) linear index of the nearest source
+        (-1: none), with `return_d2` the uint32 (H, W) squared distance (0xFFFFFFFF: none).  Not a function of the
+        reference; the definition is DeviceFlow.fill's.  One upload, two launches, one download."""
+        max_d2 = dev.fill_args(max_dist)
+        return_index = False if return_index is None else return_index
+        return_d2 = False if return_d2 is None else return_d2
+        if not isinstance(return_index, bool):
+            raise TypeError("Error filling flow: Return_index needs to be a boolean")
+        if not isinstance(return_d2, bool):
+            raise TypeError("Error filling flow: Return_d2 needs to be a boolean")
+        valid = None if valid is None else dev.fill_valid_array(valid, self.shape)
+        vecs, mask, index, d2 = dev.fill_host(self._vecs, self._mask, valid, max_d2, return_index, return_d2)
+        res = Flow(vecs, self._ref, mask)
+        extra = ((index,) if return_index else ()) + ((d2,) if return_d2 else ())
+        return (res,) + extra if extra else res
+
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
         """flow_1 (+) flow_2 = flow_3: mode k returns flow_k from the other two (`self` comes first in
         that formula among the two given).  Reference flow_class.py:1247-1424."""

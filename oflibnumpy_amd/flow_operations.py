@@ -10,7 +10,7 @@ from .flow_class import Flow
 
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
-           'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error']
+           'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -73,3 +73,11 @@ def flow_error(est: nd, gt: nd, ref: str, gt_mask: nd = None, thresholds=None, o
     `gt_mask` (None: all valid) -- Flow.error; with `return_map` also the float32 (H, W) end-point error."""
     return Flow(est, ref).error(Flow(gt, ref, gt_mask), thresholds=thresholds, outlier=outlier, speed_edges=speed_edges,
                                 return_map=return_map)
+
+
+def fill_flow(flow: nd, mask: nd, valid: nd = None, max_dist: float = None) -> tuple:
+    """(vecs, mask) of the flow array `flow` with the vectors outside `mask` (and outside `valid`, if given) replaced by the
+    vector of the nearest pixel inside, within `max_dist` px (None: no limit) -- Flow.fill; the returned bool mask is True
+    where a pixel was filled.  Not a function of the reference."""
+    filled = Flow(flow, 't', mask).fill(valid=valid, max_dist=max_dist)
+    return filled.vecs, filled.mask

@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency and K14 flow error.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error and K15 fill.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -184,6 +184,38 @@ def error_host(est_vecs, est_mask, gt_vecs, gt_mask, thr, outlier, edges, want_m
                                     None if epe_map is None else epe_map.ctypes.data,
                                     None if outlier_map is None else outlier_map.ctypes.data))
     return record[0], epe_map, None if outlier_map is None else outlier_map.view(np.bool_)
+
+
+# ------------------------------------------------------------------------------ K15: fill from the nearest valid pixel
+def fill_launch(vecs, mask, valid, shape, max_d2, batch=1, want_mask=True, want_index=False, want_d2=False, stream=None):
+    """K15 (ofl_fill_dev) on `batch` fields stored back to back; asynchronous.  max_d2: from args.fill_args; valid None: the
+    mask alone selects the sources; vecs None: the distance transform of the mask alone (want_index or want_d2 needed).  The
+    workspace comes from the buffer pool and goes back to it on return (one stream).  -> (out_vecs or None, out_mask or None,
+    index or None, d2 or None): float32 [batch][H][W][2], uint8, int32 and uint32 [batch][H][W], all still in HBM."""
+    lib, n = _lib(), batch * shape[0] * shape[1]
+    nbytes = _size_query(lib.ofl_fill_workspace_bytes, shape[0], shape[1], batch)
+    work = DeviceBuffer(nbytes)
+    out_vecs = DeviceBuffer(n * 8) if vecs is not None else None
+    out_mask = DeviceBuffer(n) if want_mask else None
+    index = DeviceBuffer(n * 4) if want_index else None
+    d2 = DeviceBuffer(n * 4) if want_d2 else None
+    nat.check(lib.ofl_fill_dev(_ptr(vecs), mask.ptr, _ptr(valid), shape[0], shape[1], batch, max_d2, work.ptr, nbytes,
+                               _ptr(out_vecs), _ptr(out_mask), _ptr(index), _ptr(d2), stream))
+    return out_vecs, out_mask, index, d2
+
+
+def fill_host(vecs, mask, valid, max_d2, want_index=False, want_d2=False):
+    """K15 for host arrays through ofl_fill (upload, launch, download) -> (vecs float32 (H, W, 2), mask bool (H, W), index
+    int32 (H, W) or None, d2 uint32 (H, W) or None).  valid: contiguous uint8 (H, W) or None."""
+    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(mask)
+    h, w = vecs.shape[:2]
+    out_vecs, out_mask = np.empty((h, w, 2), np.float32), np.empty((h, w), np.uint8)
+    index = np.empty((h, w), np.int32) if want_index else None
+    d2 = np.empty((h, w), np.uint32) if want_d2 else None
+    nat.check(_lib().ofl_fill(vecs.ctypes.data, m.ctypes.data, None if valid is None else valid.ctypes.data, h, w, 1, max_d2,
+                              out_vecs.ctypes.data, out_mask.ctypes.data, None if index is None else index.ctypes.data,
+                              None if d2 is None else d2.ctypes.data))
+    return out_vecs, out_mask.view(np.bool_), index, d2
 
 
 # ------------------------------------------------------------------------------ K7: visualise, K8: matrix fit
