@@ -173,7 +173,7 @@ void axpy_kernel(const float *__restrict__ a, const uint8_t *__restrict__ ma,
         for (size_t i = tail0 + threadIdx.x; i < n_px; i += blockDim.x) {
             for (int c = 0; c < 2; ++c)
                 out[2 * i + c] = b ? __fadd_rn(a[2 * i + c], __fmul_rn(alpha, b[2 * i + c])) : __fmul_rn(alpha, a[2 * i + c]);
-            if (mout) mout[i] = (uint8_t)(ma[i] & (mb ? mb[i] : 1));
+            if (mout) mout[i] = mb ? (uint8_t)(ma[i] & mb[i]) : ma[i];      // bytes, as the word loop above: ma alone stays ma
         }
     }
 }
