@@ -13,7 +13,9 @@
  *     library's default stream); they enqueue work and return without synchronising.
  *   - host entry points (no suffix) take caller-owned, C-contiguous HOST buffers, do
  *     H2D -> kernel -> D2H on the default stream and return when the result is in host memory.
- *     Nothing is retained after return.
+ *     Each call stages its arrays in ONE device allocation (every array on a 16-byte boundary, so the
+ *     _dev entry behind it takes its aligned kernel route) and frees it before it returns, after a
+ *     failure too: nothing is retained and nothing is left queued.
  *   - layouts: flow vecs float32 [H][W][2] (channel 0 = x / horizontal, 1 = y / vertical),
  *     masks uint8 [H][W] with values 0/1, images [H][W][C] C-contiguous.
  *   - one process drives one GPU (ofl_init(device) once per process); the library is re-entrant

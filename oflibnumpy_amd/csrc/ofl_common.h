@@ -23,6 +23,9 @@ int  need_device();                                  // OFL_OK or OFL_E_NODEVICE
 
 inline hipStream_t stream_of(void *s) { return s ? (hipStream_t)s : rt().stream; }
 
+// `p` on an `a`-byte boundary (a power of two); a NULL pointer, an absent optional argument, counts as aligned
+inline bool host_aligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
+
 }  // namespace ofl
 
 #define OFL_HIP(call)                                                      \

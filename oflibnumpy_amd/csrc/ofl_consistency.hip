@@ -24,6 +24,7 @@
 // per counter, then one lane issues at most one atomicAdd per counter (integer adds: the order cannot change the result);
 // without COUNTS the kernel has neither LDS nor atomics.
 #include "ofl_common.h"
+#include "ofl_host_stage.h"
 
 #pragma clang fp contract(off)
 
@@ -131,8 +132,6 @@ void consistency_kernel(const CArgs a)
     }
 }
 
-inline bool host_aligned(const void *p, unsigned n) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & (n - 1u)) == 0; }
-
 int check_consistency_args(const char *who, const void *f, const void *fm, const void *b, const void *bm, int sign, int H, int W,
                            int batch, float alpha, float beta, const void *consistent, int quant)
 {
@@ -186,39 +185,16 @@ int ofl_consistency(const float *f, const uint8_t *fm, const float *b, const uin
 {
     OFL_TRY(need_device());
     OFL_TRY(check_consistency_args("ofl_consistency", f, fm, b, bm, sign, H, W, batch, alpha, beta, consistent, quant));
-    const size_t n = (size_t)batch * H * W, nc = (size_t)batch * 2 * sizeof(uint32_t);
-    hipStream_t s = rt().stream;
-    // one allocation: f | b | residual | counts | fm | bm | consistent | covered, the 8-byte parts first
-    const size_t o_b = n * 8, o_res = o_b + n * 8, o_cnt = o_res + n * 4, o_fm = o_cnt + ((nc + 15) & ~(size_t)15), o_bm = o_fm + n,
-                 o_con = o_bm + n + (n & 1), o_cov = o_con + n + (n & 1), total = o_cov + n;
-    char *d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d), total);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    int rc = OFL_OK;
-    do {
-        if ((e = hipMemcpyAsync(d, f, n * 8, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d + o_b, b, n * 8, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d + o_fm, fm, n, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d + o_bm, bm, n, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if (counts_host && (e = hipMemsetAsync(d + o_cnt, 0, nc, s)) != hipSuccess) break;
-        rc = ofl_consistency_dev(reinterpret_cast<const float *>(d), reinterpret_cast<const uint8_t *>(d + o_fm),
-                                 reinterpret_cast<const float *>(d + o_b), reinterpret_cast<const uint8_t *>(d + o_bm), sign, H, W, batch,
-                                 alpha, beta, reinterpret_cast<uint8_t *>(d + o_con), covered ? reinterpret_cast<uint8_t *>(d + o_cov) : nullptr,
-                                 residual ? reinterpret_cast<float *>(d + o_res) : nullptr,
-                                 counts_host ? reinterpret_cast<uint32_t *>(d + o_cnt) : nullptr, quant, s);
-        if (rc != OFL_OK) break;
-        if ((e = hipMemcpyAsync(consistent, d + o_con, n, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if (covered && (e = hipMemcpyAsync(covered, d + o_cov, n, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if (residual && (e = hipMemcpyAsync(residual, d + o_res, n * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if (counts_host && (e = hipMemcpyAsync(counts_host, d + o_cnt, nc, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        e = hipStreamSynchronize(s);
-    } while (0);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(s);
-        rc = hip_fail(e, "ofl_consistency");
-    }
-    (void)hipFree(d);
-    return rc;
+    const size_t n = (size_t)batch * H * W;
+    HostStage st("ofl_consistency");
+    auto df = st.in(f, n * 2), db = st.in(b, n * 2);
+    auto dfm = st.in(fm, n), dbm = st.in(bm, n);
+    auto con = st.out(consistent, n), cov = st.out(covered, n);
+    auto res = st.out(residual, n);
+    auto cnt = st.out(counts_host, (size_t)batch * 2, true);      // the launch adds to the counts
+    OFL_TRY(st.upload());
+    OFL_TRY(ofl_consistency_dev(df, dfm, db, dbm, sign, H, W, batch, alpha, beta, con, cov, res, cnt, quant, st.stream()));
+    return st.download();
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 // waves in order.  Longest chain of additions: 16 + 6 + 3 + ceil(chunks / 256) + 6 + 3.
 #include <stddef.h>
 #include "ofl_common.h"
+#include "ofl_host_stage.h"
 
 #pragma clang fp contract(off)
 
@@ -281,8 +282,6 @@ void launch_error(int maps, const EArgs &a, dim3 grid, hipStream_t s)
     }
 }
 
-inline bool host_aligned(const void *p, unsigned n) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & (n - 1u)) == 0; }
-
 inline uint32_t chunks_of(int H, int W) { return (uint32_t)(((int64_t)H * W + kChunk - 1) / kChunk); }
 
 int check_error_args(const char *who, const void *est, const void *gt, const void *gt_mask, int H, int W, int batch,
@@ -358,38 +357,17 @@ int ofl_flow_error(const float *est, const uint8_t *est_mask, const float *gt, c
 {
     OFL_TRY(need_device());
     OFL_TRY(check_error_args("ofl_flow_error", est, gt, gt_mask, H, W, batch, thr, out_abs, out_rel, edges, records_host));
-    const size_t n = (size_t)batch * H * W, wsb = (size_t)batch * chunks_of(H, W) * kPartialBytes, nr = (size_t)batch * sizeof(struct ofl_flow_error);
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    hipStream_t s = rt().stream;
-    // one allocation: est | gt | epe_map | workspace | records | est_mask | gt_mask | outlier_map, each on a 16-byte boundary
-    const size_t o_gt = up16(n * 8), o_epe = o_gt + up16(n * 8), o_ws = o_epe + up16(n * 4), o_rec = o_ws + up16(wsb),
-                 o_em = o_rec + up16(nr), o_gm = o_em + up16(n), o_out = o_gm + up16(n), total = o_out + up16(n);
-    char *d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d), total);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    int rc = OFL_OK;
-    do {
-        if ((e = hipMemcpyAsync(d, est, n * 8, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d + o_gt, gt, n * 8, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if (est_mask && (e = hipMemcpyAsync(d + o_em, est_mask, n, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d + o_gm, gt_mask, n, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        rc = ofl_flow_error_dev(reinterpret_cast<const float *>(d), est_mask ? reinterpret_cast<const uint8_t *>(d + o_em) : nullptr,
-                                reinterpret_cast<const float *>(d + o_gt), reinterpret_cast<const uint8_t *>(d + o_gm), H, W, batch,
-                                thr, out_abs, out_rel, edges, d + o_ws, wsb, reinterpret_cast<struct ofl_flow_error *>(d + o_rec),
-                                epe_map ? reinterpret_cast<float *>(d + o_epe) : nullptr,
-                                outlier_map ? reinterpret_cast<uint8_t *>(d + o_out) : nullptr, s);
-        if (rc != OFL_OK) break;
-        if ((e = hipMemcpyAsync(records_host, d + o_rec, nr, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if (epe_map && (e = hipMemcpyAsync(epe_map, d + o_epe, n * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if (outlier_map && (e = hipMemcpyAsync(outlier_map, d + o_out, n, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        e = hipStreamSynchronize(s);
-    } while (0);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(s);
-        rc = hip_fail(e, "ofl_flow_error");
-    }
-    (void)hipFree(d);
-    return rc;
+    const size_t n = (size_t)batch * H * W, wsb = (size_t)batch * chunks_of(H, W) * kPartialBytes;
+    HostStage st("ofl_flow_error");
+    auto de = st.in(est, n * 2), dg = st.in(gt, n * 2);
+    auto dem = st.in(est_mask, n), dgm = st.in(gt_mask, n);
+    auto ws = st.scratch<char>(wsb);
+    auto rec = st.out(records_host, (size_t)batch);
+    auto epe = st.out(epe_map, n);
+    auto om = st.out(outlier_map, n);
+    OFL_TRY(st.upload());
+    OFL_TRY(ofl_flow_error_dev(de, dem, dg, dgm, H, W, batch, thr, out_abs, out_rel, edges, ws, wsb, rec, epe, om, st.stream()));
+    return st.download();
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 // row pass (with and without `valid`).
 #include <stddef.h>
 #include "ofl_common.h"
+#include "ofl_host_stage.h"
 
 using namespace ofl;
 
@@ -192,8 +193,6 @@ void launch_col_plain(int outs, const FArgs &a, dim3 grid, hipStream_t s)
     }
 }
 
-inline bool host_aligned(const void *p, unsigned n) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & (n - 1u)) == 0; }
-
 inline bool sizes_ok(int H, int W, int batch) { return H >= 1 && W >= 1 && H <= kMaxDim && W <= kMaxDim && batch >= 1 && batch <= 65535; }
 
 int check_fill_args(const char *who, const void *vecs, const void *mask, const void *valid, int H, int W, int batch, int max_d2,
@@ -266,36 +265,17 @@ int ofl_fill(const float *vecs, const uint8_t *mask, const uint8_t *valid, int H
     OFL_TRY(need_device());
     OFL_TRY(check_fill_args("ofl_fill", vecs, mask, valid, H, W, batch, max_d2, out_vecs, out_mask, index, d2));
     const size_t n = (size_t)batch * H * W, wsb = n * sizeof(int16_t);
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    hipStream_t s = rt().stream;
-    // one allocation: vecs | out_vecs | index | d2 | workspace | mask | valid | out_mask, each on a 16-byte boundary
-    const size_t o_ov = up16(n * 8), o_ix = o_ov + up16(n * 8), o_d2 = o_ix + up16(n * 4), o_ws = o_d2 + up16(n * 4),
-                 o_m = o_ws + up16(wsb), o_v = o_m + up16(n), o_om = o_v + up16(n), total = o_om + up16(n);
-    char *d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d), total);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    int rc = OFL_OK;
-    do {
-        if (vecs && (e = hipMemcpyAsync(d, vecs, n * 8, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d + o_m, mask, n, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if (valid && (e = hipMemcpyAsync(d + o_v, valid, n, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        rc = ofl_fill_dev(vecs ? reinterpret_cast<const float *>(d) : nullptr, reinterpret_cast<const uint8_t *>(d + o_m),
-                          valid ? reinterpret_cast<const uint8_t *>(d + o_v) : nullptr, H, W, batch, max_d2, d + o_ws, wsb,
-                          vecs ? reinterpret_cast<float *>(d + o_ov) : nullptr, out_mask ? reinterpret_cast<uint8_t *>(d + o_om) : nullptr,
-                          index ? reinterpret_cast<int32_t *>(d + o_ix) : nullptr, d2 ? reinterpret_cast<uint32_t *>(d + o_d2) : nullptr, s);
-        if (rc != OFL_OK) break;
-        if (vecs && (e = hipMemcpyAsync(out_vecs, d + o_ov, n * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if (out_mask && (e = hipMemcpyAsync(out_mask, d + o_om, n, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if (index && (e = hipMemcpyAsync(index, d + o_ix, n * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if (d2 && (e = hipMemcpyAsync(d2, d + o_d2, n * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        e = hipStreamSynchronize(s);
-    } while (0);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(s);
-        rc = hip_fail(e, "ofl_fill");
-    }
-    (void)hipFree(d);
-    return rc;
+    HostStage st("ofl_fill");
+    auto dv = st.in(vecs, n * 2);
+    auto dm = st.in(mask, n), dva = st.in(valid, n);
+    auto ws = st.scratch<char>(wsb);
+    auto ov = st.out(out_vecs, n * 2);
+    auto om = st.out(out_mask, n);
+    auto ix = st.out(index, n);
+    auto dd = st.out(d2, n);
+    OFL_TRY(st.upload());
+    OFL_TRY(ofl_fill_dev(dv, dm, dva, H, W, batch, max_d2, ws, wsb, ov, om, ix, dd, st.stream()));
+    return st.download();
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 // Numerics follow oracle/ofl_oracle.c operation for operation (contraction disabled) so that the
 // float results and the validity masks are bit-identical to the CPU restatement.
 #include "ofl_common.h"
+#include "ofl_host_stage.h"
 #include "ofl_compose3_route.h"
 #include <type_traits>
 
@@ -1509,17 +1510,6 @@ int check_dims(const char *who, int H, int W)
     return OFL_OK;
 }
 
-// scoped device buffer for the host-pointer entry points
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes)
-    {
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-        return e == hipSuccess ? OFL_OK : hip_fail(e, "hipMalloc");
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -1624,36 +1614,23 @@ int ofl_compose3(const float *fa, const uint8_t *ma, const float *fb, const uint
     OFL_TRY(check_dims("ofl_compose3", H, W));
     if (batch <= 0) return fail(OFL_E_INVALID, "ofl_compose3: batch must be >= 1");
     if (!fa || !ma || !fb || !mb || !out || !mout) return fail(OFL_E_INVALID, "ofl_compose3: NULL pointer");
-    const size_t n = (size_t)batch * H * W;
-    hipStream_t s = rt().stream;
-    DevBuf dfa, dma, dfb, dmb, dout, dmout, dst;
-    OFL_TRY(dfa.alloc(n * 8)); OFL_TRY(dma.alloc(n)); OFL_TRY(dfb.alloc(n * 8)); OFL_TRY(dmb.alloc(n));
-    OFL_TRY(dout.alloc(n * 8)); OFL_TRY(dmout.alloc(n)); OFL_TRY(dst.alloc((size_t)batch * 8 * 4));
-    OFL_HIP(hipMemcpyAsync(dfa.p, fa, n * 8, hipMemcpyHostToDevice, s));
-    OFL_HIP(hipMemcpyAsync(dma.p, ma, n, hipMemcpyHostToDevice, s));
-    OFL_HIP(hipMemcpyAsync(dfb.p, fb, n * 8, hipMemcpyHostToDevice, s));
-    OFL_HIP(hipMemcpyAsync(dmb.p, mb, n, hipMemcpyHostToDevice, s));
-    OFL_HIP(hipMemsetAsync(dst.p, 0, (size_t)batch * 8 * 4, s));
-    OFL_TRY(ofl_compose3_dev((const float *)dfa.p, (const uint8_t *)dma.p, (const float *)dfb.p,
-                             (const uint8_t *)dmb.p, sign, H, W, batch, (float *)dout.p, (uint8_t *)dmout.p,
-                             nullptr, quant, s));
-    OFL_HIP(hipMemcpyAsync(out, dout.p, n * 8, hipMemcpyDeviceToHost, s));
-    OFL_HIP(hipMemcpyAsync(mout, dmout.p, n, hipMemcpyDeviceToHost, s));
-    // exact predicates for the host caller: one pass of the statistics kernel per field (the fused
+    const size_t n = (size_t)batch * H * W, hw = (size_t)H * W;
+    HostStage st("ofl_compose3");
+    auto dfa = st.in(fa, n * 2), dfb = st.in(fb, n * 2);
+    auto dma = st.in(ma, n), dmb = st.in(mb, n);
+    auto dout = st.out(out, n * 2);
+    auto dmout = st.out(mout, n);
+    auto dst = st.out(stats_host, (size_t)batch * 2);
+    OFL_TRY(st.upload());
+    OFL_TRY(ofl_compose3_dev(dfa, dma, dfb, dmb, sign, H, W, batch, dout, dmout, nullptr, quant, st.stream()));
+    // exact predicates for the host caller: one pass of the statistics kernel per field and operand (the fused
     // launch above only certifies "fa is not zero" from the vectors it happened to gather)
     for (int b = 0; stats_host && b < batch; ++b) {
-        const size_t hw = (size_t)H * W;
-        uint32_t bits[2] = { 0, 0 };
-        for (int k = 0; k < 2; ++k) {
-            const float *f = (const float *)(k == 0 ? dfa.p : dfb.p) + (size_t)b * hw * 2;
-            const uint8_t *m = (const uint8_t *)(k == 0 ? dma.p : dmb.p) + (size_t)b * hw;
-            OFL_TRY(ofl_flow_stats_dev(f, m, hw, 1e-3f, (uint32_t *)dst.p, s));
-            OFL_HIP(hipMemcpyAsync(&bits[k], dst.p, 4, hipMemcpyDeviceToHost, s));
-            OFL_HIP(hipStreamSynchronize(s));
-        }
-        stats_host[2 * b] = bits[0] & 15u; stats_host[2 * b + 1] = bits[1] & 15u;
+        OFL_TRY(ofl_flow_stats_dev(dfa + (size_t)b * hw * 2, dma + (size_t)b * hw, hw, 1e-3f, dst + 2 * b, st.stream()));
+        OFL_TRY(ofl_flow_stats_dev(dfb + (size_t)b * hw * 2, dmb + (size_t)b * hw, hw, 1e-3f, dst + 2 * b + 1, st.stream()));
     }
-    OFL_HIP(hipStreamSynchronize(s));
+    OFL_TRY(st.download());
+    for (int k = 0; stats_host && k < 2 * batch; ++k) stats_host[k] &= 15u;
     return OFL_OK;
 }
 
@@ -1736,21 +1713,16 @@ int ofl_gather_bilinear(const void *src, int dtype, int C, int H, int W,
     if (!src || !flow || !dst) return fail(OFL_E_INVALID, "ofl_gather_bilinear: NULL pointer");
     if (fH <= 0 || fW <= 0) return fail(OFL_E_INVALID, "ofl_gather_bilinear: bad flow shape");
     const size_t n = (size_t)H * W, nf = (size_t)fH * fW;
-    hipStream_t s = rt().stream;
-    DevBuf dsrc, dflow, dsm, dfm, ddst, dval;
-    OFL_TRY(dsrc.alloc(n * C * es)); OFL_TRY(dflow.alloc(nf * 8)); OFL_TRY(ddst.alloc(n * C * es));
-    OFL_HIP(hipMemcpyAsync(dsrc.p, src, n * C * es, hipMemcpyHostToDevice, s));
-    OFL_HIP(hipMemcpyAsync(dflow.p, flow, nf * 8, hipMemcpyHostToDevice, s));
-    if (smask) { OFL_TRY(dsm.alloc(n)); OFL_HIP(hipMemcpyAsync(dsm.p, smask, n, hipMemcpyHostToDevice, s)); }
-    if (fmask) { OFL_TRY(dfm.alloc(nf)); OFL_HIP(hipMemcpyAsync(dfm.p, fmask, nf, hipMemcpyHostToDevice, s)); }
-    if (valid) OFL_TRY(dval.alloc(n));
-    OFL_TRY(ofl_gather_bilinear_dev(dsrc.p, dtype, C, H, W, (const float *)dflow.p, fH, fW, pad_top, pad_left, sign,
-                                    (const uint8_t *)dsm.p, (const uint8_t *)dfm.p, ddst.p, (uint8_t *)dval.p,
-                                    quant, arith, rule, s));
-    OFL_HIP(hipMemcpyAsync(dst, ddst.p, n * C * es, hipMemcpyDeviceToHost, s));
-    if (valid) OFL_HIP(hipMemcpyAsync(valid, dval.p, n, hipMemcpyDeviceToHost, s));
-    OFL_HIP(hipStreamSynchronize(s));
-    return OFL_OK;
+    HostStage st("ofl_gather_bilinear");
+    auto dsrc = st.in(src, n * C * es);
+    auto dflow = st.in(flow, nf * 2);
+    auto dsm = st.in(smask, n), dfm = st.in(fmask, nf);
+    auto ddst = st.out(dst, n * C * es);
+    auto dval = st.out(valid, n);
+    OFL_TRY(st.upload());
+    OFL_TRY(ofl_gather_bilinear_dev(dsrc, dtype, C, H, W, dflow, fH, fW, pad_top, pad_left, sign, dsm, dfm, ddst, dval,
+                                    quant, arith, rule, st.stream()));
+    return st.download();
 }
 
 }  // extern "C"

@@ -294,8 +294,6 @@ int launch_permute_dir(const void *src, void *dst, int C, int H, int W, int64_t 
                   : launch_permute<T, false>(src, dst, C, H, W, s_c, s_h, s_w, s);
 }
 
-inline bool host_aligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
-
 const unsigned kElemBytes[4] = { 2, 2, 4, 8 };          // OFL_EL_F16, OFL_EL_BF16, OFL_EL_F32, OFL_EL_F64
 
 }  // namespace

@@ -4,6 +4,7 @@
 // HBM-bound: every source line that is touched is read once (neighbouring output pixels share taps through
 // the vector L1 / L2), every output pixel is written once with 16-byte stores.
 #include "ofl_common.h"
+#include "ofl_host_stage.h"
 #include <stdlib.h>
 
 #pragma clang fp contract(off)
@@ -243,29 +244,14 @@ int ofl_resize_flow(const float *vecs, const uint8_t *mask, int H, int W, int Ho
     if (!vecs || !out) return fail(OFL_E_INVALID, "ofl_resize_flow: NULL pointer");
     if (H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return fail(OFL_E_INVALID, "ofl_resize_flow: sizes must be positive");
     const size_t n_in = (size_t)H * W, n_out = (size_t)Ho * Wo;
-    hipStream_t s = rt().stream;
-    void *dv = nullptr, *dm = nullptr, *dout = nullptr, *dmo = nullptr;
-    int rc = OFL_OK;
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = hipMalloc(&dv, n_in * 8)) != hipSuccess) break;
-        if ((e = hipMalloc(&dout, n_out * 8 + 16)) != hipSuccess) break;
-        if (mask && (e = hipMalloc(&dm, n_in)) != hipSuccess) break;
-        if (mask && (e = hipMalloc(&dmo, n_out + 16)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(dv, vecs, n_in * 8, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if (mask && (e = hipMemcpyAsync(dm, mask, n_in, hipMemcpyHostToDevice, s)) != hipSuccess) break;
-        if ((rc = ofl_resize_flow_dev((const float *)dv, (const uint8_t *)dm, H, W, Ho, Wo, scale_y, scale_x, mul_u, mul_v,
-                                      (float *)dout, (uint8_t *)dmo, s)) != OFL_OK) break;
-        if ((e = hipMemcpyAsync(out, dout, n_out * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        if (mask && (e = hipMemcpyAsync(mout, dmo, n_out, hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-        e = hipStreamSynchronize(s);
-    } while (0);
-    if (e != hipSuccess) rc = hip_fail(e, "ofl_resize_flow");
-    if (dv) (void)hipFree(dv);
-    if (dm) (void)hipFree(dm);
-    if (dout) (void)hipFree(dout);
-    if (dmo) (void)hipFree(dmo);
-    return rc;
+    HostStage st("ofl_resize_flow");
+    auto dv = st.in(vecs, n_in * 2);
+    auto dm = st.in(mask, n_in);
+    auto dout = st.out(out, n_out * 2);
+    auto dmo = st.out(mask ? mout : nullptr, n_out);      // without a mask, mout is not written
+    OFL_TRY(st.upload());
+    OFL_TRY(ofl_resize_flow_dev(dv, dm, H, W, Ho, Wo, scale_y, scale_x, mul_u, mul_v, dout, dmo, st.stream()));
+    return st.download();
 }
 
 }  // extern "C"

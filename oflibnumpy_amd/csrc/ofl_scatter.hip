@@ -15,6 +15,7 @@
 // There is no approximate path: wherever SciPy's triangulation is unique the interpolant is the same function
 // (tests/test_gpu_scatter*.py against outputs of the real reference).
 #include "ofl_common.h"
+#include "ofl_host_stage.h"
 #include "ofl_scatter_dev.h"
 #include <algorithm>
 
@@ -249,35 +250,19 @@ int ofl_scatter_linear(const float *flow, int sign, int point_precision, const u
 {
     OFL_TRY(need_device());
     if (H <= 0 || W <= 0) return fail(OFL_E_INVALID, "ofl_scatter_linear: bad shape");
-    const size_t n = (size_t)H * W;
-    hipStream_t s = rt().stream;
+    const size_t n = (size_t)H * W, nv = C > 0 ? (size_t)C * n : 0;
     size_t wsb = 0;
     OFL_TRY(ofl_scatter_workspace_bytes(H, W, C, &wsb));
-    void *bufs[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    const void *src[6] = { flow, pmask, vals, vmask, query, nullptr };
-    const size_t sz[8] = { n * 8, pmask ? n : 0, (size_t)C * n * 4, vmask ? n : 0, query ? n * 8 : 0,
-                           (size_t)C * n * 4, valid ? n : 0, wsb };
-    int rc = OFL_OK;
+    HostStage st("ofl_scatter_linear");
+    auto df = st.in(flow, n * 2), dv = st.in(C > 0 ? vals : nullptr, nv), dq = st.in(query, n * 2);
+    auto dpm = st.in(pmask, n), dvm = st.in(vmask, n);
+    auto dout = st.out(C > 0 ? out : nullptr, nv);
+    auto dval = st.out(valid, n);
+    auto ws = st.scratch<char>(wsb);
+    OFL_TRY(st.upload());
     uint64_t info[3];
-    do {
-        hipError_t e = hipSuccess;
-        for (int k = 0; k < 8 && e == hipSuccess; ++k)
-            if (sz[k]) e = hipMalloc(&bufs[k], sz[k]);
-        if (e != hipSuccess) { rc = hip_fail(e, "hipMalloc"); break; }
-        for (int k = 0; k < 5 && e == hipSuccess; ++k)
-            if (sz[k] && src[k]) e = hipMemcpyAsync(bufs[k], src[k], sz[k], hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) { rc = hip_fail(e, "H2D"); break; }
-        rc = ofl_scatter_linear_dev((const float *)bufs[0], sign, point_precision, (const uint8_t *)bufs[1], (const float *)bufs[2], C,
-                                    (const uint8_t *)bufs[3], H, W, (const float *)bufs[4], (float *)bufs[5],
-                                    (uint8_t *)bufs[6], valid_rule, bufs[7], wsb, info, s);
-        if (rc != OFL_OK) break;
-        if (sz[5] && (e = hipMemcpyAsync(out, bufs[5], sz[5], hipMemcpyDeviceToHost, s)) != hipSuccess) { rc = hip_fail(e, "D2H"); break; }
-        if (sz[6] && (e = hipMemcpyAsync(valid, bufs[6], sz[6], hipMemcpyDeviceToHost, s)) != hipSuccess) { rc = hip_fail(e, "D2H"); break; }
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) { rc = hip_fail(e, "sync"); break; }
-    } while (0);
-    (void)hipStreamSynchronize(s);
-    for (int k = 0; k < 8; ++k) if (bufs[k]) (void)hipFree(bufs[k]);
-    return rc;
+    OFL_TRY(ofl_scatter_linear_dev(df, sign, point_precision, dpm, dv, C, dvm, H, W, dq, dout, dval, valid_rule, ws, wsb, info, st.stream()));
+    return st.download();
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // ofl_stats.hip -- K4 zero-flow / finite statistics and K5 element-wise epilogues (gfx950).
 // Pure streaming kernels: 16-byte loads per lane, grid-stride over at most 2048 workgroups.
 #include "ofl_common.h"
+#include "ofl_host_stage.h"
 #include <stdlib.h>
 #include <algorithm>
 
@@ -271,22 +272,13 @@ int ofl_flow_stats(const float *flow, const uint8_t *mask, size_t n_px, float th
 {
     OFL_TRY(need_device());
     if (!flow || !stats_host) return fail(OFL_E_INVALID, "ofl_flow_stats: NULL pointer");
-    hipStream_t s = rt().stream;
-    void *df = nullptr, *dm = nullptr, *ds = nullptr;
-    int rc = OFL_OK;
-    hipError_t e;
-    if ((e = hipMalloc(&df, n_px * 8 + 16)) != hipSuccess) return hip_fail(e, "hipMalloc");
-    if ((e = hipMalloc(&ds, 16)) != hipSuccess) { (void)hipFree(df); return hip_fail(e, "hipMalloc"); }
-    if (mask && (e = hipMalloc(&dm, n_px + 16)) != hipSuccess) { (void)hipFree(df); (void)hipFree(ds); return hip_fail(e, "hipMalloc"); }
-    do {
-        if ((e = hipMemcpyAsync(df, flow, n_px * 8, hipMemcpyHostToDevice, s)) != hipSuccess) { rc = hip_fail(e, "H2D"); break; }
-        if (mask && (e = hipMemcpyAsync(dm, mask, n_px, hipMemcpyHostToDevice, s)) != hipSuccess) { rc = hip_fail(e, "H2D"); break; }
-        if ((rc = ofl_flow_stats_dev((const float *)df, (const uint8_t *)dm, n_px, threshold, (uint32_t *)ds, s)) != OFL_OK) break;
-        if ((e = hipMemcpyAsync(stats_host, ds, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) { rc = hip_fail(e, "D2H"); break; }
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) { rc = hip_fail(e, "sync"); break; }
-    } while (0);
-    (void)hipFree(df); (void)hipFree(ds); if (dm) (void)hipFree(dm);
-    return rc;
+    HostStage st("ofl_flow_stats");
+    auto df = st.in(flow, n_px * 2);
+    auto dm = st.in(mask, n_px);
+    auto ds = st.out(stats_host, 1);
+    OFL_TRY(st.upload());
+    OFL_TRY(ofl_flow_stats_dev(df, dm, n_px, threshold, ds, st.stream()));
+    return st.download();
 }
 
 int ofl_axpy_dev(const float *a, const uint8_t *ma, const float *b, const uint8_t *mb, float alpha,

@@ -227,8 +227,6 @@ void tensor_transpose_kernel(const T *__restrict__ src, T *__restrict__ dst, uin
     }
 }
 
-inline bool host_aligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
-
 int check_tensor_dims(const char *who, int N, int C, int H, int W)
 {
     if (N < 1 || N > 65535) return fail(OFL_E_INVALID, "%s: N must be in [1, 65535], got %d", who, N);

@@ -12,6 +12,11 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _TENSOR_EL, _TENSOR_L
                    resized_shape, mask_bytes, valid_mask_array)
 
 
+def _host_ptr(a):
+    """Address of a host array for a host-array entry point, None (NULL: the argument is absent) for None."""
+    return None if a is None else a.ctypes.data
+
+
 # ------------------------------------------------------------------------------ K1: gather
 def gather_bilinear_batch(src, dtype, C, H, W, batch, flow, sign, smask=None, fmask=None, dst=None, valid=None,
                           shared_src=False, shared_smask=False, flow_shape=None, pad=(0, 0),
@@ -109,7 +114,7 @@ def consistency_host(f_vecs, f_mask, b_vecs, b_mask, sign, alpha, beta, want_res
     residual = np.empty((h, w), np.float32) if want_residual else None
     nat.check(_lib().ofl_consistency(f_vecs.ctypes.data, fm.ctypes.data, b_vecs.ctypes.data, bm.ctypes.data, sign, h, w, 1,
                                      alpha, beta, consistent.ctypes.data, covered.ctypes.data,
-                                     None if residual is None else residual.ctypes.data, None, quant))
+                                     _host_ptr(residual), None, quant))
     res = (consistent.view(np.bool_), covered.view(np.bool_))
     return res + (residual,) if want_residual else res
 
@@ -179,10 +184,9 @@ def error_host(est_vecs, est_mask, gt_vecs, gt_mask, thr, outlier, edges, want_m
     record = np.zeros(1, ERROR_RECORD)
     epe_map = np.empty((h, w), np.float32) if want_map else None
     outlier_map = np.empty((h, w), np.uint8) if want_outliers else None
-    nat.check(_lib().ofl_flow_error(est_vecs.ctypes.data, None if em is None else em.ctypes.data, gt_vecs.ctypes.data, gm.ctypes.data,
+    nat.check(_lib().ofl_flow_error(est_vecs.ctypes.data, _host_ptr(em), gt_vecs.ctypes.data, gm.ctypes.data,
                                     h, w, 1, thr.ctypes.data, outlier[0], outlier[1], edges.ctypes.data, record.ctypes.data,
-                                    None if epe_map is None else epe_map.ctypes.data,
-                                    None if outlier_map is None else outlier_map.ctypes.data))
+                                    _host_ptr(epe_map), _host_ptr(outlier_map)))
     return record[0], epe_map, None if outlier_map is None else outlier_map.view(np.bool_)
 
 
@@ -212,9 +216,8 @@ def fill_host(vecs, mask, valid, max_d2, want_index=False, want_d2=False):
     out_vecs, out_mask = np.empty((h, w, 2), np.float32), np.empty((h, w), np.uint8)
     index = np.empty((h, w), np.int32) if want_index else None
     d2 = np.empty((h, w), np.uint32) if want_d2 else None
-    nat.check(_lib().ofl_fill(vecs.ctypes.data, m.ctypes.data, None if valid is None else valid.ctypes.data, h, w, 1, max_d2,
-                              out_vecs.ctypes.data, out_mask.ctypes.data, None if index is None else index.ctypes.data,
-                              None if d2 is None else d2.ctypes.data))
+    nat.check(_lib().ofl_fill(vecs.ctypes.data, m.ctypes.data, _host_ptr(valid), h, w, 1, max_d2,
+                              out_vecs.ctypes.data, out_mask.ctypes.data, _host_ptr(index), _host_ptr(d2)))
     return out_vecs, out_mask.view(np.bool_), index, d2
 
 
@@ -347,9 +350,8 @@ def resize_host(vecs, mask, scale):
     out = np.empty((ho, wo, 2), np.float32)
     m = None if mask is None else mask_bytes(mask)
     mout = None if mask is None else np.empty((ho, wo), np.uint8)
-    hp = lambda a: None if a is None else a.ctypes.data
-    nat.check(_lib().ofl_resize_flow(hp(vecs), hp(m), h, w, ho, wo, 1.0 / fy, 1.0 / fx,
-                                     float(np.float32(fx)), float(np.float32(fy)), hp(out), hp(mout)))
+    nat.check(_lib().ofl_resize_flow(_host_ptr(vecs), _host_ptr(m), h, w, ho, wo, 1.0 / fy, 1.0 / fx,
+                                     float(np.float32(fx)), float(np.float32(fy)), _host_ptr(out), _host_ptr(mout)))
     return out, (None if mout is None else mout.astype(bool))
 
 
