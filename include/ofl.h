@@ -801,6 +801,45 @@ int ofl_fill_dev(const float *vecs, const uint8_t *mask, const uint8_t *valid, i
 int ofl_fill(const float *vecs, const uint8_t *mask, const uint8_t *valid, int H, int W, int batch, int max_d2,
              float *out_vecs, uint8_t *out_mask, int32_t *index, uint32_t *d2);
 
+/* ------------------------------------------------------------------ K16: mask-aware median filter of the vectors
+ * The step after fill (its output is piecewise constant with Voronoi seams), after a consistency check (outliers take the
+ * median of their consistent neighbours) or on a raw network output (despeckle).  No float operation touches a vector; the
+ * reference of the field does not enter.  Per field:
+ *     vecs  float32 [H][W][2]     mask  uint8 [H][W]     valid, only  uint8 [H][W] or NULL     ksize in {3, 5, 7}, r = ksize / 2
+ *     1 <= min_count <= ksize^2
+ *     member(q)  = q inside the frame and (mask[q] & (valid ? valid[q] : 0xFF)) != 0
+ *     N(p)       = { q : |qx - x| <= r, |qy - y| <= r, member(q) }      n(p) = |N(p)|   (the frame edge shrinks the window;
+ *                                                                                        no padding)
+ *     key(f)     = bits(f) ^ (bits(f) >> 31 ? 0xFFFFFFFF : 0x80000000)   uint32; a total order, equal to < on everything
+ *                  but NaN; -0.0 < +0.0; NaNs sort beyond +-Inf by sign and payload
+ *     med_c(p)   = the element of 0-based rank (n - 1) >> 1 in ascending key order among { vecs[q].c : q in N(p) }
+ *                  c = u, v separately
+ *     target(p)  = only ? only[p] != 0 : true
+ *     ok(p)      = target(p) and n(p) >= min_count
+ *     out_vecs[p].c = ok(p) ? the 4 bytes of med_c(p) : the 4 bytes of vecs[p].c
+ *     out_mask[p]   = target(p) ? (ok(p) ? 1 : 0) : (mask[p] != 0 ? 1 : 0)
+ * The median is the LOWER median: for an even count nothing is averaged, so every output word is a word of the input field
+ * (NaN payloads, +-Inf, -0.0 and denormals survive).  The centre pixel is a member like any other; a pixel that `valid`
+ * excludes is replaced by the median of its neighbours and becomes valid.  A valid pixel with fewer than min_count members
+ * around it keeps its vector and gets mask 0.  `batch` fields lie back to back and a window never crosses from one field
+ * into the next; offsets are size_t.  out_mask is optional.
+ * One launch: a workgroup stages a tile of 64 x 16 pixels plus its halo in LDS as keys, every pixel sorts the keys of its
+ * window in registers (non-members as 0xFFFFFFFF; the chosen rank is below n, so a real key equal to it yields the same
+ * bytes) and picks the rank.  No atomics, no workspace.
+ * vecs / out_vecs 8-byte aligned; the masks may sit at any address.  Outputs must not overlap inputs.
+ * A bad argument -- a NULL vecs, mask or out_vecs, H or W < 1, batch outside [1, 65535], a ksize other than 3, 5, 7, a
+ * min_count outside [1, ksize^2], an output range that overlaps an input range, a misaligned vector pointer -- returns
+ * OFL_E_INVALID with a message before any launch.  The _dev entry is asynchronous; the host entry takes host pointers,
+ * uploads, launches, downloads and synchronises.
+ * Not built: a vector (L1) median, weighted and bilateral medians, ksize > 7, an iteration count (call it twice).
+ */
+int ofl_median_dev(const float *vecs, const uint8_t *mask, const uint8_t *valid, const uint8_t *only,
+                   int H, int W, int batch, int ksize, int min_count,
+                   float *out_vecs, uint8_t *out_mask, void *stream);
+int ofl_median(const float *vecs, const uint8_t *mask, const uint8_t *valid, const uint8_t *only,
+               int H, int W, int batch, int ksize, int min_count,
+               float *out_vecs, uint8_t *out_mask);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

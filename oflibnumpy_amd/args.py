@@ -329,6 +329,42 @@ def fill_valid_array(valid, shape):
     return mask_bytes(valid)
 
 
+# -- mask-aware median filter (K16)
+MEDIAN_KSIZES = (3, 5, 7)
+
+
+def median_args(ksize=5, min_count=None):
+    """Validation of the window and the member threshold of a median filter (K16) on the host before any device work
+    -> (ksize, min_count) as Python ints: ksize an int in {3, 5, 7}; min_count None -> 1, otherwise an int in
+    1 ... ksize^2.  A bool or a non-integer is a TypeError, a value outside its set a ValueError."""
+    if isinstance(ksize, (bool, np.bool_)) or not isinstance(ksize, (int, np.integer)):
+        raise TypeError("Error filtering flow: ksize must be an integer, got {}".format(type(ksize).__name__))
+    if ksize not in MEDIAN_KSIZES:
+        raise ValueError("Error filtering flow: ksize must be 3, 5 or 7, got {}".format(ksize))
+    if min_count is None:
+        return int(ksize), 1
+    if isinstance(min_count, (bool, np.bool_)) or not isinstance(min_count, (int, np.integer)):
+        raise TypeError("Error filtering flow: min_count must be an integer or None, got {}".format(type(min_count).__name__))
+    if not 1 <= min_count <= ksize * ksize:
+        raise ValueError("Error filtering flow: min_count must be in 1 ... {} for ksize {}, got {}"
+                         .format(ksize * ksize, ksize, min_count))
+    return int(ksize), int(min_count)
+
+
+def median_mask_array(array, shape, name):
+    """A host array given as the `valid` or the `only` (`name`) of Flow.median / median_flow -> contiguous uint8 (H, W): a
+    NumPy array of bool or uint8 with the shape of the flow (TypeError for another type or dtype, ValueError for another
+    shape)."""
+    if not isinstance(array, np.ndarray):
+        raise TypeError("Error filtering flow: {} needs to be a numpy array, got {}".format(name, type(array).__name__))
+    if array.dtype != np.bool_ and array.dtype != np.uint8:
+        raise TypeError("Error filtering flow: {} needs to have dtype bool or uint8, got {}".format(name, array.dtype))
+    if array.shape != (shape[0], shape[1]):
+        raise ValueError("Error filtering flow: {} needs to have the shape of the flow, got {} and {}"
+                         .format(name, array.shape, (shape[0], shape[1])))
+    return mask_bytes(array)
+
+
 # -- many-channel float tensors (K12)
 def tensor_dtype(array_dtype, dtype=None):
     """The element type of a tensor -> 'float32', 'float16' or 'bfloat16'.  `array_dtype`: the dtype of the array that holds

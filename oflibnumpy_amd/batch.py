@@ -167,6 +167,20 @@ class DeviceFlowBatch:
         extra = ((index,) if return_index else ()) + ((d2,) if return_d2 else ())
         return (b,) + extra if extra else b
 
+    def median(self, ksize=5, valid=None, only=None, min_count=None):
+        """self[i].median(ksize, valid[i], only[i], min_count) for every i in ONE launch of K16 (DeviceFlow.median): `valid`
+        and `only` uint8 DeviceBuffers of n * H * W bytes or None; a window never crosses from one field into the next.
+        -> an unpacked DeviceFlowBatch of the same length, shape and reference.  A packed batch is read through its byte
+        masks.  Nothing synchronises."""
+        ksize, min_count = dev.median_args(ksize, min_count)
+        n_bytes = self.n * self.shape[0] * self.shape[1]
+        valid = dev.median_mask_buffer(valid, n_bytes, "valid")
+        only = dev.median_mask_buffer(only, n_bytes, "only")
+        out_vecs, out_mask = dev.median_launch(self.vecs, self.mask, valid, only, self.shape, ksize, min_count, batch=self.n)
+        b = DeviceFlowBatch.__new__(DeviceFlowBatch)
+        b.n, b.shape, b.ref, b.vecs, b.packed, b.bits, b._mask = self.n, self.shape, self.ref, out_vecs, False, None, out_mask
+        return b
+
     def apply_images(self, images, dtype, channels, shared=False, target_masks=None, shared_masks=False, quant=nat.QUANT_OPENCV):
         """self[i].apply(image_i, target_mask_i, return_valid_area=True) for every i in ONE launch of the gather kernel
         (ref 't' batches; Flow.apply, flow_class.py:604-695 without padding).  `images`: a DeviceBuffer holding [n][H][W][C] of

@@ -31,13 +31,13 @@ from .memory import (_lib, _ptr, _size_query, _Pool, _PinnedPool, empty_cache, D
 from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rules, mask_bytes, _points_array, visualise_args,
                    percentile_ranks, matrix_args, validate_transforms, valid_mask_array, scale_operand, crop_args,
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
-                   consistency_args, error_args, fill_args, fill_valid_array)
+                   consistency_args, error_args, fill_args, fill_valid_array, median_args, median_mask_array)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
                       track_bilinear_launch, track_query_points, track_query_epilogue, gather_tensor, tensor_import_launch,
                       tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
-                      FlowErrorStats, fill_launch, fill_host)
+                      FlowErrorStats, fill_launch, fill_host, median_launch, median_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -354,6 +354,16 @@ def fill_valid_buffer(valid, n_bytes):
     if valid is not None and valid.nbytes < n_bytes:
         raise ValueError("Error filling flow: valid needs to hold {} bytes, got {}".format(n_bytes, valid.nbytes))
     return valid
+
+
+def median_mask_buffer(buf, n_bytes, name):
+    """The `valid` or the `only` (`name`) of DeviceFlow.median / DeviceFlowBatch.median: None, or a uint8 buffer
+    (DeviceBuffer or a view) of at least n_bytes bytes -- e.g. `consistent` out of a consistency check."""
+    if buf is not None and not isinstance(buf, (DeviceBuffer, _BufferView)):
+        raise TypeError("Error filtering flow: {} needs to be a DeviceBuffer of uint8 or None, got {}".format(name, type(buf).__name__))
+    if buf is not None and buf.nbytes < n_bytes:
+        raise ValueError("Error filtering flow: {} needs to hold {} bytes, got {}".format(name, n_bytes, buf.nbytes))
+    return buf
 
 
 def mask_distance(mask_buf, shape, batch=1, max_dist=None):
@@ -682,6 +692,22 @@ class DeviceFlow:
         res = DeviceFlow(out_vecs, out_mask, self.shape, self.ref)
         extra = ((index,) if return_index else ()) + ((d2,) if return_d2 else ())
         return (res,) + extra if extra else res
+
+    def median(self, ksize=5, valid=None, only=None, min_count=None):
+        """The vectors median-filtered over a ksize x ksize window (3, 5 or 7), mask-aware, in one launch of K16
+        (include/ofl.h) and without leaving HBM.  A pixel is a member where self.mask -- and `valid`, a uint8 DeviceBuffer
+        of H * W bytes such as `consistent` out of DeviceFlow.consistency, if given -- is set; every pixel takes, per
+        component, the lower median of the members in its window (the frame edge shrinks the window; the centre is a
+        member like any other), provided there are at least `min_count` of them (None: 1; args.median_args).  `only`, a
+        uint8 DeviceBuffer of H * W bytes, restricts the filter to the pixels where it is set: the others keep vector and
+        mask.  A filtered pixel with too few members keeps its vector and gets mask 0.  Every output word is a word of
+        the input: nothing is averaged, NaN payloads and -0.0 survive.  -> a DeviceFlow of the same shape and reference.
+        Not a function of the reference.  Nothing synchronises; the inputs are not modified."""
+        ksize, min_count = median_args(ksize, min_count)
+        valid = median_mask_buffer(valid, self.n_px, "valid")
+        only = median_mask_buffer(only, self.n_px, "only")
+        out_vecs, out_mask = median_launch(self.vecs, self.mask, valid, only, self.shape, ksize, min_count)
+        return DeviceFlow(out_vecs, out_mask, self.shape, self.ref)
 
     # -- warping
     def apply(self, target, consider_mask=True, quant=nat.QUANT_OPENCV, target_mask=None):

@@ -501,6 +501,20 @@ class Flow(object):
         extra = ((index,) if return_index else ()) + ((d2,) if return_d2 else ())
         return (res,) + extra if extra else res
 
+    def median(self, ksize: int = 5, valid: np.ndarray = None, only: np.ndarray = None, min_count: int = None) -> FlowAlias:
+        """This flow with its vectors median-filtered over a ksize x ksize window (3, 5 or 7), mask-aware: a
+        pixel is a member where the mask -- and `valid`, a bool or uint8 (H, W) array, if given -- is set, every pixel
+        takes, per component, the lower median of the members in its window if there are at least `min_count` (None: 1)
+        of them, and keeps its vector and gets mask False otherwise; `only`, a bool or uint8 (H, W) array, restricts the
+        filter to the pixels where it is set.  Nothing is averaged: every output value is a value of the input.  -> a
+        Flow of the same reference.  Not a function of the reference; the definition is DeviceFlow.median's.  One upload,
+        one launch, one download."""
+        ksize, min_count = dev.median_args(ksize, min_count)
+        valid = None if valid is None else dev.median_mask_array(valid, self.shape, "valid")
+        only = None if only is None else dev.median_mask_array(only, self.shape, "only")
+        vecs, mask = dev.median_host(self._vecs, self._mask, valid, only, ksize, min_count)
+        return Flow(vecs, self._ref, mask)
+
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
         """flow_1 (+) flow_2 = flow_3: mode k returns flow_k from the other two (`self` comes first in
         that formula among the two given).  Reference flow_class.py:1247-1424."""

@@ -10,7 +10,7 @@ from .flow_class import Flow
 
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
-           'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow']
+           'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -81,3 +81,11 @@ def fill_flow(flow: nd, mask: nd, valid: nd = None, max_dist: float = None) -> t
     where a pixel was filled.  Not a function of the reference."""
     filled = Flow(flow, 't', mask).fill(valid=valid, max_dist=max_dist)
     return filled.vecs, filled.mask
+
+
+def median_flow(flow: nd, mask: nd, ksize: int = 5, valid: nd = None, only: nd = None, min_count: int = None) -> tuple:
+    """(vecs, mask) of the flow array `flow` median-filtered over a ksize x ksize window (3, 5 or 7) among the
+    pixels inside `mask` (and inside `valid`, if given), at the pixels where `only` is set (None: everywhere), with at
+    least `min_count` (None: 1) members per window -- Flow.median.  Not a function of the reference."""
+    filtered = Flow(flow, 't', mask).median(ksize=ksize, valid=valid, only=only, min_count=min_count)
+    return filtered.vecs, filtered.mask

@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error and K15 fill.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill and K16 median filter.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -219,6 +219,30 @@ def fill_host(vecs, mask, valid, max_d2, want_index=False, want_d2=False):
     nat.check(_lib().ofl_fill(vecs.ctypes.data, m.ctypes.data, _host_ptr(valid), h, w, 1, max_d2,
                               out_vecs.ctypes.data, out_mask.ctypes.data, _host_ptr(index), _host_ptr(d2)))
     return out_vecs, out_mask.view(np.bool_), index, d2
+
+
+# ------------------------------------------------------------------------------ K16: mask-aware median filter
+def median_launch(vecs, mask, valid, only, shape, ksize, min_count, batch=1, want_mask=True, stream=None):
+    """K16 (ofl_median_dev) on `batch` fields stored back to back; asynchronous, one launch.  ksize, min_count: from
+    args.median_args; valid None: the mask alone selects the members; only None: every pixel is filtered.
+    -> (out_vecs, out_mask or None): float32 [batch][H][W][2] and uint8 [batch][H][W], still in HBM."""
+    n = batch * shape[0] * shape[1]
+    out_vecs = DeviceBuffer(n * 8)
+    out_mask = DeviceBuffer(n) if want_mask else None
+    nat.check(_lib().ofl_median_dev(vecs.ptr, mask.ptr, _ptr(valid), _ptr(only), shape[0], shape[1], batch, ksize, min_count,
+                                    out_vecs.ptr, _ptr(out_mask), stream))
+    return out_vecs, out_mask
+
+
+def median_host(vecs, mask, valid, only, ksize, min_count):
+    """K16 for host arrays through ofl_median (upload, launch, download) -> (vecs float32 (H, W, 2), mask bool (H, W)).
+    valid, only: contiguous uint8 (H, W) or None."""
+    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(mask)
+    h, w = vecs.shape[:2]
+    out_vecs, out_mask = np.empty((h, w, 2), np.float32), np.empty((h, w), np.uint8)
+    nat.check(_lib().ofl_median(vecs.ctypes.data, m.ctypes.data, _host_ptr(valid), _host_ptr(only), h, w, 1, ksize, min_count,
+                                out_vecs.ctypes.data, out_mask.ctypes.data))
+    return out_vecs, out_mask.view(np.bool_)
 
 
 # ------------------------------------------------------------------------------ K7: visualise, K8: matrix fit
