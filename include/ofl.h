@@ -840,6 +840,46 @@ int ofl_median(const float *vecs, const uint8_t *mask, const uint8_t *valid, con
                int H, int W, int batch, int ksize, int min_count,
                float *out_vecs, uint8_t *out_mask);
 
+/* ------------------------------------------------------------------ K17: convex upsampling of a network's coarse flow
+ * The step between a flow network (RAFT, GMA, GMFlow / UniMatch, SEA-RAFT, FlowFormer) and the chain above: the network
+ * emits the flow at 1/f resolution with 9 f^2 mask logits per coarse pixel, and every fine pixel is the softmax-weighted
+ * combination of the 3 x 3 coarse neighbours, scaled by f.  Per item:
+ *     vecs    float32 [h][w][2]     mask  uint8 [h][w]     factor f in {2, 4, 8}
+ *     logits  9 f^2 channels of OFL_EL_F32, OFL_EL_F16 or OFL_EL_BF16, [9 f^2][h][w] (OFL_TENSOR_NCHW) or [h][w][9 f^2]
+ *             (OFL_TENSOR_NHWC); channel c = k f^2 + i f + j  (RAFT's order): tap k = (dy + 1) 3 + (dx + 1) with dy, dx in
+ *             {-1, 0, 1} as unfold orders them, sub-row i and sub-column j in [0, f)
+ *     out_vecs  float32 [f h][f w][2]     out_mask  uint8 [f h][f w] or NULL
+ * For the fine pixel (f y + i, f x + j), every operation float32 and rounded once (no FMA), taps in the order k = 0 .. 8:
+ *     x_k   = the logit as float32 (exact)               M = max_k x_k               t_k = x_k - M
+ *     e_k   = t_k < -87 ? 0 : exp32(t_k)
+ *     u_k   = f * vecs[y + dy][x + dx] (exact), 0 where the tap lies outside the coarse frame -- the zero padding of
+ *             unfold(padding=1); such a tap still takes part in the softmax
+ *     s     = e_0 + e_1 + ... + e_8          a_c = e_0 u_0c + e_1 u_1c + ... + e_8 u_8c          out_c = a_c / s  (IEEE)
+ *     out_mask = 1 where every tap INSIDE the frame has mask != 0, else 0; the vector is computed regardless
+ *     exp32(t), t in [-87, 0]:  n = rint(t * 1.44269504f);  r = (t - n * 0.693359375f) - n * -2.12194440e-4f;
+ *             p = 1/5040;  p = p r + c  for c = 1/720, 1/120, 1/24, 1/6, 1/2, 1, 1  (multiply and add rounded apart);
+ *             result = the float whose bit pattern is bits(p) + (n << 23).   exp32(0) = 1 exactly; within 2 * 2^-24
+ *             relative error of exp (tests/test_upsample_host.py measures it).
+ * float32 subnormals are kept, as NumPy keeps them.  Logits that are NaN or +-Inf give unspecified values in their pixel
+ * and never an access outside the buffers: no address depends on a logit's value.
+ * `batch` items lie back to back; offsets are 64-bit.  One launch: a workgroup stages the 3 x (T + 2) coarse neighbourhood
+ * of a tile of one coarse row in LDS, computes a band of fine rows into LDS and writes it out as whole rows.  No atomics,
+ * no workspace.
+ * vecs / out_vecs 8-byte aligned, logits aligned to their element, masks at any address.  Outputs must not overlap inputs.
+ * A bad argument -- a NULL vecs, mask, logits or out_vecs, a factor other than 2, 4, 8, another elem or layout, h or w < 1,
+ * f h or f w > 32766 (what the field kernels accept), batch outside [1, 65535], an overlap, a misaligned pointer -- returns
+ * OFL_E_INVALID with a message before any launch.  The _dev entry is asynchronous; the host entry takes host pointers,
+ * uploads, launches, downloads and synchronises.
+ * Not built: a batched bilinear resize, mask-aware renormalisation of the softmax, windows other than 3 x 3, other factors,
+ * a backward pass.
+ */
+int ofl_upsample_convex_dev(const float *vecs, const uint8_t *mask, const void *logits, int elem, int layout,
+                            int h, int w, int batch, int factor,
+                            float *out_vecs, uint8_t *out_mask, void *stream);
+int ofl_upsample_convex(const float *vecs, const uint8_t *mask, const void *logits, int elem, int layout,
+                        int h, int w, int batch, int factor,
+                        float *out_vecs, uint8_t *out_mask);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

@@ -148,6 +148,8 @@ SIGNATURES = {
     "ofl_fill": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
     "ofl_median_dev": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
     "ofl_median": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
+    "ofl_upsample_convex_dev": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "ofl_upsample_convex": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

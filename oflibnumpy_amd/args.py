@@ -365,6 +365,46 @@ def median_mask_array(array, shape, name):
     return mask_bytes(array)
 
 
+# -- convex upsampling (K17)
+UPSAMPLE_FACTORS = (2, 4, 8)
+
+
+def upsample_args(factor, weights_shape, coarse_shape):
+    """Validation of a convex upsampling (K17) on the host before any device work -> factor as a Python int.  `factor`: an
+    int in {2, 4, 8} (a bool or a non-integer is a TypeError, another value a ValueError); `weights_shape`: the LOGICAL
+    shape of the logits, (C, h, w) or (N, C, h, w), whose channel count must be 9 * factor^2 and whose height and width
+    must be those of `coarse_shape`, the (h, w) of the coarse field (ValueError otherwise)."""
+    if isinstance(factor, (bool, np.bool_)) or not isinstance(factor, (int, np.integer)):
+        raise TypeError("Error upsampling flow: factor must be an integer, got {}".format(type(factor).__name__))
+    if factor not in UPSAMPLE_FACTORS:
+        raise ValueError("Error upsampling flow: factor must be 2, 4 or 8, got {}".format(factor))
+    weights_shape = tuple(int(v) for v in weights_shape)
+    if len(weights_shape) not in (3, 4):
+        raise ValueError("Error upsampling flow: weights of shape {} are not (C, h, w) or (N, C, h, w)".format(weights_shape))
+    c, h, w = weights_shape[-3:]
+    if c != 9 * factor * factor:
+        raise ValueError("Error upsampling flow: factor {} needs {} weight channels, got {}".format(factor, 9 * factor * factor, c))
+    if (h, w) != (int(coarse_shape[0]), int(coarse_shape[1])):
+        raise ValueError("Error upsampling flow: weights and flow need the same height and width, got {} and {}"
+                         .format((h, w), (int(coarse_shape[0]), int(coarse_shape[1]))))
+    if h * factor > 32766 or w * factor > 32766:
+        raise ValueError("Error upsampling flow: {} x {} times {} is beyond the 32766 x 32766 a flow may have".format(h, w, factor))
+    return int(factor)
+
+
+def upsample_weights_array(weights, factor, coarse_shape):
+    """The `weights` of Flow.upsample_convex / upsample_flow_convex -> (contiguous array, factor): a NumPy array (9 f^2, h, w)
+    of float32 or float16 (TypeError for another type or dtype; the ValueErrors of upsample_args)."""
+    if not isinstance(weights, np.ndarray):
+        raise TypeError("Error upsampling flow: weights need to be a numpy array, got {}".format(type(weights).__name__))
+    if weights.dtype != np.float32 and weights.dtype != np.float16:
+        raise TypeError("Error upsampling flow: weights need to have dtype float32 or float16, got {}".format(weights.dtype))
+    factor = upsample_args(factor, weights.shape, coarse_shape)
+    if weights.ndim != 3:
+        raise ValueError("Error upsampling flow: one field takes weights of shape (C, h, w), got {}".format(weights.shape))
+    return np.ascontiguousarray(weights), factor
+
+
 # -- many-channel float tensors (K12)
 def tensor_dtype(array_dtype, dtype=None):
     """The element type of a tensor -> 'float32', 'float16' or 'bfloat16'.  `array_dtype`: the dtype of the array that holds

@@ -181,6 +181,19 @@ class DeviceFlowBatch:
         b.n, b.shape, b.ref, b.vecs, b.packed, b.bits, b._mask = self.n, self.shape, self.ref, out_vecs, False, None, out_mask
         return b
 
+    def upsample_convex(self, weights, factor=8):
+        """self[i].upsample_convex(weights[i], factor) for every i in ONE launch of K17 (DeviceFlow.upsample_convex):
+        `weights` a DeviceTensor of logical shape (n, 9 f^2, h, w) in either layout.  -> an unpacked DeviceFlowBatch of the
+        same length and reference and of shape (f h, f w).  A packed batch is read through its byte masks.  Nothing
+        synchronises."""
+        factor = dev.upsample_weights(weights, factor, self.shape, batch=self.n)
+        out_vecs, out_mask = dev.upsample_launch(self.vecs, self.mask, weights.buf, weights.dtype, weights.layout, self.shape,
+                                                 factor, batch=self.n)
+        b = DeviceFlowBatch.__new__(DeviceFlowBatch)
+        b.n, b.shape, b.ref, b.vecs = self.n, (factor * self.shape[0], factor * self.shape[1]), self.ref, out_vecs
+        b.packed, b.bits, b._mask = False, None, out_mask
+        return b
+
     def apply_images(self, images, dtype, channels, shared=False, target_masks=None, shared_masks=False, quant=nat.QUANT_OPENCV):
         """self[i].apply(image_i, target_mask_i, return_valid_area=True) for every i in ONE launch of the gather kernel
         (ref 't' batches; Flow.apply, flow_class.py:604-695 without padding).  `images`: a DeviceBuffer holding [n][H][W][C] of

@@ -31,13 +31,15 @@ from .memory import (_lib, _ptr, _size_query, _Pool, _PinnedPool, empty_cache, D
 from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rules, mask_bytes, _points_array, visualise_args,
                    percentile_ranks, matrix_args, validate_transforms, valid_mask_array, scale_operand, crop_args,
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
-                   consistency_args, error_args, fill_args, fill_valid_array, median_args, median_mask_array)
+                   consistency_args, error_args, fill_args, fill_valid_array, median_args, median_mask_array,
+                   upsample_args, upsample_weights_array)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
                       track_bilinear_launch, track_query_points, track_query_epilogue, gather_tensor, tensor_import_launch,
                       tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
-                      FlowErrorStats, fill_launch, fill_host, median_launch, median_host)
+                      FlowErrorStats, fill_launch, fill_host, median_launch, median_host, upsample_launch,
+                      upsample_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -364,6 +366,20 @@ def median_mask_buffer(buf, n_bytes, name):
     if buf is not None and buf.nbytes < n_bytes:
         raise ValueError("Error filtering flow: {} needs to hold {} bytes, got {}".format(name, n_bytes, buf.nbytes))
     return buf
+
+
+def upsample_weights(weights, factor, shape, batch=None):
+    """The `weights` of DeviceFlow.upsample_convex (batch None: logical shape (9 f^2, h, w)) or
+    DeviceFlowBatch.upsample_convex (batch n: (n, 9 f^2, h, w)) checked against the coarse field's `shape` -> factor."""
+    if not isinstance(weights, DeviceTensor):
+        raise TypeError("Error upsampling flow: weights need to be a DeviceTensor, got {}".format(type(weights).__name__))
+    factor = upsample_args(factor, weights.shape, shape)
+    if batch is None and weights.batched:
+        raise ValueError("Error upsampling flow: one field takes weights of shape (C, h, w), got {}".format(weights.shape))
+    if batch is not None and (not weights.batched or weights.n != batch):
+        raise ValueError("Error upsampling flow: a batch of {} fields takes weights of shape ({}, C, h, w), got {}"
+                         .format(batch, batch, weights.shape))
+    return factor
 
 
 def mask_distance(mask_buf, shape, batch=1, max_dist=None):
@@ -708,6 +724,17 @@ class DeviceFlow:
         only = median_mask_buffer(only, self.n_px, "only")
         out_vecs, out_mask = median_launch(self.vecs, self.mask, valid, only, self.shape, ksize, min_count)
         return DeviceFlow(out_vecs, out_mask, self.shape, self.ref)
+
+    def upsample_convex(self, weights, factor=8):
+        """This field, a network's coarse flow of shape (h, w), convexly upsampled by `factor` (2, 4 or 8) in one launch of
+        K17 (include/ofl.h) and without leaving HBM: `weights`, a DeviceTensor of logical shape (9 f^2, h, w) in either
+        layout and of float32, float16 or bfloat16, holds the network's mask logits in RAFT's channel order; every fine
+        pixel is the softmax-weighted combination of the 3 x 3 coarse neighbours, times f, with zero padding at the frame
+        edge.  The mask of a fine pixel is set where every neighbour inside the frame is valid.  -> a DeviceFlow of shape
+        (f h, f w) with the same reference.  Nothing synchronises; the inputs are not modified."""
+        factor = upsample_weights(weights, factor, self.shape)
+        out_vecs, out_mask = upsample_launch(self.vecs, self.mask, weights.buf, weights.dtype, weights.layout, self.shape, factor)
+        return DeviceFlow(out_vecs, out_mask, (factor * self.shape[0], factor * self.shape[1]), self.ref)
 
     # -- warping
     def apply(self, target, consider_mask=True, quant=nat.QUANT_OPENCV, target_mask=None):

@@ -515,6 +515,16 @@ class Flow(object):
         vecs, mask = dev.median_host(self._vecs, self._mask, valid, only, ksize, min_count)
         return Flow(vecs, self._ref, mask)
 
+    def upsample_convex(self, weights: np.ndarray, factor: int = 8) -> FlowAlias:
+        """This flow, a network's coarse output of shape (h, w), convexly upsampled by `factor` (2, 4 or 8): `weights`, a
+        float32 or float16 array (9 f^2, h, w), holds the network's mask logits in RAFT's channel order; every fine pixel
+        is the softmax-weighted combination of the 3 x 3 coarse neighbours, times f, and is valid where every neighbour
+        inside the frame is.  -> a Flow of shape (f h, f w) and the same reference; the definition is
+        DeviceFlow.upsample_convex's.  One upload, one launch, one download."""
+        weights, factor = dev.upsample_weights_array(weights, factor, self.shape)
+        vecs, mask = dev.upsample_host(self._vecs, self._mask, weights, factor)
+        return Flow(vecs, self._ref, mask)
+
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
         """flow_1 (+) flow_2 = flow_3: mode k returns flow_k from the other two (`self` comes first in
         that formula among the two given).  Reference flow_class.py:1247-1424."""

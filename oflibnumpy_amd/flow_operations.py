@@ -10,7 +10,8 @@ from .flow_class import Flow
 
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
-           'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow']
+           'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow',
+           'upsample_flow_convex']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -89,3 +90,11 @@ def median_flow(flow: nd, mask: nd, ksize: int = 5, valid: nd = None, only: nd =
     least `min_count` (None: 1) members per window -- Flow.median.  Not a function of the reference."""
     filtered = Flow(flow, 't', mask).median(ksize=ksize, valid=valid, only=only, min_count=min_count)
     return filtered.vecs, filtered.mask
+
+
+def upsample_flow_convex(flow: nd, mask: nd, weights: nd, factor: int = 8) -> tuple:
+    """(vecs, mask) of the coarse flow array `flow` (h, w, 2) convexly upsampled by `factor` (2, 4 or 8) with the mask
+    logits `weights`, a float32 or float16 array (9 factor^2, h, w) in RAFT's channel order -- Flow.upsample_convex.  Not a
+    function of the reference."""
+    fine = Flow(flow, 't', mask).upsample_convex(weights, factor=factor)
+    return fine.vecs, fine.mask

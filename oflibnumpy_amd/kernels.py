@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill and K16 median filter.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter and K17 convex upsampling.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -242,6 +242,31 @@ def median_host(vecs, mask, valid, only, ksize, min_count):
     out_vecs, out_mask = np.empty((h, w, 2), np.float32), np.empty((h, w), np.uint8)
     nat.check(_lib().ofl_median(vecs.ctypes.data, m.ctypes.data, _host_ptr(valid), _host_ptr(only), h, w, 1, ksize, min_count,
                                 out_vecs.ctypes.data, out_mask.ctypes.data))
+    return out_vecs, out_mask.view(np.bool_)
+
+
+# ------------------------------------------------------------------------------ K17: convex upsampling
+def upsample_launch(vecs, mask, weights, dtype, layout, shape, factor, batch=1, want_mask=True, stream=None):
+    """K17 (ofl_upsample_convex_dev) on `batch` coarse fields of `shape` (h, w) stored back to back; asynchronous, one
+    launch.  weights: the buffer of the logits, [batch][9 f^2][h][w] ('chw') or [batch][h][w][9 f^2] ('hwc') of `dtype`;
+    factor: from args.upsample_args.  -> (out_vecs, out_mask or None): float32 [batch][f h][f w][2] and uint8
+    [batch][f h][f w], still in HBM."""
+    n = batch * shape[0] * shape[1] * factor * factor
+    out_vecs = DeviceBuffer(n * 8)
+    out_mask = DeviceBuffer(n) if want_mask else None
+    nat.check(_lib().ofl_upsample_convex_dev(vecs.ptr, mask.ptr, weights.ptr, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout],
+                                             shape[0], shape[1], batch, factor, out_vecs.ptr, _ptr(out_mask), stream))
+    return out_vecs, out_mask
+
+
+def upsample_host(vecs, mask, weights, factor):
+    """K17 for host arrays through ofl_upsample_convex (upload, launch, download) -> (vecs float32 (f h, f w, 2), mask bool
+    (f h, f w)).  weights: a contiguous float32 or float16 array (9 f^2, h, w)."""
+    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(mask)
+    h, w = vecs.shape[:2]
+    out_vecs, out_mask = np.empty((factor * h, factor * w, 2), np.float32), np.empty((factor * h, factor * w), np.uint8)
+    nat.check(_lib().ofl_upsample_convex(vecs.ctypes.data, m.ctypes.data, weights.ctypes.data, _TENSOR_EL[weights.dtype.name],
+                                         nat.TENSOR_NCHW, h, w, 1, factor, out_vecs.ctypes.data, out_mask.ctypes.data))
     return out_vecs, out_mask.view(np.bool_)
 
 
