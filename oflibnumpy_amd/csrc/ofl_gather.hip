@@ -86,7 +86,7 @@ __device__ __forceinline__ uint32_t c3_spread16(uint32_t x)
 //
 // Register budget (tests/test_k2_resources.py): kC3Waves per SIMD with no spills and <= 80 SGPRs, so that scalar registers
 // never limit residency.  Only the interior gather is unrolled over a lane's four pixels; the border paths take one pixel
-// per loop trip through the lane's LDS slots, sample positions stay in their compact form while the loads are in flight,
+// (c3_border_px) or one pixel pair (c3_border_pair) per loop trip through the lane's LDS slots, sample positions stay in their compact form while the loads are in flight,
 // and every address is a wave-uniform field base plus a 32-bit offset (ofl_compose3_route.h sends fields whose vector
 // plane reaches 4 GiB to the generic kernel).
 constexpr int kC3LanesX = 32;      // lanes along x per tile row: tile = 4*LX px x 256/LX rows
@@ -422,6 +422,77 @@ __device__ __forceinline__ void c3_classify(const C3Pos &p, int H, int W, bool a
     outside = outside && (out_j || !act);
 }
 
+// The two pixels of one lane pair (gx, gx + 1 of row gy; slots v[0..1], k[0..1]) in ONE gather round trip instead of
+// c3_border_px's two: both pixels' mask taps (one unaligned 2-byte load per row and pixel at the clamped column, bytes
+// ixc and ixc + 1 <= W - 1) and then both pixels' vector taps are requested before anything is selected or blended.  Per
+// pixel the calls and their order are c3_border_px's, so the values are too: a tap outside the source becomes 0.0f by
+// selecting the VALUE (a zeroed weight would change the sign of zero sums and let a clamped Inf / NaN through).  A pair
+// group whose pixels are outside (or inactive) in every lane of the wave loads nothing: (0, 0) and validity 0 are what the
+// selects give such pixels.  Byte masks with QUANT_OPENCV only: QUANT_EXACT has no register left for it (HISTORY round 7).
+template <int QUANT, bool STATS>
+__device__ __forceinline__ void c3_border_pair(const C3Args &a, const C3Field &F, int gx, int gy, bool act,
+                                               float2 *v, uint8_t *k, C3Stat &st)
+{
+    const int H = a.H, W = a.W;
+    const float4 f = *reinterpret_cast<const float4 *>(v);
+    C3Pos p[2] = { c3_pos<QUANT>(gx, gy, f.x, f.y, a.sign), c3_pos<QUANT>(gx + 1, gy, f.z, f.w, a.sign) };
+    bool inside = true, outside = true;       // (`inside` is not used: the wave is a border wave)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) c3_classify<QUANT>(p[i], H, W, act, inside, outside);
+    if (__all(outside)) {
+        *reinterpret_cast<float4 *>(v) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        *reinterpret_cast<uint16_t *>(k) = 0;
+        return;
+    }
+    uint32_t s0[2], s1[2];                    // the clamped tap rows' offsets (the rows clamp independently)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int ix  = c3_tap<QUANT>(p[i].x), iy = c3_tap<QUANT>(p[i].y);
+        const int ixc = min(max(ix, 0), max(W - 2, 0));
+        s0[i] = (uint32_t)min(max(iy, 0), H - 1) * (uint32_t)W + (uint32_t)ixc;
+        s1[i] = (uint32_t)min(max(iy + 1, 0), H - 1) * (uint32_t)W + (uint32_t)ixc;
+    }
+    uint32_t q0[2], q1[2];
+    Pair2    p0[2], p1[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {             // mask taps first, as in the interior gather
+        q0[i] = reinterpret_cast<const U16u *>(c3_elem(F.ma, s0[i]))->v;
+        q1[i] = reinterpret_cast<const U16u *>(c3_elem(F.ma, s1[i]))->v;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        p0[i] = c3_pair(F.fa, s0[i]);
+        p1[i] = c3_pair(F.fa, s1[i]);
+    }
+    float   su[2], sv[2];
+    uint32_t ok = 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        // Which taps exist is worked out only here, behind the loads and behind the first pixel's blend: as compare results
+        // the select conditions and the mask taps are wave masks, two scalar registers each, and with those of both pixels
+        // alive across the round trip the kernel goes past its 80 SGPRs.  The empty statements emit nothing; they only keep
+        // the compiler from moving what follows them to the front.
+        if (i == 0) asm volatile("" : "+v"(p[0].x), "+v"(p[0].y));
+        else        asm volatile("" : "+v"(p[1].x), "+v"(p[1].y), "+v"(su[0]), "+v"(sv[0]), "+v"(ok));
+        const int  ix = c3_tap<QUANT>(p[i].x), iy = c3_tap<QUANT>(p[i].y);
+        const int  d  = ix - min(max(ix, 0), max(W - 2, 0));
+        const bool r0 = (unsigned)iy < (unsigned)H;
+        const bool r1 = (unsigned)(iy + 1) < (unsigned)H;
+        float u00, v00, u01, v01, u10, v10, u11, v11, a00, a01, a10, a11;
+        select_pair(p0[i], d, r0, u00, v00, u01, v01);
+        select_pair(p1[i], d, r1, u10, v10, u11, v11);
+        select_mask(q0[i] & 0xffu, q0[i] & 0xff00u, d, r0, a00, a01);
+        select_mask(q1[i] & 0xffu, q1[i] & 0xff00u, d, r1, a10, a11);
+        const C3Tap w = c3_weights<QUANT>(p[i]);
+        su[i] = c3_blend(u00, u01, u10, u11, w);
+        sv[i] = c3_blend(v00, v01, v10, v11, w);
+        ok |= c3_valid<QUANT>(a00 != 0.0f, a01 != 0.0f, a10 != 0.0f, a11 != 0.0f, w) ? 1u << (8 * i) : 0u;
+        if (STATS) st.amax_m = fmaxf(st.amax_m, (a00 != 0.0f && act) ? fmaxf(fabsf(u00), fabsf(v00)) : 0.0f);
+    }
+    *reinterpret_cast<float4 *>(v) = make_float4(su[0], sv[0], su[1], sv[1]);
+    *reinterpret_cast<uint16_t *>(k) = (uint16_t)ok;
+}
+
 constexpr int kXpRowF2 = 128 + 4;             // LDS row stride in float2 (padding spreads the 8 rows over the banks)
 constexpr int kXposeRows = 6;                 // source rows one streamed 128-px segment may cross before we transpose
 
@@ -541,13 +612,20 @@ __device__ __forceinline__ void c3_tile(const C3Args &a, const C3Field &F, int y
         bu[0] = b01.x; bu[1] = b01.z; bu[2] = b23.x; bu[3] = b23.z;
         bv[0] = b01.y; bv[1] = b01.w; bv[2] = b23.y; bv[3] = b23.w;
     } else {
-        // border path, one pixel per trip through the lane's LDS slots
+        // border path through the lane's LDS slots: a pixel PAIR per trip, or one pixel where the pair form does not fit
+        constexpr bool pairs = !BITS && QUANT == OFL_QUANT_OPENCV;      // (c3_border_pair: QUANT_EXACT is at 80 of 80 VGPRs without it)
         *reinterpret_cast<float4 *>(v)      = in.v[0];
         *reinterpret_cast<float4 *>(v + 64) = in.v[1];
+        if constexpr (pairs) {
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-        for (int j = 0; j < kC3Px; ++j) {
-            const int o = (j & 1) + 64 * (j >> 1);
-            c3_border_px<QUANT, STATS, BITS>(a, F, xg[0] + o, y, y < H && xg[0] + o < W, v[o], k[o], st);
+            for (int g = 0; g < 2; ++g)
+                c3_border_pair<QUANT, STATS>(a, F, xg[0] + 64 * g, y, g ? act[1] : act[0], v + 64 * g, k + 64 * g, st);
+        } else {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+            for (int j = 0; j < kC3Px; ++j) {
+                const int o = (j & 1) + 64 * (j >> 1);
+                c3_border_px<QUANT, STATS, BITS>(a, F, xg[0] + o, y, y < H && xg[0] + o < W, v[o], k[o], st);
+            }
         }
         const float4 s01 = *reinterpret_cast<const float4 *>(v), s23 = *reinterpret_cast<const float4 *>(v + 64);
         const uint32_t k01 = *reinterpret_cast<const uint16_t *>(k), k23 = *reinterpret_cast<const uint16_t *>(k + 64);
