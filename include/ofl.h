@@ -880,6 +880,66 @@ int ofl_upsample_convex(const float *vecs, const uint8_t *mask, const void *logi
                         int h, int w, int batch, int factor,
                         float *out_vecs, uint8_t *out_mask);
 
+/* ------------------------------------------------------------------ K18: on-demand correlation lookup of two feature tensors
+ * The correlation step of a flow network -- RAFT's multi-level lookup (levels = 4, r = 4, scale = 1 / sqrt(C)), the local
+ * cost volume of PWC-Net (levels = 1 after a warp by K12) -- without the all-pairs volume of (H W)^2 floats: the dot
+ * products a pixel needs are formed when it asks for them.  Per item:
+ *     f1   C channels on an H x W grid, channels last [H][W][C], of OFL_EL_F32, OFL_EL_F16 or OFL_EL_BF16
+ *     f2_l level l of the pyramid of f2, channels last [H_l][W_l][C]: level 0 is f2 as stored (any of the three types, not
+ *          necessarily f1's), level l >= 1 is the 2 x 2 mean of level l - 1 (ofl_avgpool2_dev), always float32:
+ *              ((a + b) + (c + d)) * 0.25f      a, b, c, d = top-left, top-right, bottom-left, bottom-right
+ *          H_l = H >> l, W_l = W >> l: a trailing odd row or column is dropped, as avg_pool2d(2, stride=2) drops it; an
+ *          empty level is refused.  16-bit values are widened to float32, which is exact.
+ *     flow float32 [H][W][2] in pixels of the H x W grid, or NULL (u = v = 0, nothing is read); one field per item, or one
+ *          for all (flow_shared).  No mask is read and none is written.
+ * For pixel (x, y), every operation float32 and rounded once (no FMA):
+ *     px = map_coord(x, u, sign) * 2^-l,  py = map_coord(y, v, sign) * 2^-l      map_coord: the float64 sum x +- u rounded
+ *          once to float32, as in K1 / K12; the product with a power of two is exact.  sign +1 is the 's' rule, -1 the 't' rule
+ *     t  = make_tap<quant>(px, py)        K1's taps: OFL_QUANT_EXACT floor and fraction (what grid_sample does),
+ *          OFL_QUANT_OPENCV the 1/32-px snap; t.ix, t.iy saturated to [-32768, 32767]
+ *     D(ix, iy) = sum_c f1[x, y, c] * f2_l[ix, iy, c]  for the (2r + 2)^2 integer taps ix in [t.ix - r, t.ix + r + 1], iy in
+ *          [t.iy - r, t.iy + r + 1]; exactly 0 where the tap lies outside the H_l x W_l frame.  The order of the sum:
+ *          the channels go in groups of V = OFL_CORR_V = 4 consecutive channels, group g to partial sum g mod L,
+ *          L = OFL_CORR_L = 16; partial sum p starts with its first product and adds the others in ascending channel order
+ *          (p_0 = c0 + c1 + c2 + c3 + c64 + c65 + ..., left to right); the partial sums are added in the pairwise tree
+ *          ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7))  +  the same of p8 .. p15.  A partial sum without a channel
+ *          (C <= 4 p) is left out of the tree -- nothing is added for it, not even + 0.0f, so a sum of -0.0 stays -0.0 --
+ *          and the tree keeps its shape: with C = 20, D = ((p0 + p1) + (p2 + p3)) + p4.  V and L do not depend on C, N,
+ *          the element types or the position in a batch: 16 lanes x 4 channels is one 128- or 256-byte load of a row.
+ *     value(ox, oy) = blend4(D(t.ix + ox, t.iy + oy), D(t.ix + ox + 1, t.iy + oy), D(t.ix + ox, t.iy + oy + 1),
+ *          D(t.ix + ox + 1, t.iy + oy + 1), t) * scale          ox, oy in [-r, r]; K1's blend, left to right; all
+ *          (2r + 1)^2 samples of a pixel share the centre's fraction, as alt_cuda_corr does
+ *     out  float32, planar [total_channels][H][W] per item; this level writes the (2r + 1)^2 channels from first_channel:
+ *          channel first_channel + k with k = (ox + r)(2r + 1) + (oy + r) for OFL_CORR_XY -- the order of RAFT's
+ *          CorrBlock, whose first window axis moves x -- and k = (oy + r)(2r + 1) + (ox + r) for OFL_CORR_YX, the row-major
+ *          order of PWC-style cost volumes.  A multi-level lookup is one call per level with first_channel = l (2r + 1)^2.
+ * A NaN or huge coordinate leads only to taps that are inside the frame or skipped (the clamps of make_tap; the window
+ * arithmetic is int); the values of a pixel with a NaN coordinate are unspecified.  No address depends on a feature value.
+ * `N` items lie back to back; offsets are 64-bit.  One launch per level: a wave reads whole rows of f2_l, 16 lanes a row;
+ * no atomics, no workspace.  Both entries take channels-last tensors only (ofl_tensor_permute_dev makes one of a planar
+ * tensor, at the cost of one read and one write of it).
+ * f1 / f2_l aligned to their element (a base aligned to four elements, with C % 4 == 0, is read four elements a load),
+ * out 4-byte, flow 8-byte aligned.  A bad argument -- a NULL f1, f2_l or out, an element other than the three (OFL_EL_F64
+ * included), an unknown order or quant, a sign other than +-1, r outside [1, 4], level outside [0, 7], N or C outside
+ * [1, 65535], H or W outside [1, 32766], H_l, W_l other than H >> level, W >> level or < 1, channels
+ * [first_channel, first_channel + (2r + 1)^2) that do not lie in [0, total_channels), an output that overlaps an input, a
+ * misaligned pointer -- returns OFL_E_INVALID with a message before any launch.  ofl_avgpool2_dev refuses H or W < 2 likewise.
+ * The _dev entries are asynchronous.  The host entry ofl_corr_lookup takes host pointers -- f1 and f2 (level 0) channels last,
+ * the optional flow, out [N][levels (2r + 1)^2][H][W] with levels in [1, 8] --, uploads, builds the pyramid, launches the
+ * `levels` lookups, downloads and synchronises.
+ * Not built: a backward pass, radii above 4, strides and dilations, an MFMA or FMA path (neither can be restated in NumPy
+ * float32), 16-bit output, the all-pairs volume itself.
+ */
+enum { OFL_CORR_XY = 0, OFL_CORR_YX = 1 };
+#define OFL_CORR_V 4
+#define OFL_CORR_L 16
+int ofl_avgpool2_dev(const void *src, int elem, int N, int C, int H, int W, float *dst, void *stream);
+int ofl_corr_lookup_dev(const void *f1, int elem1, const void *f2_l, int elem2, int N, int C, int H, int W, int H_l, int W_l,
+                        int level, const float *flow, int flow_shared, int sign, int r, float scale, int order, int quant,
+                        float *out, int total_channels, int first_channel, void *stream);
+int ofl_corr_lookup(const void *f1, int elem1, const void *f2, int elem2, int N, int C, int H, int W, int levels,
+                    const float *flow, int flow_shared, int sign, int r, float scale, int order, int quant, float *out);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

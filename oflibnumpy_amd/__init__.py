@@ -14,6 +14,7 @@ from .flow_operations import *
 from .utils import from_matrix, from_transforms, load_sintel, save_sintel, load_sintel_mask, load_kitti, apply_flow, is_zero_flow, threshold_vectors, track_pts, resize_flow
 from .device import DeviceFlow, DeviceImage, DeviceTensor, DeviceBuffer, DevicePoints, DeviceArray, external_args, DeviceFlowError, FlowErrorStats
 from .batch import DeviceFlowBatch, combine_flows_batch
+from .correlation import DeviceCorrelation
 from . import _native as native
 
 __version__ = "0.1.0"

@@ -24,6 +24,8 @@ VIS_SHOW_MASK, VIS_MASK_BORDERS = 1, 2
 TRACK_F64, TRACK_I32, TRACK_I64 = 0, 1, 2
 EL_F16, EL_BF16, EL_F32, EL_F64 = 0, 1, 2, 3
 TENSOR_NCHW, TENSOR_NHWC = 0, 1
+CORR_XY, CORR_YX = 0, 1
+CORR_V, CORR_L = 4, 16
 
 
 class MeshCert(ctypes.Structure):
@@ -150,6 +152,10 @@ SIGNATURES = {
     "ofl_median": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
     "ofl_upsample_convex_dev": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
     "ofl_upsample_convex": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
+    "ofl_avgpool2_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
+    "ofl_corr_lookup_dev": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _ci, _cf, _ci, _ci,
+                                  _vp, _ci, _ci, _vp]),
+    "ofl_corr_lookup": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _ci, _cf, _ci, _ci, _vp]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

@@ -405,6 +405,57 @@ def upsample_weights_array(weights, factor, coarse_shape):
     return np.ascontiguousarray(weights), factor
 
 
+# -- on-demand correlation lookup (K18)
+CORR_ORDERS = {'xy': 0, 'yx': 1}        # OFL_CORR_XY (RAFT's CorrBlock), OFL_CORR_YX (row-major cost volumes)
+
+
+def corr_args(radius, levels, scale, order, quant, channels, shape):
+    """Validation of a correlation lookup (K18) on the host before any device work -> (radius, levels, scale as float32,
+    order code, quant).  radius: an int in 1 ... 4; levels: an int in 1 ... 8 whose last pyramid level of `shape` (H, W),
+    (H >> levels - 1, W >> levels - 1), must not be empty; scale: None for float32(1 / sqrt(float64(channels))), or a finite
+    number; order: 'xy' or 'yx'; quant: 0 (the 1/32-px snap) or 1 (exact).  A bool or a non-number is a TypeError, a value
+    outside its set a ValueError."""
+    for name, value in (("radius", radius), ("levels", levels), ("quant", quant)):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+            raise TypeError("Error looking up correlation: {} must be an integer, got {}".format(name, type(value).__name__))
+    if not 1 <= radius <= 4:
+        raise ValueError("Error looking up correlation: radius must be in 1 ... 4, got {}".format(radius))
+    if not 1 <= levels <= 8:
+        raise ValueError("Error looking up correlation: levels must be in 1 ... 8, got {}".format(levels))
+    h, w = int(shape[0]), int(shape[1])
+    if h >> (levels - 1) < 1 or w >> (levels - 1) < 1:
+        raise ValueError("Error looking up correlation: level {} of a {} x {} grid is empty".format(levels - 1, h, w))
+    if quant not in (0, 1):
+        raise ValueError("Error looking up correlation: quant must be 0 (QUANT_OPENCV) or 1 (QUANT_EXACT), got {}".format(quant))
+    if not isinstance(order, str):
+        raise TypeError("Error looking up correlation: order must be a string, got {}".format(type(order).__name__))
+    if order not in CORR_ORDERS:
+        raise ValueError("Error looking up correlation: order must be 'xy' or 'yx', got {!r}".format(order))
+    if scale is None:
+        scale = np.float32(1.0 / np.sqrt(np.float64(channels)))
+    else:
+        if isinstance(scale, (bool, np.bool_)) or not isinstance(scale, (int, float, np.integer, np.floating)):
+            raise TypeError("Error looking up correlation: scale must be a number or None, got {}".format(type(scale).__name__))
+        with np.errstate(over='ignore'):
+            scale = np.float32(float(scale)) if abs(scale) < 1e300 else np.float32(np.inf)
+        if not np.isfinite(scale):
+            raise ValueError("Error looking up correlation: scale must be finite as float32")
+    return int(radius), int(levels), scale, CORR_ORDERS[order], int(quant)
+
+
+def corr_host_array(a, name):
+    """A feature map given to correlation_lookup -> (contiguous channels-last array (1, H, W, C), logical shape): a NumPy
+    array (C, H, W) of float32 or float16 (TypeError for another type or dtype, ValueError for another rank)."""
+    if not isinstance(a, np.ndarray):
+        raise TypeError("Error looking up correlation: {} needs to be a numpy array, got {}".format(name, type(a).__name__))
+    if a.dtype != np.float32 and a.dtype != np.float16:
+        raise TypeError("Error looking up correlation: {} needs to have dtype float32 or float16, got {}".format(name, a.dtype))
+    if a.ndim != 3:
+        raise ValueError("Error looking up correlation: {} needs to have shape (C, H, W), got {}".format(name, a.shape))
+    tensor_args(a.shape, 'chw', a.dtype.name)
+    return np.ascontiguousarray(np.moveaxis(a, 0, -1))[None], tuple(a.shape)
+
+
 # -- many-channel float tensors (K12)
 def tensor_dtype(array_dtype, dtype=None):
     """The element type of a tensor -> 'float32', 'float16' or 'bfloat16'.  `array_dtype`: the dtype of the array that holds

@@ -32,14 +32,14 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rul
                    percentile_ranks, matrix_args, validate_transforms, valid_mask_array, scale_operand, crop_args,
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
                    consistency_args, error_args, fill_args, fill_valid_array, median_args, median_mask_array,
-                   upsample_args, upsample_weights_array)
+                   upsample_args, upsample_weights_array, corr_args, corr_host_array)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
                       track_bilinear_launch, track_query_points, track_query_epilogue, gather_tensor, tensor_import_launch,
                       tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
                       FlowErrorStats, fill_launch, fill_host, median_launch, median_host, upsample_launch,
-                      upsample_host)
+                      upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -267,6 +267,14 @@ class DeviceTensor:
                              .format(self.layout, layout))
         buf = tensor_permute_launch(self.buf, self.dtype, self.n, self.channels, self.h, self.w, layout == 'hwc')
         return DeviceArray(buf, out_shape, _TENSOR_TYPESTR[self.dtype])
+
+    def correlation(self, other, flow=None, radius=4, levels=1, scale=None, order='xy', quant=nat.QUANT_EXACT):
+        """The correlation of this tensor's features with those of `other` around every pixel, in one call:
+        DeviceCorrelation.build(self, other, levels).lookup(flow, radius, scale, order, quant) (correlation.py, K18).  With
+        levels = 1 and flow = None on a tensor that DeviceFlow.apply_tensor has warped this is the cost volume of PWC-Net.
+        -> a planar float32 DeviceTensor of levels (2 radius + 1)^2 channels."""
+        from .correlation import DeviceCorrelation
+        return DeviceCorrelation.build(self, other, levels).lookup(flow, radius, scale, order, quant)
 
 
 # ------------------------------------------------------------------------------ the launch wrappers that hand back a DeviceImage

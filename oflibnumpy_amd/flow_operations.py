@@ -11,7 +11,7 @@ from .flow_class import Flow
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
            'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow',
-           'upsample_flow_convex']
+           'upsample_flow_convex', 'correlation_lookup']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -98,3 +98,28 @@ def upsample_flow_convex(flow: nd, mask: nd, weights: nd, factor: int = 8) -> tu
     function of the reference."""
     fine = Flow(flow, 't', mask).upsample_convex(weights, factor=factor)
     return fine.vecs, fine.mask
+
+
+def correlation_lookup(fmap1: nd, fmap2: nd, flow: nd = None, ref: str = 's', radius: int = 4, levels: int = 1,
+                       scale: float = None, order: str = 'xy') -> nd:
+    """The correlation of the feature maps `fmap1` and `fmap2`, float32 or float16 arrays (C, H, W), looked up around
+    x + flow (ref 's') or x - flow (ref 't') on `levels` pyramid levels of fmap2 within `radius` (1 ... 4) -- RAFT's
+    CorrBlock without the all-pairs volume; DeviceCorrelation.lookup with the exact taps of grid_sample.  flow: a float32
+    array (H, W, 2) in pixels of the feature grid, or None for the window around the pixel itself.  scale: None for
+    1 / sqrt(C).  order: 'xy' (RAFT's channel order) or 'yx' (row-major).  -> float32 (levels (2 radius + 1)^2, H, W).
+    One upload, `levels` launches, one download."""
+    from . import device as dev
+    from .utils import get_valid_ref
+    sign = 1 if get_valid_ref(ref) == 's' else -1
+    f1, shape1 = dev.corr_host_array(fmap1, "fmap1")
+    f2, shape2 = dev.corr_host_array(fmap2, "fmap2")
+    if shape1 != shape2:
+        raise ValueError("Error looking up correlation: the feature maps need the same shape, got {} and {}".format(shape1, shape2))
+    radius, levels, scale, order, quant = dev.corr_args(radius, levels, scale, order, dev.nat.QUANT_EXACT, shape1[0], shape1[1:])
+    if flow is not None:
+        if not isinstance(flow, np.ndarray):
+            raise TypeError("Error looking up correlation: flow needs to be a numpy array or None, got {}".format(type(flow).__name__))
+        if flow.shape != shape1[1:] + (2,):
+            raise ValueError("Error looking up correlation: flow needs to have shape {}, got {}".format(shape1[1:] + (2,), flow.shape))
+        flow = np.ascontiguousarray(flow, np.float32)
+    return dev.corr_lookup_host(f1, f2, flow, sign, radius, levels, scale, order, quant)[0]

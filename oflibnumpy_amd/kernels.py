@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter and K17 convex upsampling.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling and K18 correlation lookup.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -482,3 +482,36 @@ def tensor_permute_launch(src, dtype, n, c, h, w, to_hwc, stream=None):
     dst = DeviceBuffer(n * c * h * w * _tensor_bytes(dtype))
     nat.check(_lib().ofl_tensor_permute_dev(src.ptr, dst.ptr, _tensor_bytes(dtype), n, c, h, w, 1 if to_hwc else 0, stream))
     return dst
+
+
+# ------------------------------------------------------------------------------ K18: on-demand correlation lookup
+def avgpool2_launch(src, dtype, n, c, h, w, stream=None):
+    """ofl_avgpool2_dev: the 2 x 2 mean of a channels-last tensor [n][h][w][c] of `dtype` -> float32 [n][h >> 1][w >> 1][c]."""
+    dst = DeviceBuffer(n * (h >> 1) * (w >> 1) * c * 4)
+    nat.check(_lib().ofl_avgpool2_dev(src.ptr, _TENSOR_EL[dtype], n, c, h, w, dst.ptr, stream))
+    return dst
+
+
+def corr_lookup_launch(f1, dtype1, pyramid, n, c, h, w, flow, flow_shared, sign, radius, scale, order, quant, stream=None):
+    """K18 (ofl_corr_lookup_dev), one launch per level of `pyramid`, a list of (buffer, dtype) of the channels-last levels
+    of f2; f1: the channels-last buffer [n][h][w][c] of `dtype1`; flow: the buffer of the field(s) or None; scale, order,
+    quant: from args.corr_args.  Asynchronous.  -> float32 [n][levels (2 radius + 1)^2][h][w], still in HBM."""
+    nch = (2 * radius + 1) ** 2
+    total = len(pyramid) * nch
+    out = DeviceBuffer(n * total * h * w * 4)
+    for level, (buf, dtype2) in enumerate(pyramid):
+        nat.check(_lib().ofl_corr_lookup_dev(f1.ptr, _TENSOR_EL[dtype1], buf.ptr, _TENSOR_EL[dtype2], n, c, h, w, h >> level, w >> level,
+                                             level, _ptr(flow), 1 if flow_shared else 0, sign, radius, scale, order, quant,
+                                             out.ptr, total, level * nch, stream))
+    return out
+
+
+def corr_lookup_host(f1, f2, flow, sign, radius, levels, scale, order, quant):
+    """K18 for host arrays through ofl_corr_lookup (upload, pyramid, `levels` launches, download): f1, f2 contiguous
+    channels-last (n, h, w, c) of float32 or float16, flow float32 (h, w, 2) -- one field for all items -- or None
+    -> float32 (n, levels (2 radius + 1)^2, h, w)."""
+    n, h, w, c = f1.shape
+    out = np.empty((n, levels * (2 * radius + 1) ** 2, h, w), np.float32)
+    nat.check(_lib().ofl_corr_lookup(f1.ctypes.data, _TENSOR_EL[f1.dtype.name], f2.ctypes.data, _TENSOR_EL[f2.dtype.name], n, c, h, w,
+                                     levels, _host_ptr(flow), 1, sign, radius, scale, order, quant, out.ctypes.data))
+    return out
