@@ -36,6 +36,33 @@ def mask_bytes(mask):
     return m.view(np.uint8) if m.dtype == np.bool_ else m.astype(np.uint8)
 
 
+def optional_bool(value, default, message):
+    """An optional boolean argument -> bool: None gives `default`, anything but a bool is TypeError(message)."""
+    value = default if value is None else value
+    if not isinstance(value, bool):
+        raise TypeError(message)
+    return value
+
+
+def _is_integer(value):
+    """an integer, Python's or NumPy's, and not a bool"""
+    return isinstance(value, (int, np.integer)) and not isinstance(value, (bool, np.bool_))
+
+
+def mask_array_arg(array, shape, prefix, name):
+    """A host array given as a mask argument `name` (the `valid` of Flow.fill, the `valid` or `only` of Flow.median) ->
+    contiguous uint8 (H, W): a NumPy array of bool or uint8 with the shape of the flow (TypeError for another type or
+    dtype, ValueError for another shape).  `prefix` opens the message, e.g. "Error filling flow: "."""
+    if not isinstance(array, np.ndarray):
+        raise TypeError("{}{} needs to be a numpy array, got {}".format(prefix, name, type(array).__name__))
+    if array.dtype != np.bool_ and array.dtype != np.uint8:
+        raise TypeError("{}{} needs to have dtype bool or uint8, got {}".format(prefix, name, array.dtype))
+    if array.shape != (shape[0], shape[1]):
+        raise ValueError("{}{} needs to have the shape of the flow, got {} and {}"
+                         .format(prefix, name, array.shape, (shape[0], shape[1])))
+    return mask_bytes(array)
+
+
 def _points_array(arr):
     """A host array of points, checked like track_pts (utils.py:571-574, :592) -> contiguous (n, 2) float64, int32 or int64.
     Other float dtypes become float64; any other dtype -- the narrow integers, which NumPy would add to the float32 vectors
@@ -316,19 +343,6 @@ def fill_args(max_dist=None):
         return int(min(np.floor(d * d), np.float64(FILL_MAX_D2)))
 
 
-def fill_valid_array(valid, shape):
-    """A host array given as the `valid` of Flow.fill / fill_flow -> contiguous uint8 (H, W): a NumPy array of bool or uint8
-    with the shape of the flow (TypeError for another type or dtype, ValueError for another shape)."""
-    if not isinstance(valid, np.ndarray):
-        raise TypeError("Error filling flow: valid needs to be a numpy array, got {}".format(type(valid).__name__))
-    if valid.dtype != np.bool_ and valid.dtype != np.uint8:
-        raise TypeError("Error filling flow: valid needs to have dtype bool or uint8, got {}".format(valid.dtype))
-    if valid.shape != (shape[0], shape[1]):
-        raise ValueError("Error filling flow: valid needs to have the shape of the flow, got {} and {}"
-                         .format(valid.shape, (shape[0], shape[1])))
-    return mask_bytes(valid)
-
-
 # -- mask-aware median filter (K16)
 MEDIAN_KSIZES = (3, 5, 7)
 
@@ -337,32 +351,18 @@ def median_args(ksize=5, min_count=None):
     """Validation of the window and the member threshold of a median filter (K16) on the host before any device work
     -> (ksize, min_count) as Python ints: ksize an int in {3, 5, 7}; min_count None -> 1, otherwise an int in
     1 ... ksize^2.  A bool or a non-integer is a TypeError, a value outside its set a ValueError."""
-    if isinstance(ksize, (bool, np.bool_)) or not isinstance(ksize, (int, np.integer)):
+    if not _is_integer(ksize):
         raise TypeError("Error filtering flow: ksize must be an integer, got {}".format(type(ksize).__name__))
     if ksize not in MEDIAN_KSIZES:
         raise ValueError("Error filtering flow: ksize must be 3, 5 or 7, got {}".format(ksize))
     if min_count is None:
         return int(ksize), 1
-    if isinstance(min_count, (bool, np.bool_)) or not isinstance(min_count, (int, np.integer)):
+    if not _is_integer(min_count):
         raise TypeError("Error filtering flow: min_count must be an integer or None, got {}".format(type(min_count).__name__))
     if not 1 <= min_count <= ksize * ksize:
         raise ValueError("Error filtering flow: min_count must be in 1 ... {} for ksize {}, got {}"
                          .format(ksize * ksize, ksize, min_count))
     return int(ksize), int(min_count)
-
-
-def median_mask_array(array, shape, name):
-    """A host array given as the `valid` or the `only` (`name`) of Flow.median / median_flow -> contiguous uint8 (H, W): a
-    NumPy array of bool or uint8 with the shape of the flow (TypeError for another type or dtype, ValueError for another
-    shape)."""
-    if not isinstance(array, np.ndarray):
-        raise TypeError("Error filtering flow: {} needs to be a numpy array, got {}".format(name, type(array).__name__))
-    if array.dtype != np.bool_ and array.dtype != np.uint8:
-        raise TypeError("Error filtering flow: {} needs to have dtype bool or uint8, got {}".format(name, array.dtype))
-    if array.shape != (shape[0], shape[1]):
-        raise ValueError("Error filtering flow: {} needs to have the shape of the flow, got {} and {}"
-                         .format(name, array.shape, (shape[0], shape[1])))
-    return mask_bytes(array)
 
 
 # -- convex upsampling (K17)
@@ -374,7 +374,7 @@ def upsample_args(factor, weights_shape, coarse_shape):
     int in {2, 4, 8} (a bool or a non-integer is a TypeError, another value a ValueError); `weights_shape`: the LOGICAL
     shape of the logits, (C, h, w) or (N, C, h, w), whose channel count must be 9 * factor^2 and whose height and width
     must be those of `coarse_shape`, the (h, w) of the coarse field (ValueError otherwise)."""
-    if isinstance(factor, (bool, np.bool_)) or not isinstance(factor, (int, np.integer)):
+    if not _is_integer(factor):
         raise TypeError("Error upsampling flow: factor must be an integer, got {}".format(type(factor).__name__))
     if factor not in UPSAMPLE_FACTORS:
         raise ValueError("Error upsampling flow: factor must be 2, 4 or 8, got {}".format(factor))
@@ -416,7 +416,7 @@ def corr_args(radius, levels, scale, order, quant, channels, shape):
     number; order: 'xy' or 'yx'; quant: 0 (the 1/32-px snap) or 1 (exact).  A bool or a non-number is a TypeError, a value
     outside its set a ValueError."""
     for name, value in (("radius", radius), ("levels", levels), ("quant", quant)):
-        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        if not _is_integer(value):
             raise TypeError("Error looking up correlation: {} must be an integer, got {}".format(name, type(value).__name__))
     if not 1 <= radius <= 4:
         raise ValueError("Error looking up correlation: radius must be in 1 ... 4, got {}".format(radius))

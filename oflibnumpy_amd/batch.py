@@ -34,15 +34,19 @@ class DeviceFlowBatch:
             self._mask = dev.mask_unpack(self.bits, self.shape[0], self.shape[1], self.n)
         return self._mask
 
+    @classmethod
+    def wrap(cls, n, shape, ref, vecs, mask, bits=None):
+        """A batch on existing buffers: `vecs` and the byte masks `mask`, plus -- `bits` given -- their packed bit planes."""
+        b = cls.__new__(cls)
+        b.n, b.shape, b.ref, b.vecs, b.packed, b.bits, b._mask = n, shape, ref, vecs, bits is not None, bits, mask
+        return b
+
     def pack(self):
         """the same fields with their masks as bit planes (a copy of the masks only; the vectors are shared)"""
         if self.packed:
             return self
-        b = DeviceFlowBatch.__new__(DeviceFlowBatch)
-        b.n, b.shape, b.ref, b.vecs, b.packed = self.n, self.shape, self.ref, self.vecs, True
-        b.bits = dev.mask_pack(self._mask, self.shape[0], self.shape[1], self.n)
-        b._mask = self._mask
-        return b
+        bits = dev.mask_pack(self._mask, self.shape[0], self.shape[1], self.n)
+        return DeviceFlowBatch.wrap(self.n, self.shape, self.ref, self.vecs, self._mask, bits)
 
     @classmethod
     def from_flows(cls, flows, packed=False):
@@ -88,9 +92,7 @@ class DeviceFlowBatch:
         from .utils import get_valid_ref
         ref = get_valid_ref(ref)
         v, m, n, shape = dev.import_flow(vecs, masks, layout, dtype, stream, True, check_finite, batch=True)
-        b = cls.__new__(cls)
-        b.n, b.shape, b.ref, b.vecs, b.packed, b.bits, b._mask = n, shape, ref, v, False, None, m
-        return b
+        return cls.wrap(n, shape, ref, v, m)
 
     def export(self, layout='hwc', dtype='float32', copy=True):
         """The vectors of all fields as ONE DeviceArray: (N, H, W, 2) for 'hwc', (N, 2, H, W) for 'chw', of float32, float16
@@ -159,11 +161,10 @@ class DeviceFlowBatch:
         plus, on request, the int32 index and the uint32 squared distance as DeviceBuffers [n][H][W]; an index counts
         within its own field.  A packed batch is read through its byte masks.  Nothing synchronises."""
         max_d2 = dev.fill_args(max_dist)
-        valid = dev.fill_valid_buffer(valid, self.n * self.shape[0] * self.shape[1])
+        valid = dev.mask_buffer_arg(valid, self.n * self.shape[0] * self.shape[1], "Error filling flow: ", "valid")
         out_vecs, out_mask, index, d2 = dev.fill_launch(self.vecs, self.mask, valid, self.shape, max_d2, batch=self.n,
                                                         want_index=bool(return_index), want_d2=bool(return_d2))
-        b = DeviceFlowBatch.__new__(DeviceFlowBatch)
-        b.n, b.shape, b.ref, b.vecs, b.packed, b.bits, b._mask = self.n, self.shape, self.ref, out_vecs, False, None, out_mask
+        b = DeviceFlowBatch.wrap(self.n, self.shape, self.ref, out_vecs, out_mask)
         extra = ((index,) if return_index else ()) + ((d2,) if return_d2 else ())
         return (b,) + extra if extra else b
 
@@ -174,12 +175,10 @@ class DeviceFlowBatch:
         masks.  Nothing synchronises."""
         ksize, min_count = dev.median_args(ksize, min_count)
         n_bytes = self.n * self.shape[0] * self.shape[1]
-        valid = dev.median_mask_buffer(valid, n_bytes, "valid")
-        only = dev.median_mask_buffer(only, n_bytes, "only")
+        valid = dev.mask_buffer_arg(valid, n_bytes, "Error filtering flow: ", "valid")
+        only = dev.mask_buffer_arg(only, n_bytes, "Error filtering flow: ", "only")
         out_vecs, out_mask = dev.median_launch(self.vecs, self.mask, valid, only, self.shape, ksize, min_count, batch=self.n)
-        b = DeviceFlowBatch.__new__(DeviceFlowBatch)
-        b.n, b.shape, b.ref, b.vecs, b.packed, b.bits, b._mask = self.n, self.shape, self.ref, out_vecs, False, None, out_mask
-        return b
+        return DeviceFlowBatch.wrap(self.n, self.shape, self.ref, out_vecs, out_mask)
 
     def upsample_convex(self, weights, factor=8):
         """self[i].upsample_convex(weights[i], factor) for every i in ONE launch of K17 (DeviceFlow.upsample_convex):
@@ -189,10 +188,7 @@ class DeviceFlowBatch:
         factor = dev.upsample_weights(weights, factor, self.shape, batch=self.n)
         out_vecs, out_mask = dev.upsample_launch(self.vecs, self.mask, weights.buf, weights.dtype, weights.layout, self.shape,
                                                  factor, batch=self.n)
-        b = DeviceFlowBatch.__new__(DeviceFlowBatch)
-        b.n, b.shape, b.ref, b.vecs = self.n, (factor * self.shape[0], factor * self.shape[1]), self.ref, out_vecs
-        b.packed, b.bits, b._mask = False, None, out_mask
-        return b
+        return DeviceFlowBatch.wrap(self.n, (factor * self.shape[0], factor * self.shape[1]), self.ref, out_vecs, out_mask)
 
     def apply_images(self, images, dtype, channels, shared=False, target_masks=None, shared_masks=False, quant=nat.QUANT_OPENCV):
         """self[i].apply(image_i, target_mask_i, return_valid_area=True) for every i in ONE launch of the gather kernel
@@ -331,8 +327,8 @@ class DeviceFlowBatch:
         points and path, DeviceBuffers int32 / uint8 for lost_at and status) or an (n, 2) array (answered with arrays).  The
         fields, and between the steps the points, stay in HBM."""
         int_out, get_valid_status, _ = dev.track_args(pts, int_out, get_valid_status, None)
-        if not isinstance(return_path, bool):
-            raise TypeError("Error tracking points: Return_path needs to be a boolean")
+        # no default to fall back on: None is refused like any other non-bool, as it always was
+        return_path = dev.optional_bool(return_path, None, "Error tracking points: Return_path needs to be a boolean")
         dp, on_host = self._float_points(pts, "DeviceFlowBatch.track_sequence")
         n, B = dp.n, self.n
         out = dev.DevicePoints(dev.DeviceBuffer(n * (8 if int_out else 16)), n, np.int32 if int_out else np.float64)

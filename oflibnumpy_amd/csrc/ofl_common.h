@@ -26,6 +26,13 @@ inline hipStream_t stream_of(void *s) { return s ? (hipStream_t)s : rt().stream;
 // `p` on an `a`-byte boundary (a power of two); a NULL pointer, an absent optional argument, counts as aligned
 inline bool host_aligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 
+// [p, p + n) and [q, q + m) share a byte; an absent (NULL) range shares none
+inline bool overlap(const void *p, size_t n, const void *q, size_t m)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return p && q && a < b + m && b < a + n;
+}
+
 }  // namespace ofl
 
 #define OFL_HIP(call)                                                      \

@@ -256,12 +256,6 @@ void launch_elem2(int elem2, const CArgs &a, int N, bool wide, hipStream_t s)
     else                           launch_pair<E1, OFL_EL_F32>(a, N, wide, s);
 }
 
-inline bool overlap(const void *p, size_t n, const void *q, size_t m)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return p && q && a < b + m && b < a + n;
-}
-
 size_t elem_bytes(int elem) { return elem == OFL_EL_F32 ? 4 : 2; }
 
 bool float_elem(int elem) { return elem == OFL_EL_F16 || elem == OFL_EL_BF16 || elem == OFL_EL_F32; }

@@ -162,13 +162,6 @@ void launch_k(const MArgs &a, dim3 grid, hipStream_t s)
     else         { if (a.only) launch_mask<K, false, true>(mask, a, grid, s); else launch_mask<K, false, false>(mask, a, grid, s); }
 }
 
-// [p, p + n) and [q, q + m) share a byte; an absent (NULL) range shares none
-inline bool overlap(const void *p, size_t n, const void *q, size_t m)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return p && q && a < b + m && b < a + n;
-}
-
 int check_median_args(const char *who, const void *vecs, const void *mask, const void *valid, const void *only, int H, int W,
                       int batch, int ksize, int min_count, const void *out_vecs, const void *out_mask)
 {

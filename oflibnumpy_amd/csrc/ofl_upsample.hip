@@ -215,13 +215,6 @@ void launch_elem(int elem, int layout, const UArgs &a, int batch, hipStream_t s)
     else                          launch_layout<F, OFL_EL_F32>(layout, a, batch, s);
 }
 
-// [p, p + n) and [q, q + m) share a byte; an absent (NULL) range shares none
-inline bool overlap(const void *p, size_t n, const void *q, size_t m)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return p && q && a < b + m && b < a + n;
-}
-
 size_t elem_bytes(int elem) { return elem == OFL_EL_F32 ? 4 : 2; }
 
 int check_upsample_args(const char *who, const void *vecs, const void *mask, const void *logits, int elem, int layout, int h, int w,

@@ -31,8 +31,8 @@ from .memory import (_lib, _ptr, _size_query, _Pool, _PinnedPool, empty_cache, D
 from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rules, mask_bytes, _points_array, visualise_args,
                    percentile_ranks, matrix_args, validate_transforms, valid_mask_array, scale_operand, crop_args,
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
-                   consistency_args, error_args, fill_args, fill_valid_array, median_args, median_mask_array,
-                   upsample_args, upsample_weights_array, corr_args, corr_host_array)
+                   consistency_args, error_args, fill_args, median_args, upsample_args, upsample_weights_array, corr_args,
+                   corr_host_array, optional_bool, mask_array_arg)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
@@ -323,15 +323,9 @@ def track_args(pts, int_out=None, get_valid_status=None, s_exact_mode=None):
     DevicePoints or an (n, 2) array of a dtype DevicePoints.from_host takes."""
     if not isinstance(pts, DevicePoints):
         _points_array(pts)
-    int_out = False if int_out is None else int_out
-    get_valid_status = False if get_valid_status is None else get_valid_status
-    s_exact_mode = False if s_exact_mode is None else s_exact_mode
-    if not isinstance(int_out, bool):
-        raise TypeError("Error tracking points: Int_out needs to be a boolean")
-    if not isinstance(get_valid_status, bool):
-        raise TypeError("Error tracking points: Get_tracked needs to be a boolean")
-    if not isinstance(s_exact_mode, bool):
-        raise TypeError("Error tracking points: S_exact_mode needs to be a boolean")
+    int_out = optional_bool(int_out, False, "Error tracking points: Int_out needs to be a boolean")
+    get_valid_status = optional_bool(get_valid_status, False, "Error tracking points: Get_tracked needs to be a boolean")
+    s_exact_mode = optional_bool(s_exact_mode, False, "Error tracking points: S_exact_mode needs to be a boolean")
     return int_out, get_valid_status, s_exact_mode
 
 
@@ -356,23 +350,14 @@ class DeviceFlowError:
         return stats[0] if self.n is None else stats
 
 
-def fill_valid_buffer(valid, n_bytes):
-    """The `valid` of DeviceFlow.fill / DeviceFlowBatch.fill: None, or a uint8 buffer (DeviceBuffer or a view) of at least
-    n_bytes bytes -- e.g. `consistent` out of a consistency check."""
-    if valid is not None and not isinstance(valid, (DeviceBuffer, _BufferView)):
-        raise TypeError("Error filling flow: valid needs to be a DeviceBuffer of uint8 or None, got {}".format(type(valid).__name__))
-    if valid is not None and valid.nbytes < n_bytes:
-        raise ValueError("Error filling flow: valid needs to hold {} bytes, got {}".format(n_bytes, valid.nbytes))
-    return valid
-
-
-def median_mask_buffer(buf, n_bytes, name):
-    """The `valid` or the `only` (`name`) of DeviceFlow.median / DeviceFlowBatch.median: None, or a uint8 buffer
-    (DeviceBuffer or a view) of at least n_bytes bytes -- e.g. `consistent` out of a consistency check."""
+def mask_buffer_arg(buf, n_bytes, prefix, name):
+    """A device mask argument `name` (the `valid` of DeviceFlow.fill / DeviceFlowBatch.fill, the `valid` or `only` of their
+    median): None, or a uint8 buffer (DeviceBuffer or a view) of at least n_bytes bytes -- e.g. `consistent` out of a
+    consistency check.  `prefix` opens the message, e.g. "Error filling flow: "."""
     if buf is not None and not isinstance(buf, (DeviceBuffer, _BufferView)):
-        raise TypeError("Error filtering flow: {} needs to be a DeviceBuffer of uint8 or None, got {}".format(name, type(buf).__name__))
+        raise TypeError("{}{} needs to be a DeviceBuffer of uint8 or None, got {}".format(prefix, name, type(buf).__name__))
     if buf is not None and buf.nbytes < n_bytes:
-        raise ValueError("Error filtering flow: {} needs to hold {} bytes, got {}".format(name, n_bytes, buf.nbytes))
+        raise ValueError("{}{} needs to hold {} bytes, got {}".format(prefix, name, n_bytes, buf.nbytes))
     return buf
 
 
@@ -710,7 +695,7 @@ class DeviceFlow:
         linear index (-1: none), return_d2 the uint32 DeviceBuffer [H][W] of its squared distance (0xFFFFFFFF: none).
         Not a function of the reference.  Nothing synchronises; the inputs are not modified."""
         max_d2 = fill_args(max_dist)
-        valid = fill_valid_buffer(valid, self.n_px)
+        valid = mask_buffer_arg(valid, self.n_px, "Error filling flow: ", "valid")
         out_vecs, out_mask, index, d2 = fill_launch(self.vecs, self.mask, valid, self.shape, max_d2,
                                                     want_index=bool(return_index), want_d2=bool(return_d2))
         res = DeviceFlow(out_vecs, out_mask, self.shape, self.ref)
@@ -728,8 +713,8 @@ class DeviceFlow:
         the input: nothing is averaged, NaN payloads and -0.0 survive.  -> a DeviceFlow of the same shape and reference.
         Not a function of the reference.  Nothing synchronises; the inputs are not modified."""
         ksize, min_count = median_args(ksize, min_count)
-        valid = median_mask_buffer(valid, self.n_px, "valid")
-        only = median_mask_buffer(only, self.n_px, "only")
+        valid = mask_buffer_arg(valid, self.n_px, "Error filtering flow: ", "valid")
+        only = mask_buffer_arg(only, self.n_px, "Error filtering flow: ", "only")
         out_vecs, out_mask = median_launch(self.vecs, self.mask, valid, only, self.shape, ksize, min_count)
         return DeviceFlow(out_vecs, out_mask, self.shape, self.ref)
 

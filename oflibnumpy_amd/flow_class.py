@@ -109,9 +109,7 @@ class Flow(object):
     def from_kitti(cls, path: str, load_valid: bool = None) -> FlowAlias:
         """KITTI uint16 PNG -> flow with reference 's', optionally with the valid pixels as mask
         (reference flow_class.py:237-259)."""
-        load_valid = True if load_valid is None else load_valid
-        if not isinstance(load_valid, bool):
-            raise TypeError("Error loading flow from KITTI data: Load_valid needs to be boolean")
+        load_valid = dev.optional_bool(load_valid, True, "Error loading flow from KITTI data: Load_valid needs to be boolean")
         data = load_kitti(path)
         return cls(data[..., :2], 's', data[..., 2].astype('bool')) if load_valid else cls(data[..., :2], 's')
 
@@ -228,15 +226,9 @@ class Flow(object):
               ) -> Union[Union[np.ndarray, FlowAlias], Tuple[Union[np.ndarray, FlowAlias], np.ndarray]]:
         """Warp `target` (ndarray (H, W[, C]) or Flow) with this flow.  Arguments, defaults, return
         conventions and raised exception types follow the reference (flow_class.py:528-695)."""
-        return_valid_area = False if return_valid_area is None else return_valid_area
-        if not isinstance(return_valid_area, bool):
-            raise TypeError("Error applying flow: Return_valid_area needs to be a boolean")
-        consider_mask = True if consider_mask is None else consider_mask
-        if not isinstance(consider_mask, bool):
-            raise TypeError("Error applying flow: Consider_mask needs to be a boolean")
-        cut = True if cut is None else cut
-        if not isinstance(cut, bool):
-            raise TypeError("Error applying flow: Cut needs to be a boolean")
+        return_valid_area = dev.optional_bool(return_valid_area, False, "Error applying flow: Return_valid_area needs to be a boolean")
+        consider_mask = dev.optional_bool(consider_mask, True, "Error applying flow: Consider_mask needs to be a boolean")
+        cut = dev.optional_bool(cut, True, "Error applying flow: Cut needs to be a boolean")
         if padding is None:
             if self.shape[0] != target.shape[0] or self.shape[1] != target.shape[1]:
                 raise ValueError("Error applying flow: Flow shape does not match target shape")
@@ -367,9 +359,7 @@ class Flow(object):
               s_exact_mode: bool = None) -> np.ndarray:
         """Warp points (N, 2) in (row, col) order with the flow; optionally also return which points are
         moved by valid vectors to a position inside the flow area (reference flow_class.py:755-795)."""
-        get_valid_status = False if get_valid_status is None else get_valid_status
-        if not isinstance(get_valid_status, bool):
-            raise TypeError("Error tracking points: Get_tracked needs to be a boolean")
+        get_valid_status = dev.optional_bool(get_valid_status, False, "Error tracking points: Get_tracked needs to be a boolean")
         warped = track_pts(flow=self._vecs, ref=self._ref, pts=pts, int_out=int_out, s_exact_mode=s_exact_mode)
         if get_valid_status:
             status = self.valid_source()[np.round(pts[..., 0]).astype('i'), np.round(pts[..., 1]).astype('i')]
@@ -378,17 +368,13 @@ class Flow(object):
 
     def valid_target(self, consider_mask: bool = None) -> np.ndarray:
         """Area of the target domain reached by valid vectors (reference flow_class.py:1113-1151)."""
-        consider_mask = True if consider_mask is None else consider_mask
-        if not isinstance(consider_mask, bool):
-            raise TypeError("Error applying flow: Consider_mask needs to be a boolean")
+        consider_mask = dev.optional_bool(consider_mask, True, "Error applying flow: Consider_mask needs to be a boolean")
         buf = self.to_device().valid_target(consider_mask)
         return buf.to_host(self.shape, np.uint8).view(np.bool_)
 
     def valid_source(self, consider_mask: bool = None) -> np.ndarray:
         """Area of the source domain that ends up valid in the target (reference flow_class.py:1153-1195)."""
-        consider_mask = True if consider_mask is None else consider_mask
-        if not isinstance(consider_mask, bool):
-            raise TypeError("Error applying flow: Consider_mask needs to be a boolean")
+        consider_mask = dev.optional_bool(consider_mask, True, "Error applying flow: Consider_mask needs to be a boolean")
         buf = self.to_device().valid_source(consider_mask)
         return buf.to_host(self.shape, np.uint8).view(np.bool_)
 
@@ -399,12 +385,8 @@ class Flow(object):
 
     def is_zero(self, thresholded: bool = None, masked: bool = None) -> bool:
         """All (masked) vectors zero?  (reference flow_class.py:1230-1245)"""
-        masked = True if masked is None else masked
-        if not isinstance(masked, bool):
-            raise TypeError("Error checking whether flow is zero: Masked needs to be a boolean")
-        thresholded = True if thresholded is None else thresholded
-        if not isinstance(thresholded, bool):
-            raise TypeError("Error checking whether flow is zero: Thresholded needs to be a boolean")
+        masked = dev.optional_bool(masked, True, "Error checking whether flow is zero: Masked needs to be a boolean")
+        thresholded = dev.optional_bool(thresholded, True, "Error checking whether flow is zero: Thresholded needs to be a boolean")
         return self.to_device().is_zero(thresholded, masked)
 
     def visualise(self, mode: str, show_mask: bool = None, show_mask_borders: bool = None,
@@ -437,9 +419,7 @@ class Flow(object):
         |self + sampled| (0 where not covered) with `return_residual`.  Not a function of the reference; the definition,
         which takes no zero-flow short cut, is DeviceFlow.consistency's.  One upload, one launch, one download."""
         alpha, beta = dev.consistency_args(alpha, beta)
-        return_residual = False if return_residual is None else return_residual
-        if not isinstance(return_residual, bool):
-            raise TypeError("Error checking flow consistency: Return_residual needs to be a boolean")
+        return_residual = dev.optional_bool(return_residual, False, "Error checking flow consistency: Return_residual needs to be a boolean")
         if not isinstance(backward, Flow):
             raise TypeError("Error checking flow consistency: Backward needs to be of type 'Flow'")
         if self.shape != backward.shape:
@@ -461,12 +441,8 @@ class Flow(object):
         float32 (H, W) error (0 where not evaluated).  Not a function of the reference; the definition is DeviceFlow.error's.
         One upload, one launch, one download."""
         thr, out, edges, n_thr, n_edges = dev.error_args(thresholds, outlier, speed_edges)
-        use_est_mask = True if use_est_mask is None else use_est_mask
-        return_map = False if return_map is None else return_map
-        if not isinstance(use_est_mask, bool):
-            raise TypeError("Error evaluating flow error: Use_est_mask needs to be a boolean")
-        if not isinstance(return_map, bool):
-            raise TypeError("Error evaluating flow error: Return_map needs to be a boolean")
+        use_est_mask = dev.optional_bool(use_est_mask, True, "Error evaluating flow error: Use_est_mask needs to be a boolean")
+        return_map = dev.optional_bool(return_map, False, "Error evaluating flow error: Return_map needs to be a boolean")
         if not isinstance(gt, Flow):
             raise TypeError("Error evaluating flow error: Gt needs to be of type 'Flow'")
         if self.shape != gt.shape:
@@ -489,13 +465,9 @@ class Flow(object):
         (-1: none), with `return_d2` the uint32 (H, W) squared distance (0xFFFFFFFF: none).  Not a function of the
         reference; the definition is DeviceFlow.fill's.  One upload, two launches, one download."""
         max_d2 = dev.fill_args(max_dist)
-        return_index = False if return_index is None else return_index
-        return_d2 = False if return_d2 is None else return_d2
-        if not isinstance(return_index, bool):
-            raise TypeError("Error filling flow: Return_index needs to be a boolean")
-        if not isinstance(return_d2, bool):
-            raise TypeError("Error filling flow: Return_d2 needs to be a boolean")
-        valid = None if valid is None else dev.fill_valid_array(valid, self.shape)
+        return_index = dev.optional_bool(return_index, False, "Error filling flow: Return_index needs to be a boolean")
+        return_d2 = dev.optional_bool(return_d2, False, "Error filling flow: Return_d2 needs to be a boolean")
+        valid = None if valid is None else dev.mask_array_arg(valid, self.shape, "Error filling flow: ", "valid")
         vecs, mask, index, d2 = dev.fill_host(self._vecs, self._mask, valid, max_d2, return_index, return_d2)
         res = Flow(vecs, self._ref, mask)
         extra = ((index,) if return_index else ()) + ((d2,) if return_d2 else ())
@@ -510,8 +482,8 @@ class Flow(object):
         Flow of the same reference.  Not a function of the reference; the definition is DeviceFlow.median's.  One upload,
         one launch, one download."""
         ksize, min_count = dev.median_args(ksize, min_count)
-        valid = None if valid is None else dev.median_mask_array(valid, self.shape, "valid")
-        only = None if only is None else dev.median_mask_array(only, self.shape, "only")
+        valid = None if valid is None else dev.mask_array_arg(valid, self.shape, "Error filtering flow: ", "valid")
+        only = None if only is None else dev.mask_array_arg(only, self.shape, "Error filtering flow: ", "only")
         vecs, mask = dev.median_host(self._vecs, self._mask, valid, only, ksize, min_count)
         return Flow(vecs, self._ref, mask)
 
@@ -536,9 +508,7 @@ class Flow(object):
             raise ValueError("Error combining flows: Flow fields need to have the same reference")
         if mode not in [1, 2, 3]:
             raise ValueError("Error combining flows: Mode needs to be 1, 2 or 3")
-        thresholded = False if thresholded is None else thresholded
-        if not isinstance(thresholded, bool):
-            raise TypeError("Error combining flows: Thresholded needs to be a boolean")
+        thresholded = dev.optional_bool(thresholded, False, "Error combining flows: Thresholded needs to be a boolean")
 
         d_self, d_flow = self.to_device(), flow.to_device()
         res = d_self.combine_with(d_flow, mode, thresholded)

@@ -228,9 +228,7 @@ def threshold_vectors(vecs: nd, threshold: Union[float, int] = None, use_mag: bo
 def is_zero_flow(flow: nd, thresholded: bool = None) -> bool:
     """True if every (optionally thresholded) vector component is zero (reference utils.py:527-544)."""
     flow = validate_flow_array(flow, "Error checking whether flow is zero: ")
-    thresholded = True if thresholded is None else thresholded
-    if not isinstance(thresholded, bool):
-        raise TypeError("Error checking whether flow is zero: Thresholded needs to be a boolean")
+    thresholded = dev.optional_bool(thresholded, True, "Error checking whether flow is zero: Thresholded needs to be a boolean")
     bits = dev.flow_stats(dev.DeviceBuffer.from_host(flow), None, flow.shape[0] * flow.shape[1])
     return not (bits & (nat.STAT_NONZERO_TH if thresholded else nat.STAT_NONZERO))
 
@@ -310,12 +308,8 @@ def track_pts(flow: nd, ref: str, pts: nd, int_out: bool = None, s_exact_mode: b
         raise TypeError("Error tracking points: Pts needs to be a numpy array")
     if pts.ndim != 2 or pts.shape[1] != 2:
         raise ValueError("Error tracking points: Pts needs to have shape N-2")
-    int_out = False if int_out is None else int_out
-    s_exact_mode = False if s_exact_mode is None else s_exact_mode
-    if not isinstance(int_out, bool):
-        raise TypeError("Error tracking points: Int_out needs to be a boolean")
-    if not isinstance(s_exact_mode, bool):
-        raise TypeError("Error tracking points: S_exact_mode needs to be a boolean")
+    int_out = dev.optional_bool(int_out, False, "Error tracking points: Int_out needs to be a boolean")
+    s_exact_mode = dev.optional_bool(s_exact_mode, False, "Error tracking points: S_exact_mode needs to be a boolean")
 
     if is_zero_flow(flow, thresholded=True):
         warped = pts

@@ -7,18 +7,16 @@ and keep the LDS of a workgroup -- the dots of 32 pixels and their weights -- sm
 residency either."""
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
 from oflibnumpy_amd import build_native as bn
+import kernel_resources
+from kernel_resources import FIELDS
 
 SOURCE = os.path.join(bn.CSRC, "ofl_correlation.hip")
 CORR = re.compile(r"corr_kernelILi(\d)ELi(\d)ELi(n?\d)EE")
 POOL = re.compile(r"avgpool_kernelILi(\d)EE")
-FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "ScratchSize [bytes/lane]": "scratch", "SGPRs Spill": "sgpr_spill",
-          "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds", "Occupancy [waves/SIMD]": "occupancy"}
 LDS_PER_CU = 160 * 1024
 BLOCK_WAVES = 4
 
@@ -29,27 +27,15 @@ def _waves():
     return int(m.group(1))
 
 
+def _key(name):
+    k, p = CORR.search(name), POOL.search(name)
+    assert k or p, "a kernel this test does not know: " + name
+    return ("corr",) + tuple(int(k.group(i).replace("n", "-")) for i in (1, 2, 3)) if k else ("pool", int(p.group(1)))
+
+
 @pytest.fixture(scope="module")
 def usage():
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [bn._hipcc()] + bn.FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                                         "-c", SOURCE, "-o", os.path.join(d, "c.o")]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-4000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k, p = CORR.search(m.group(1)), POOL.search(m.group(1))
-            assert k or p, "a kernel this test does not know: " + m.group(1)
-            cur = ("corr",) + tuple(int(k.group(i).replace("n", "-")) for i in (1, 2, 3)) if k else ("pool", int(p.group(1)))
-            out[cur] = {}
-            continue
-        if cur:
-            m = re.search(r"remark:\s+(.+?): (\d+) \[", line)
-            if m and m.group(1).split(":")[-1].strip() in FIELDS:
-                out[cur][FIELDS[m.group(1).split(":")[-1].strip()]] = int(m.group(2))
-    return out
+    return kernel_resources.usage(SOURCE, _key)
 
 
 def test_every_instantiation_is_found(usage):

@@ -7,7 +7,7 @@ import pytest
 from scipy import ndimage
 
 import oflibnumpy_amd as of
-from oflibnumpy_amd import args, _native as nat
+from oflibnumpy_amd import args
 import fill_ref as F
 
 
@@ -96,13 +96,6 @@ def test_fill_args_value_errors(bad):
 def test_fill_args_type_errors(bad):
     with pytest.raises(TypeError, match="Error filling flow"):
         args.fill_args(bad)
-
-
-def test_symbols_are_in_the_ctypes_table():
-    for name, n_args in (("ofl_fill_workspace_bytes", 4), ("ofl_fill_dev", 14), ("ofl_fill", 11)):
-        assert name in nat.SIGNATURES and len(nat.SIGNATURES[name][1]) == n_args
-        assert hasattr(nat.load(), name)
-    assert nat.ABI_VERSION == 4
 
 
 def test_host_entry_points_check_arguments_before_the_device():

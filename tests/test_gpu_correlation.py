@@ -15,6 +15,8 @@ import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from oflibnumpy_amd.batch import DeviceFlowBatch
 import correlation_ref as K
+import devmem
+from devmem import guarded, read_guarded
 import interop_ref as R
 import tensor_ref as T
 
@@ -28,25 +30,10 @@ PAIRS = [("float32", "float32"), ("float16", "float16"), ("bfloat16", "bfloat16"
 FIELDS = ("none", "zero", "shift", "random", "borders", "outside", "far", "huge")
 
 
-def guarded(nbytes):
-    buf = dev.DeviceBuffer(nbytes + 2 * GUARD)
-    nat.check(nat.load().ofl_memset(buf.ptr, 0xA5, buf.nbytes, None))
-    return buf
-
-
 def place(arr, shift=0):
-    """the bytes of a host array in device memory, `shift` bytes into a fresh buffer -> (buffer, address, array)"""
+    """devmem.place that also keeps the array, for `unchanged` -> (buffer, address, array)"""
     arr = np.ascontiguousarray(arr)
-    buf = dev.DeviceBuffer(arr.nbytes + shift)
-    nat.check(nat.load().ofl_upload(buf.ptr + shift, arr.ctypes.data, arr.nbytes, None))
-    dev.sync()
-    return buf, buf.ptr + shift, arr
-
-
-def read_guarded(buf, size, dtype, shape):
-    raw = buf.to_host((buf.nbytes,), np.uint8)
-    assert (raw[:GUARD] == 0xA5).all() and (raw[GUARD + size:] == 0xA5).all() and raw[GUARD + size:].size == GUARD, "guard bytes"
-    return raw[GUARD:GUARD + size].copy().view(dtype).reshape(shape)
+    return devmem.place(arr, shift) + (arr,)
 
 
 def unchanged(kept):
@@ -81,20 +68,20 @@ def raw_lookup(f1, dt1, f2, dt2, flow, sign, r, levels, scale, order, quant, shi
     level_ptr, level_dt, pooled = [keep[1][1]], [dt2], []
     for l in range(1, levels):
         hl, wl = h >> l, w >> l
-        buf = guarded(n * hl * wl * c * 4)
+        buf = guarded(n * hl * wl * c * 4, GUARD, GUARD)
         nat.check(lib.ofl_avgpool2_dev(level_ptr[-1], EL[level_dt[-1]], n, c, h >> (l - 1), w >> (l - 1), buf.ptr + GUARD, None))
         pooled.append((buf, (n, hl, wl, c)))
         level_ptr.append(buf.ptr + GUARD)
         level_dt.append("float32")
     nch = (2 * r + 1) ** 2
     total = levels * nch
-    out = guarded(n * total * h * w * 4)
+    out = guarded(n * total * h * w * 4, GUARD, GUARD)
     for l in range(levels):
         nat.check(lib.ofl_corr_lookup_dev(keep[0][1], EL[dt1], level_ptr[l], EL[level_dt[l]], n, c, h, w, h >> l, w >> l, l,
                                           None if flow is None else keep[2][1], 1 if shared else 0, sign, r, np.float32(scale),
                                           nat.CORR_XY if order == "xy" else nat.CORR_YX, quant, out.ptr + GUARD, total, l * nch, None))
-    res = read_guarded(out, n * total * h * w * 4, np.float32, (n, total, h, w))
-    levels_host = [read_guarded(b, int(np.prod(s)) * 4, np.float32, s) for b, s in pooled]
+    res = read_guarded(out, GUARD, n * total * h * w * 4, GUARD, np.float32, (n, total, h, w))
+    levels_host = [read_guarded(b, GUARD, int(np.prod(s)) * 4, GUARD, np.float32, s) for b, s in pooled]
     for k in keep:
         unchanged(k)
     return (res if batched else res[0]), levels_host
@@ -228,8 +215,8 @@ def test_refusals_write_nothing(gpu):
     h, w, c, r = 4, 6, 8, 1
     f1, f2, flow = K.features((h, w), c, "float32", 0), K.features((h, w), c, "float32", 1), K.fields((h, w), r)["random"]
     k1, k2, kf = place(f1), place(f2), place(flow)
-    out = guarded(2 * 9 * h * w * 4)
-    pooled = guarded(2 * 3 * c * 4)
+    out = guarded(2 * 9 * h * w * 4, GUARD, GUARD)
+    pooled = guarded(2 * 3 * c * 4, GUARD, GUARD)
     good = dict(f1=k1[1], elem1=nat.EL_F32, f2=k2[1], elem2=nat.EL_F32, N=1, C=c, H=h, W=w, Hl=h, Wl=w, level=0, flow=kf[1], shared=1,
                 sign=1, r=r, scale=np.float32(1.0), order=nat.CORR_XY, quant=nat.QUANT_EXACT, out=out.ptr + GUARD, total=18, first=9)
     order = ("f1", "elem1", "f2", "elem2", "N", "C", "H", "W", "Hl", "Wl", "level", "flow", "shared", "sign", "r", "scale", "order",

@@ -13,6 +13,7 @@ import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from oflibnumpy_amd.batch import DeviceFlowBatch
 from oflibnumpy_amd.kernels import ERROR_RECORD
+from devmem import guarded, read_guarded
 import error_ref as E
 
 pytestmark = pytest.mark.gpu
@@ -32,13 +33,6 @@ def workspace(shape, batch):
     return dev.DeviceBuffer(n), n
 
 
-def guarded(nbytes):
-    """a buffer of nbytes + GUARD bytes, every byte 0xA5"""
-    buf = dev.DeviceBuffer(nbytes + GUARD)
-    nat.check(nat.load().ofl_memset(buf.ptr, 0xA5, buf.nbytes, None))
-    return buf
-
-
 def raw_call(ptrs, shape, batch=1, est_mask=True, epe_map=True, outlier_map=True, thr=E.THR, out=(E.OUT_ABS, E.OUT_REL), edges=E.EDGES,
              map_shift=(0, 0)):
     """ofl_flow_error_dev on device addresses (est, em, gt, gm) -> (records, epe_map | None, outlier_map | None) on the host.
@@ -48,8 +42,8 @@ def raw_call(ptrs, shape, batch=1, est_mask=True, epe_map=True, outlier_map=True
     est, em, gt, gm = ptrs
     work, nbytes = workspace(shape, batch)
     rec = dev.DeviceBuffer(batch * 96)
-    d_epe = guarded(n * 4 + map_shift[0]) if epe_map else None
-    d_out = guarded(n + map_shift[1]) if outlier_map else None
+    d_epe = guarded(n * 4, GUARD, map_shift[0]) if epe_map else None
+    d_out = guarded(n, GUARD, map_shift[1]) if outlier_map else None
     thr, edges = np.ascontiguousarray(thr, np.float32), np.ascontiguousarray(edges, np.float32)
     nat.check(nat.load().ofl_flow_error_dev(est, em if est_mask else None, gt, gm, h, w, batch, thr.ctypes.data, np.float32(out[0]),
                                             np.float32(out[1]), edges.ctypes.data, work.ptr, nbytes, rec.ptr,
@@ -58,9 +52,7 @@ def raw_call(ptrs, shape, batch=1, est_mask=True, epe_map=True, outlier_map=True
     res = [rec.to_host((batch,), ERROR_RECORD), None, None]
     for k, (buf, size, shift, dtype) in enumerate(((d_epe, n * 4, map_shift[0], np.float32), (d_out, n, map_shift[1], np.uint8))):
         if buf is not None:
-            raw = buf.to_host((buf.nbytes,), np.uint8)
-            assert (raw[:shift] == 0xA5).all() and (raw[shift + size:] == 0xA5).all() and raw[shift + size:].size >= GUARD, "guard bytes"
-            res[k + 1] = raw[shift:shift + size].copy().view(dtype).reshape(full)
+            res[k + 1] = read_guarded(buf, shift, size, GUARD, dtype, full)
     return tuple(res)
 
 

@@ -11,34 +11,13 @@ import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from oflibnumpy_amd.batch import DeviceFlowBatch
 import consistency_ref as C
+from devmem import guarded, place, read_guarded
 import fill_ref as F
 
 pytestmark = pytest.mark.gpu
 nat = of.native
 GUARD = 64
 ALL_OUTPUTS = (True, True, True, True)                     # out_vecs, out_mask, index, d2
-
-
-def guarded(nbytes):
-    """a buffer of nbytes + GUARD bytes, every byte 0xA5"""
-    buf = dev.DeviceBuffer(nbytes + GUARD)
-    nat.check(nat.load().ofl_memset(buf.ptr, 0xA5, buf.nbytes, None))
-    return buf
-
-
-def place(arr, shift=0):
-    """the bytes of a host array in device memory, `shift` bytes into a fresh buffer -> (buffer, address)"""
-    arr = np.ascontiguousarray(arr)
-    buf = dev.DeviceBuffer(arr.nbytes + shift)
-    nat.check(nat.load().ofl_upload(buf.ptr + shift, arr.ctypes.data, arr.nbytes, None))
-    dev.sync()
-    return buf, buf.ptr + shift
-
-
-def read_guarded(buf, shift, size, dtype, shape):
-    raw = buf.to_host((buf.nbytes,), np.uint8)
-    assert (raw[:shift] == 0xA5).all() and (raw[shift + size:] == 0xA5).all() and raw[shift + size:].size >= GUARD, "guard bytes"
-    return raw[shift:shift + size].copy().view(dtype).reshape(shape)
 
 
 def workspace(shape, batch):
@@ -57,18 +36,18 @@ def raw_call(vecs, mask, valid, shape, batch=1, max_d2=-1, outputs=ALL_OUTPUTS, 
     if mask_shift:
         assert keep[1][1] % 2 == 1
     work, nbytes = workspace(shape, batch)
-    d_v = guarded(n * 8) if want_v else None
-    d_m = guarded(n + out_shift) if want_m else None
-    d_i = guarded(n * 4) if want_i else None
-    d_d = guarded(n * 4) if want_d else None
+    d_v = guarded(n * 8, GUARD) if want_v else None
+    d_m = guarded(n, GUARD, out_shift) if want_m else None
+    d_i = guarded(n * 4, GUARD) if want_i else None
+    d_d = guarded(n * 4, GUARD) if want_d else None
     ptr = lambda b, s=0: None if b is None else b.ptr + s
     nat.check(nat.load().ofl_fill_dev(keep[0][1] if want_v else None, keep[1][1], keep[2][1] if valid is not None else None, h, w, batch,
                                       max_d2, work.ptr, nbytes, ptr(d_v), ptr(d_m, out_shift), ptr(d_i), ptr(d_d), None))
     full = (batch, h, w) if batch > 1 else (h, w)
-    res = (read_guarded(d_v, 0, n * 8, np.float32, full + (2,)) if want_v else None,
-           read_guarded(d_m, out_shift, n, np.uint8, full) if want_m else None,
-           read_guarded(d_i, 0, n * 4, np.int32, full) if want_i else None,
-           read_guarded(d_d, 0, n * 4, np.uint32, full) if want_d else None)
+    res = (read_guarded(d_v, 0, n * 8, GUARD, np.float32, full + (2,)) if want_v else None,
+           read_guarded(d_m, out_shift, n, GUARD, np.uint8, full) if want_m else None,
+           read_guarded(d_i, 0, n * 4, GUARD, np.int32, full) if want_i else None,
+           read_guarded(d_d, 0, n * 4, GUARD, np.uint32, full) if want_d else None)
     # the inputs are unchanged
     for kept, a in zip(keep, (vecs, mask, valid)):
         if kept is not None:
@@ -216,7 +195,7 @@ def test_raw_entry_refuses_bad_arguments_without_launching(gpu):
     n = h * w
     vec, msk = dev.DeviceBuffer.zeros(n * 8), dev.DeviceBuffer.zeros(n)
     work, nbytes = workspace((h, w), 1)
-    outs = [guarded(n * 8), guarded(n), guarded(n * 4), guarded(n * 4)]
+    outs = [guarded(n * 8, GUARD), guarded(n, GUARD), guarded(n * 4, GUARD), guarded(n * 4, GUARD)]
     o_v, o_m, o_i, o_d = [b.ptr for b in outs]
 
     def call(vecs=vec.ptr, mask=msk.ptr, valid=None, h=h, w=w, batch=1, max_d2=-1, ws=work.ptr, ws_bytes=nbytes, out_vecs=o_v, out_mask=o_m,

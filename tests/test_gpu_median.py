@@ -13,6 +13,7 @@ import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from oflibnumpy_amd.batch import DeviceFlowBatch
 import consistency_ref as C
+from devmem import guarded, place, read_guarded
 import fill_ref as F
 import median_ref as M
 
@@ -20,28 +21,6 @@ pytestmark = pytest.mark.gpu
 nat = of.native
 GUARD = 64
 COMBOS = list(itertools.product((False, True), repeat=3))          # valid, only, out_mask: the eight instantiations per ksize
-
-
-def guarded(nbytes):
-    """a buffer of nbytes + GUARD bytes, every byte 0xA5"""
-    buf = dev.DeviceBuffer(nbytes + GUARD)
-    nat.check(nat.load().ofl_memset(buf.ptr, 0xA5, buf.nbytes, None))
-    return buf
-
-
-def place(arr, shift=0):
-    """the bytes of a host array in device memory, `shift` bytes into a fresh buffer -> (buffer, address)"""
-    arr = np.ascontiguousarray(arr)
-    buf = dev.DeviceBuffer(arr.nbytes + shift)
-    nat.check(nat.load().ofl_upload(buf.ptr + shift, arr.ctypes.data, arr.nbytes, None))
-    dev.sync()
-    return buf, buf.ptr + shift
-
-
-def read_guarded(buf, shift, size, dtype, shape):
-    raw = buf.to_host((buf.nbytes,), np.uint8)
-    assert (raw[:shift] == 0xA5).all() and (raw[shift + size:] == 0xA5).all() and raw[shift + size:].size >= GUARD, "guard bytes"
-    return raw[shift:shift + size].copy().view(dtype).reshape(shape)
 
 
 def raw_call(vecs, mask, valid, only, shape, ksize, min_count=1, batch=1, want_mask=True, mask_shift=0, out_shift=0):
@@ -53,13 +32,13 @@ def raw_call(vecs, mask, valid, only, shape, ksize, min_count=1, batch=1, want_m
     keep = [None if a is None else place(a, s) for a, s in zip(arrays, (0, mask_shift, mask_shift + 2, mask_shift + 4))]
     if mask_shift % 2:
         assert keep[1][1] % 2 == 1
-    d_v = guarded(n * 8)
-    d_m = guarded(n + out_shift) if want_mask else None
+    d_v = guarded(n * 8, GUARD)
+    d_m = guarded(n, GUARD, out_shift) if want_mask else None
     addr = lambda k: None if k is None else k[1]
     nat.check(nat.load().ofl_median_dev(addr(keep[0]), addr(keep[1]), addr(keep[2]), addr(keep[3]), h, w, batch, ksize, min_count,
                                         d_v.ptr, None if d_m is None else d_m.ptr + out_shift, None))
     full = (batch, h, w) if batch > 1 else (h, w)
-    res = (read_guarded(d_v, 0, n * 8, np.float32, full + (2,)), read_guarded(d_m, out_shift, n, np.uint8, full) if want_mask else None)
+    res = (read_guarded(d_v, 0, n * 8, GUARD, np.float32, full + (2,)), read_guarded(d_m, out_shift, n, GUARD, np.uint8, full) if want_mask else None)
     for kept, a in zip(keep, arrays):                                   # the inputs are unchanged
         if kept is not None:
             a = np.ascontiguousarray(a)
@@ -188,7 +167,7 @@ def test_raw_entry_refuses_bad_arguments_without_launching(gpu):
     h, w = 6, 9
     n = h * w
     vec, msk, aux = dev.DeviceBuffer.zeros(n * 8 + 64), dev.DeviceBuffer.zeros(n + 8), dev.DeviceBuffer.zeros(n + 8)
-    outs = [guarded(n * 8), guarded(n)]
+    outs = [guarded(n * 8, GUARD), guarded(n, GUARD)]
     o_v, o_m = [b.ptr for b in outs]
 
     def call(vecs=vec.ptr, mask=msk.ptr, valid=None, only=None, h=h, w=w, batch=1, ksize=3, min_count=1, out_vecs=o_v, out_mask=o_m):

@@ -21,6 +21,7 @@ import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from oflibnumpy_amd.batch import DeviceFlowBatch
 import consistency_ref as C
+from devmem import guarded, place, read_guarded
 import interop_ref as R
 import upsample_ref as U
 
@@ -31,28 +32,6 @@ ELEMS = ("float32", "float16", "bfloat16")
 LAYOUTS = ("chw", "hwc")
 EL = {"float32": nat.EL_F32, "float16": nat.EL_F16, "bfloat16": nat.EL_BF16}
 LAY = {"chw": nat.TENSOR_NCHW, "hwc": nat.TENSOR_NHWC}
-
-
-def guarded(nbytes):
-    """a buffer of nbytes + 2 * GUARD bytes, every byte 0xA5; the output starts GUARD bytes in"""
-    buf = dev.DeviceBuffer(nbytes + 2 * GUARD)
-    nat.check(nat.load().ofl_memset(buf.ptr, 0xA5, buf.nbytes, None))
-    return buf
-
-
-def place(arr, shift=0):
-    """the bytes of a host array in device memory, `shift` bytes into a fresh buffer -> (buffer, address)"""
-    arr = np.ascontiguousarray(arr)
-    buf = dev.DeviceBuffer(arr.nbytes + shift)
-    nat.check(nat.load().ofl_upload(buf.ptr + shift, arr.ctypes.data, arr.nbytes, None))
-    dev.sync()
-    return buf, buf.ptr + shift
-
-
-def read_guarded(buf, size, dtype, shape):
-    raw = buf.to_host((buf.nbytes,), np.uint8)
-    assert (raw[:GUARD] == 0xA5).all() and (raw[GUARD + size:] == 0xA5).all() and raw[GUARD + size:].size == GUARD, "guard bytes"
-    return raw[GUARD:GUARD + size].copy().view(dtype).reshape(shape)
 
 
 def raw_call(v, m, x, elem, layout, f, want_mask=True, shifted=False):
@@ -68,12 +47,12 @@ def raw_call(v, m, x, elem, layout, f, want_mask=True, shifted=False):
     if shifted:
         assert keep[2][1] % 16 == xm.itemsize and keep[1][1] % 2 == 1
     n = batch * f * h * f * w
-    d_v = guarded(n * 8)
-    d_m = guarded(n) if want_mask else None
+    d_v = guarded(n * 8, GUARD, GUARD)
+    d_m = guarded(n, GUARD, GUARD) if want_mask else None
     nat.check(nat.load().ofl_upsample_convex_dev(keep[0][1], keep[1][1], keep[2][1], EL[elem], LAY[layout], h, w, batch, f,
                                                  d_v.ptr + GUARD, None if d_m is None else d_m.ptr + GUARD, None))
     full = ((batch,) if v.ndim == 4 else ()) + (f * h, f * w)
-    res = (read_guarded(d_v, n * 8, np.float32, full + (2,)), read_guarded(d_m, n, np.uint8, full) if want_mask else None)
+    res = (read_guarded(d_v, GUARD, n * 8, GUARD, np.float32, full + (2,)), read_guarded(d_m, GUARD, n, GUARD, np.uint8, full) if want_mask else None)
     for kept, a in zip(keep, arrays):                                   # the inputs are unchanged
         got = kept[0].to_host((kept[0].nbytes,), np.uint8)[kept[1] - kept[0].ptr:][:a.nbytes]
         assert got.tobytes() == a.tobytes(), "an input was written"
@@ -184,7 +163,7 @@ def test_refusals_write_nothing(gpu):
     v, m, x, _ = case(shape, f, "float32", 1.0)
     kv, km, kx = place(v), place(m), place(x)
     n = f * f * shape[0] * shape[1]
-    d_v, d_m = guarded(n * 8), guarded(n)
+    d_v, d_m = guarded(n * 8, GUARD, GUARD), guarded(n, GUARD, GUARD)
     ov, om = d_v.ptr + GUARD, d_m.ptr + GUARD
     good = dict(vecs=kv[1], mask=km[1], logits=kx[1], elem=nat.EL_F32, layout=nat.TENSOR_NCHW, h=3, w=5, batch=1, factor=2,
                 out_vecs=ov, out_mask=om)

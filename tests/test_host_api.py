@@ -31,6 +31,50 @@ def test_abi_exports_every_declared_symbol():
     assert nat.load().ofl_abi_version() == nat.ABI_VERSION == 4
 
 
+_C_CLASS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double,
+            "int64_t": ctypes.c_int64}
+
+
+def _ctypes_class(t):
+    """a ctypes type -> 'pointer' or the name of its C scalar type"""
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return {v: k for k, v in _C_CLASS.items()}[t]
+
+
+def header_prototypes():
+    """{name: (return class, [parameter classes])} of every declaration of include/ofl.h: a parameter with a '*' or a '['
+    (const float thr[4]) is a pointer, any other is named by its type without `const`"""
+    text = open(os.path.join(ROOT, "include", "ofl.h")).read()
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    out = {}
+    for ret, name, params in re.findall(r"\b(int|const char \*)\s*(ofl_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in out, name
+        classes = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            words = [w for w in p.split() if w != "const"]
+            assert len(words) >= 2, (name, p)
+            classes.append("pointer" if "*" in p or "[" in p else " ".join(words[:-1]))
+        out[name] = ("int" if ret == "int" else "pointer", classes)
+    return out
+
+
+def test_ctypes_table_agrees_with_the_header_type_by_type():
+    """Every row of _native.SIGNATURES -- return type, argument count and per argument pointer / int / size_t / float /
+    double / int64_t -- is what include/ofl.h declares, and load() attaches exactly the table's argtypes.  A c_int written
+    where the header says size_t would load and mis-pass arguments silently."""
+    protos = header_prototypes()
+    assert set(protos) == set(header_symbols()) == set(nat.SIGNATURES)
+    lib = nat.load()
+    for name, (res, args) in nat.SIGNATURES.items():
+        want_res, want_args = protos[name]
+        assert set(want_args) <= {"pointer"} | set(_C_CLASS), (name, want_args)
+        assert _ctypes_class(res) == want_res, name
+        assert [_ctypes_class(a) for a in args] == want_args, name
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name
+
+
 def test_shipped_library_is_lean():
     """The product library reads no environment knobs and carries no A/B kernel variants.  The one test hook,
     OFL_DL_NEAR2_MIN, is read only by the experiments build (libofl_hip_exp.so), which a subprocess test loads through OFL_LIB."""

@@ -12,11 +12,11 @@ import tempfile
 import pytest
 
 from oflibnumpy_amd import build_native as bn
+import kernel_resources
+from kernel_resources import FIELDS
 
 GATHER = os.path.join(bn.CSRC, "ofl_gather.hip")
 KERNEL = re.compile(r"compose3_xpose_kernelILi([01])ELb([01])ELb0E")
-FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "ScratchSize [bytes/lane]": "scratch", "SGPRs Spill": "sgpr_spill",
-          "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds"}
 
 
 def _waves():
@@ -25,27 +25,14 @@ def _waves():
     return int(m.group(1))
 
 
+def _key(name):
+    k = KERNEL.search(name)
+    return (int(k.group(1)), bool(int(k.group(2)))) if k else None
+
+
 @pytest.fixture(scope="module")
 def usage():
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [bn._hipcc()] + bn.FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                                         "-c", GATHER, "-o", os.path.join(d, "g.o")]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-4000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k = KERNEL.search(m.group(1))
-            cur = (int(k.group(1)), bool(int(k.group(2)))) if k else None
-            if cur:
-                out[cur] = {}
-            continue
-        if cur:
-            m = re.search(r"remark:\s+(.+?): (\d+) \[", line)
-            if m and m.group(1) in FIELDS:
-                out[cur][FIELDS[m.group(1)]] = int(m.group(2))
-    return out
+    return kernel_resources.usage(GATHER, _key)
 
 
 @pytest.mark.parametrize("quant", [0, 1])

@@ -169,29 +169,22 @@ def test_median_args_min_count_errors():
 
 @pytest.mark.parametrize("name", ["valid", "only"])
 def test_median_mask_array(name):
-    a = args.median_mask_array(np.ones((4, 6), bool), (4, 6), name)
+    a = args.mask_array_arg(np.ones((4, 6), bool), (4, 6), "Error filtering flow: ", name)
     assert a.dtype == np.uint8 and a.shape == (4, 6) and a.flags.c_contiguous and a.all()
-    assert args.median_mask_array(np.zeros((4, 6), np.uint8), (4, 6, 2), name).dtype == np.uint8
+    assert args.mask_array_arg(np.zeros((4, 6), np.uint8), (4, 6, 2), "Error filtering flow: ", name).dtype == np.uint8
     with pytest.raises(ValueError, match=r"{}.*\(4, 5\).*\(4, 6\)".format(name)):
-        args.median_mask_array(np.ones((4, 5), bool), (4, 6), name)
+        args.mask_array_arg(np.ones((4, 5), bool), (4, 6), "Error filtering flow: ", name)
     with pytest.raises(ValueError, match=name):
-        args.median_mask_array(np.ones((4, 6, 1), bool), (4, 6), name)
+        args.mask_array_arg(np.ones((4, 6, 1), bool), (4, 6), "Error filtering flow: ", name)
     with pytest.raises(TypeError, match=name + ".*float32"):
-        args.median_mask_array(np.ones((4, 6), np.float32), (4, 6), name)
+        args.mask_array_arg(np.ones((4, 6), np.float32), (4, 6), "Error filtering flow: ", name)
     with pytest.raises(TypeError, match=name):
-        args.median_mask_array(np.ones((4, 6), np.int32), (4, 6), name)
+        args.mask_array_arg(np.ones((4, 6), np.int32), (4, 6), "Error filtering flow: ", name)
     with pytest.raises(TypeError, match=name):
-        args.median_mask_array([[True] * 6] * 4, (4, 6), name)
+        args.mask_array_arg([[True] * 6] * 4, (4, 6), "Error filtering flow: ", name)
 
 
-# ---------------------------------------------------------------------------------------------- the table, the host forms
-def test_symbols_are_in_the_ctypes_table():
-    for name, n_args in (("ofl_median_dev", 12), ("ofl_median", 11)):
-        assert name in nat.SIGNATURES and len(nat.SIGNATURES[name][1]) == n_args
-        assert hasattr(nat.load(), name)
-    assert nat.ABI_VERSION == 4
-
-
+# ---------------------------------------------------------------------------------------------- the host forms
 def test_host_entry_points_check_arguments_before_the_device():
     """Flow.median and median_flow raise for bad arguments without a device (this suite has none)"""
     f = of.Flow.zero((4, 6), 't')

@@ -6,17 +6,15 @@ window lives in a register array that only a sorting network with constant indic
 dynamically gets scratch and fails here before it reaches the hardware."""
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
 from oflibnumpy_amd import build_native as bn
+import kernel_resources
+from kernel_resources import FIELDS
 
 MEDIAN = os.path.join(bn.CSRC, "ofl_median.hip")
 KERNEL = re.compile(r"median_kernelILi(\d)ELb([01])ELb([01])ELb([01])E")
-FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "ScratchSize [bytes/lane]": "scratch", "SGPRs Spill": "sgpr_spill",
-          "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds", "Occupancy [waves/SIMD]": "occupancy"}
 
 
 def _waves(ksize):
@@ -25,28 +23,15 @@ def _waves(ksize):
     return int(m.group(1)) if ksize == 7 else int(m.group(2))
 
 
+def _key(name):
+    k = KERNEL.search(name)
+    assert k or "median" not in name, "a median kernel this test does not know: " + name
+    return (int(k.group(1)),) + tuple(bool(int(k.group(i))) for i in (2, 3, 4)) if k else None
+
+
 @pytest.fixture(scope="module")
 def usage():
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [bn._hipcc()] + bn.FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                                         "-c", MEDIAN, "-o", os.path.join(d, "m.o")]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-4000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k = KERNEL.search(m.group(1))
-            assert k or "median" not in m.group(1), "a median kernel this test does not know: " + m.group(1)
-            cur = (int(k.group(1)),) + tuple(bool(int(k.group(i))) for i in (2, 3, 4)) if k else None
-            if cur:
-                out[cur] = {}
-            continue
-        if cur:
-            m = re.search(r"remark:\s+(.+?): (\d+) \[", line)
-            if m and m.group(1) in FIELDS:
-                out[cur][FIELDS[m.group(1)]] = int(m.group(2))
-    return out
+    return kernel_resources.usage(MEDIAN, _key)
 
 
 def test_every_instantiation_is_found(usage):

@@ -24,9 +24,7 @@ def field(shape, ref='t'):
 
 
 def batch(n, shape, ref='t'):
-    b = DeviceFlowBatch.__new__(DeviceFlowBatch)
-    b.n, b.shape, b.ref, b.vecs, b.packed, b.bits, b._mask = n, shape, ref, None, False, None, None
-    return b
+    return DeviceFlowBatch.wrap(n, shape, ref, None, None)
 
 
 def test_tensor_args_accepts_and_decodes():

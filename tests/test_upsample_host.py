@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import oflibnumpy_amd as of
-from oflibnumpy_amd import args, _native as nat
+from oflibnumpy_amd import args
 import upsample_ref as U
 
 HOST_SPREADS = (1.0, 8.0, 32.0, 80.0)
@@ -150,14 +150,7 @@ def test_upsample_args_value_errors(factor, wshape, cshape, what):
         args.upsample_args(factor, wshape, cshape)
 
 
-# ---------------------------------------------------------------------------------------------- the table, the host forms
-def test_symbols_are_in_the_ctypes_table():
-    for name, n_args in (("ofl_upsample_convex_dev", 12), ("ofl_upsample_convex", 11)):
-        assert name in nat.SIGNATURES and len(nat.SIGNATURES[name][1]) == n_args
-        assert hasattr(nat.load(), name)
-    assert nat.ABI_VERSION == 4
-
-
+# ---------------------------------------------------------------------------------------------- the host forms
 def test_host_forms_check_arguments_before_the_device():
     f = of.Flow.zero((3, 4), 't')
     good = np.zeros((36, 3, 4), np.float32)

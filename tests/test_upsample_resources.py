@@ -5,17 +5,15 @@ use no scratch, spill nothing, fit the waves per SIMD its __launch_bounds__ name
 staged coarse neighbourhood plus the band of fine rows -- small enough that LDS does not limit that residency either."""
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
 from oflibnumpy_amd import build_native as bn
+import kernel_resources
+from kernel_resources import FIELDS
 
 UPSAMPLE = os.path.join(bn.CSRC, "ofl_upsample.hip")
 KERNEL = re.compile(r"upsample_kernelILi(\d)ELi(\d)ELi(\d)EE")
-FIELDS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "ScratchSize [bytes/lane]": "scratch", "SGPRs Spill": "sgpr_spill",
-          "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds", "Occupancy [waves/SIMD]": "occupancy"}
 LDS_PER_CU = 160 * 1024
 NCHW = 0
 
@@ -31,28 +29,15 @@ def _block_waves(factor, layout):
     return min(factor, 4) if layout == NCHW else 4
 
 
+def _key(name):
+    k = KERNEL.search(name)
+    assert k or "upsample" not in name, "an upsample kernel this test does not know: " + name
+    return tuple(int(k.group(i)) for i in (1, 2, 3)) if k else None
+
+
 @pytest.fixture(scope="module")
 def usage():
-    with tempfile.TemporaryDirectory() as d:
-        cmd = [bn._hipcc()] + bn.FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                                         "-c", UPSAMPLE, "-o", os.path.join(d, "u.o")]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-4000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k = KERNEL.search(m.group(1))
-            assert k or "upsample" not in m.group(1), "an upsample kernel this test does not know: " + m.group(1)
-            cur = tuple(int(k.group(i)) for i in (1, 2, 3)) if k else None
-            if cur:
-                out[cur] = {}
-            continue
-        if cur:
-            m = re.search(r"remark:\s+(.+?): (\d+) \[", line)
-            if m and m.group(1) in FIELDS:
-                out[cur][FIELDS[m.group(1)]] = int(m.group(2))
-    return out
+    return kernel_resources.usage(UPSAMPLE, _key)
 
 
 def test_every_instantiation_is_found(usage):

@@ -17,7 +17,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
@@ -27,22 +26,11 @@ import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from oflibnumpy_amd.batch import DeviceFlowBatch
 from bench_ops import n_sets, timed
+from bench_kit import wall
 
 nat = of.native
 TRANSFORMS = [['rotation', 960, 540, -30], ['scaling', 400, 300, 0.9], ['translation', 20, 10]]
 PROJECTIVE = np.array([[1.02, 0.01, 3.0], [-0.02, 0.98, -2.0], [1e-5, -2e-5, 1.0]])
-
-
-def wall(fn, iters, warm=1):
-    """seconds per call by the host clock, every call followed by a device synchronise"""
-    for _ in range(warm):
-        fn()
-        dev.sync()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-        dev.sync()
-    return (time.perf_counter() - t0) / iters
 
 
 def copy_rate(nbytes_moved, iters):
@@ -82,7 +70,7 @@ def main():
         shape, n = (h, w), h * w
         # ---- the constructor end to end against the route it replaces
         t_dev = wall(lambda: dev.DeviceFlow.from_transforms(TRANSFORMS, shape, 't'), a.iters, warm=3)
-        t_host = wall(lambda: of.Flow.from_transforms(TRANSFORMS, shape, 't').to_device(), a.host_iters)
+        t_host = wall(lambda: of.Flow.from_transforms(TRANSFORMS, shape, 't').to_device(), a.host_iters, warm=1)
         got = dev.DeviceFlow.from_transforms(TRANSFORMS, shape, 't').to_host()[0]
         want = of.Flow.from_transforms(TRANSFORMS, shape, 't').vecs
         emit({"key": "build_%s_from_transforms" % name, "op": "DeviceFlow.from_transforms vs Flow.from_transforms(...).to_device()",

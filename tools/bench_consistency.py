@@ -20,9 +20,6 @@ compose kernel's own repeats in this run, the margin below which a difference sa
 
     python tools/bench_consistency.py [--repeats 16] [--out profiles/r12_consistency_bench.jsonl]
 """
-import argparse
-import ctypes
-import json
 import os
 import sys
 
@@ -33,6 +30,7 @@ import numpy as np
 import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from bench_ops import n_sets
+import bench_kit as kit
 
 nat = of.native
 ALPHA, BETA = np.float32(0.01), np.float32(0.5)
@@ -67,26 +65,7 @@ def upload_pairs(h, w, n, seed, f, fm, b, bm):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=16)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    nat.ensure_device()
-    lib = nat.load()
-    e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
-    nat.check(lib.ofl_event_create(ctypes.byref(e0)))
-    nat.check(lib.ofl_event_create(ctypes.byref(e1)))
-
-    def one_launch(fn):
-        nat.check(lib.ofl_event_record(e0, None))
-        nat.check(fn())
-        nat.check(lib.ofl_event_record(e1, None))
-        nat.check(lib.ofl_event_sync(e1))
-        ms = ctypes.c_float()
-        nat.check(lib.ofl_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
-        return ms.value
-
-    lines = []
+    a, lib, timer, report = kit.start(16)
     for name, h, w, n in (("4k_x8", 2160, 3840, 8), ("1080p_x16", 1080, 1920, 16)):
         px = n * h * w
         k = n_sets(20 * px)
@@ -100,45 +79,36 @@ def main():
             sets.append(bufs)
 
         def consistency(q, width, residual):
-            return lambda: lib.ofl_consistency_dev(q["f"].ptr, q["fm"].ptr, q["b"].ptr, q["bm"].ptr, -1, h, width, n, ALPHA, BETA,
-                                                   q["con"].ptr, q["cov"].ptr, q["res"].ptr if residual else None, None,
-                                                   nat.QUANT_OPENCV, None)
+            return lambda: nat.check(lib.ofl_consistency_dev(q["f"].ptr, q["fm"].ptr, q["b"].ptr, q["bm"].ptr, -1, h, width, n, ALPHA, BETA,
+                                                             q["con"].ptr, q["cov"].ptr, q["res"].ptr if residual else None, None,
+                                                             nat.QUANT_OPENCV, None))
 
         variants = [
             ("consistency_masks", 20, lambda q: consistency(q, w, False)),
             ("consistency_residual", 24, lambda q: consistency(q, w, True)),
             ("consistency_masks_odd", 20, lambda q: consistency(q, w - 1, False)),
-            ("compose3", 27, lambda q: (lambda: lib.ofl_compose3_dev(q["b"].ptr, q["bm"].ptr, q["f"].ptr, q["fm"].ptr, -1, h, w, n,
-                                                                     q["out"].ptr, q["mout"].ptr, None, nat.QUANT_OPENCV, None))),
-            ("copy_20Bpx", 20, lambda q: (lambda: lib.ofl_copy_dev(q["c1"].ptr, q["c0"].ptr, px * 10, None))),
+            ("compose3", 27, lambda q: (lambda: nat.check(lib.ofl_compose3_dev(q["b"].ptr, q["bm"].ptr, q["f"].ptr, q["fm"].ptr, -1, h, w, n,
+                                                                               q["out"].ptr, q["mout"].ptr, None, nat.QUANT_OPENCV, None)))),
+            ("copy_20Bpx", 20, kit.copy_variant(px * 10)),
         ]
-        ms = {key: [] for key, _, _ in variants}
-        for r in range(-2, a.repeats):                      # two warm-up rounds over every variant
-            for key, _, make in variants:
-                t = one_launch(make(sets[r % k]))
-                if r >= 0:
-                    ms[key].append(t)
+        ms = kit.interleaved(timer, [(key, make) for key, _, make in variants], sets, a.repeats)
         # the kernel's covered mask is the compose kernel's, also at this size
         q = sets[(a.repeats - 1) % k]
-        nat.check(consistency(q, w, False)())
+        consistency(q, w, False)()
         same = bool(np.array_equal(q["cov"].to_host((px,), np.uint8), q["mout"].to_host((px,), np.uint8)))
-        med = {key: float(np.median(v)) for key, v in ms.items()}
-        spread = (max(ms["compose3"]) - min(ms["compose3"])) / med["compose3"]
+        med, spread = kit.median_ms(ms), kit.spread(ms["compose3"])
         for key, bpp, _ in variants:
             width = w - 1 if key.endswith("_odd") else w
             moved = bpp * n * h * width
-            lines.append(json.dumps({
+            report.line({
                 "key": "%s_%s" % (key, name), "shape": [h, width], "pairs": n, "bytes_per_px": bpp, "bytes_moved": int(moved),
-                "device_ms_median": round(med[key], 4), "device_ms_min": round(min(ms[key]), 4), "device_ms_max": round(max(ms[key]), 4),
+                **kit.ms_fields(ms[key]),
                 "GBps": round(moved / med[key] / 1e6, 1), "repeats": a.repeats, "rotating_sets": k,
                 "over_compose3": round(med[key] / med["compose3"], 3), "compose3_spread": round(spread, 3),
-                "covered_equals_compose3_mask": same, "device": nat.device_name()}))
-            print(lines[-1], flush=True)
+                "covered_equals_compose3_mask": same, "device": nat.device_name()})
         del sets, q
         dev.empty_cache()
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    report.write(a.out)
 
 
 if __name__ == "__main__":

@@ -23,19 +23,18 @@ also says what the definition's arithmetic and traffic amount to:
 
     python tools/bench_correlation.py [--repeats 12] [--out profiles/r17_correlation_bench.jsonl]
 """
-import argparse
-import ctypes
-import json
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
 import numpy as np
 import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from oflibnumpy_amd.batch import DeviceFlowBatch
+import bench_kit as kit
 import correlation_ref as K
 
 nat = of.native
@@ -46,37 +45,12 @@ FP32_VECTOR_PEAK = 157.3e12
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=12)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    nat.ensure_device()
-    lib = nat.load()
-    e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
-    nat.check(lib.ofl_event_create(ctypes.byref(e0)))
-    nat.check(lib.ofl_event_create(ctypes.byref(e1)))
-
-    def one_call(fn):
-        nat.check(lib.ofl_event_record(e0, None))
-        keep = fn()
-        nat.check(lib.ofl_event_record(e1, None))
-        nat.check(lib.ofl_event_sync(e1))
-        ms = ctypes.c_float()
-        nat.check(lib.ofl_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
-        del keep
-        return ms.value
+    a, lib, timer, report = kit.start(12)
 
     def replicated(arr, n):
         """n copies of a host array back to back in one device buffer"""
-        arr = np.ascontiguousarray(arr)
-        buf = dev.DeviceBuffer(n * arr.nbytes)
-        nat.check(lib.ofl_upload(buf.ptr, arr.ctypes.data, arr.nbytes, None))
-        nat.check(lib.ofl_stream_sync(None))
-        for i in range(1, n):
-            nat.check(lib.ofl_copy_dev(buf.ptr + i * arr.nbytes, buf.ptr, arr.nbytes, None))
-        return buf
+        return kit.replicate(dev.DeviceBuffer(n * arr.nbytes), arr, n)
 
-    lines = []
     nch = LEVELS * (2 * RADIUS + 1) ** 2
     for c, h, w, dt in ((256, 136, 240, "float16"), (256, 136, 240, "float32"), (128, 270, 480, "float16")):
         for n in (1, 8):
@@ -93,41 +67,32 @@ def main():
                 for name, arr in (("f1", f1), ("f2", f2)):
                     q[name, "hwc"] = dev.DeviceTensor(replicated(arr, n), (n, c, h, w), dt, "hwc")
                     q[name, "chw"] = dev.DeviceTensor(replicated(np.moveaxis(arr, -1, 0), n), (n, c, h, w), dt, "chw")
-                batch = DeviceFlowBatch.__new__(DeviceFlowBatch)
-                batch.n, batch.shape, batch.ref, batch.packed, batch.bits, batch._mask = n, (h, w), 's', False, None, None
-                batch.vecs = replicated(flow, n)
-                q["flow"] = batch
+                q["flow"] = DeviceFlowBatch.wrap(n, (h, w), 's', replicated(flow, n), None)
                 q["corr"] = of.DeviceCorrelation.build(q["f1", "hwc"], q["f2", "hwc"], LEVELS)
                 q["c0"], q["c1"] = dev.DeviceBuffer(out_bytes), dev.DeviceBuffer(out_bytes)
                 nat.check(lib.ofl_memset(q["c0"].ptr, 1, out_bytes, None))
                 first = first or (f1, f2, flow)
                 sets.append(q)
             variants = [
-                ("lookup", lambda q: q["corr"].lookup(q["flow"], RADIUS)),
-                ("build_hwc", lambda q: of.DeviceCorrelation.build(q["f1", "hwc"], q["f2", "hwc"], LEVELS)),
-                ("build_chw", lambda q: of.DeviceCorrelation.build(q["f1", "chw"], q["f2", "chw"], LEVELS)),
-                ("copy", lambda q: nat.check(lib.ofl_copy_dev(q["c1"].ptr, q["c0"].ptr, out_bytes, None))),
+                ("lookup", lambda q: (lambda: q["corr"].lookup(q["flow"], RADIUS))),
+                ("build_hwc", lambda q: (lambda: of.DeviceCorrelation.build(q["f1", "hwc"], q["f2", "hwc"], LEVELS))),
+                ("build_chw", lambda q: (lambda: of.DeviceCorrelation.build(q["f1", "chw"], q["f2", "chw"], LEVELS))),
+                ("copy", kit.copy_variant(out_bytes)),
             ]
-            ms = {key: [] for key, _ in variants}
-            for r in range(-2, a.repeats):                      # two warm-up rounds over every variant
-                for key, fn in variants:
-                    t = one_call(lambda: fn(sets[r % SETS]))
-                    if r >= 0:
-                        ms[key].append(t)
+            ms = kit.interleaved(timer, variants, sets, a.repeats)
             f1, f2, flow = first
             got = sets[0]["corr"].lookup(sets[0]["flow"], RADIUS).to_host()[0][:, :CROP[0], :CROP[1]]
             want = K.lookup(K.widen(f1[:CROP[0], :CROP[1]], dt), K.widen(f2, dt), flow[:CROP[0], :CROP[1]], 1, RADIUS, LEVELS)
             same = bool(np.ascontiguousarray(got).tobytes() == want.tobytes())
-            med = {key: float(np.median(v)) for key, v in ms.items()}
-            spread = (max(ms["copy"]) - min(ms["copy"])) / med["copy"]
+            med, spread = kit.median_ms(ms), kit.spread(ms["copy"])
             taps = (2 * RADIUS + 2) ** 2
             flop = 2.0 * taps * c * LEVELS * px * n
             f2_bytes = float(taps * c * px * n * (e + 4 * (LEVELS - 1)))
             volume = sum(n * px * (h >> l) * (w >> l) * 4 for l in range(LEVELS))
             for key, _ in variants:
                 line = {"key": "%s_%s_c%d_%dx%d_x%d" % (key, dt, c, h, w, n), "features": [c, h, w], "dtype": dt, "items": n,
-                        "radius": RADIUS, "levels": LEVELS, "device_ms_median": round(med[key], 4), "device_ms_min": round(min(ms[key]), 4),
-                        "device_ms_max": round(max(ms[key]), 4), "repeats": a.repeats, "rotating_sets": SETS, "device": nat.device_name()}
+                        "radius": RADIUS, "levels": LEVELS, **kit.ms_fields(ms[key]), "repeats": a.repeats, "rotating_sets": SETS,
+                        "device": nat.device_name()}
                 if key == "lookup":
                     t = med[key] * 1e-3
                     line.update({"flop": flop, "TFLOPs": round(flop / t / 1e12, 3), "share_fp32_vec": round(flop / t / FP32_VECTOR_PEAK, 4),
@@ -137,13 +102,10 @@ def main():
                 if key == "copy":
                     line.update({"bytes_moved": 2 * out_bytes, "TBps": round(2 * out_bytes / (med[key] * 1e-3) / 1e12, 3),
                                  "copy_spread": round(spread, 3)})
-                lines.append(json.dumps(line))
-                print(lines[-1], flush=True)
+                report.line(line)
             del sets, q
             dev.empty_cache()
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    report.write(a.out)
 
 
 if __name__ == "__main__":

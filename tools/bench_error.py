@@ -23,9 +23,6 @@ to_host() calls (17 B/px each over PCIe) plus the NumPy restatement of tests/err
 
     python tools/bench_error.py [--repeats 16] [--out profiles/r13_error_bench.jsonl]
 """
-import argparse
-import ctypes
-import json
 import os
 import sys
 import time
@@ -38,6 +35,7 @@ import numpy as np
 import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from bench_ops import n_sets
+import bench_kit as kit
 import error_ref
 
 nat = of.native
@@ -55,27 +53,8 @@ def generate(h, w, seed):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=16)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    nat.ensure_device()
-    lib = nat.load()
-    e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
-    nat.check(lib.ofl_event_create(ctypes.byref(e0)))
-    nat.check(lib.ofl_event_create(ctypes.byref(e1)))
+    a, lib, timer, report = kit.start(16)
     thr, (out_abs, out_rel), edges, _, _ = dev.error_args()
-
-    def one_launch(fn):
-        nat.check(lib.ofl_event_record(e0, None))
-        nat.check(fn())
-        nat.check(lib.ofl_event_record(e1, None))
-        nat.check(lib.ofl_event_sync(e1))
-        ms = ctypes.c_float()
-        nat.check(lib.ofl_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
-        return ms.value
-
-    lines = []
     for name, h, w, n in (("4k_x8", 2160, 3840, 8), ("1080p_x16", 1080, 1920, 16)):
         px1, px = h * w, n * h * w
         k = n_sets(18 * px)
@@ -87,48 +66,38 @@ def main():
                  "c0": dev.DeviceBuffer(px * 9), "c1": dev.DeviceBuffer(px * 9)}
             pair = generate(h, w, 100 + s)
             first = first or pair
-            for key, arr, step in (("est", pair[0], px1 * 8), ("em", pair[1], px1), ("gt", pair[2], px1 * 8), ("gm", pair[3], px1)):
-                nat.check(lib.ofl_upload(q[key].ptr, arr.ctypes.data, step, None))
-                nat.check(lib.ofl_stream_sync(None))
-                for i in range(1, n):
-                    nat.check(lib.ofl_copy_dev(q[key].ptr + i * step, q[key].ptr, step, None))
+            for key, arr in zip(("est", "em", "gt", "gm"), pair):
+                kit.replicate(q[key], arr, n)
             nat.check(lib.ofl_memset(q["c0"].ptr, 1, px * 9, None))
             sets.append(q)
 
         def error(q, odd, with_map):
-            return lambda: lib.ofl_flow_error_dev(q["est"].ptr, q["em"].ptr, q["gt"].ptr, q["gm"].ptr, h - odd, w - odd, n, thr.ctypes.data, out_abs,
-                                                  out_rel, edges.ctypes.data, q["work"].ptr, nbytes, q["rec"].ptr,
-                                                  q["epe"].ptr if with_map else None, None, None)
+            return lambda: nat.check(lib.ofl_flow_error_dev(q["est"].ptr, q["em"].ptr, q["gt"].ptr, q["gm"].ptr, h - odd, w - odd, n, thr.ctypes.data,
+                                                            out_abs, out_rel, edges.ctypes.data, q["work"].ptr, nbytes, q["rec"].ptr,
+                                                            q["epe"].ptr if with_map else None, None, None))
 
         variants = [
             ("error_records", 18, lambda q: error(q, 0, False)),
             ("error_epe_map", 22, lambda q: error(q, 0, True)),
             ("error_records_odd", 18, lambda q: error(q, 1, False)),
-            ("copy_18Bpx", 18, lambda q: (lambda: lib.ofl_copy_dev(q["c1"].ptr, q["c0"].ptr, px * 9, None))),
+            ("copy_18Bpx", 18, kit.copy_variant(px * 9)),
         ]
-        ms = {key: [] for key, _, _ in variants}
-        for r in range(-2, a.repeats):                      # two warm-up rounds over every variant
-            for key, _, make in variants:
-                t = one_launch(make(sets[r % k]))
-                if r >= 0:
-                    ms[key].append(t)
+        ms = kit.interleaved(timer, [(key, make) for key, _, make in variants], sets, a.repeats)
         # the records of the timed buffers are the restatement's, also at this size (the first pair of the first set)
-        nat.check(error(sets[0], 0, False)())
+        error(sets[0], 0, False)()
         rec = sets[0]["rec"].to_host((n,), dev.ERROR_RECORD)[0]
         want = error_ref.flow_error(*first, thr, out_abs, out_rel, edges)
         same = np.frombuffer(rec.tobytes()[:48], np.uint32).tolist() == error_ref.record_words(want)
-        med = {key: float(np.median(v)) for key, v in ms.items()}
-        spread = (max(ms["copy_18Bpx"]) - min(ms["copy_18Bpx"])) / med["copy_18Bpx"]
+        med, spread = kit.median_ms(ms), kit.spread(ms["copy_18Bpx"])
         for key, bpp, _ in variants:
             height, width = (h - 1, w - 1) if key.endswith("_odd") else (h, w)
             moved = bpp * n * height * width
-            lines.append(json.dumps({
+            report.line({
                 "key": "%s_%s" % (key, name), "shape": [height, width], "pairs": n, "bytes_per_px": bpp, "bytes_moved": int(moved),
-                "device_ms_median": round(med[key], 4), "device_ms_min": round(min(ms[key]), 4), "device_ms_max": round(max(ms[key]), 4),
+                **kit.ms_fields(ms[key]),
                 "TBps": round(moved / med[key] / 1e9, 3), "repeats": a.repeats, "rotating_sets": k,
                 "over_copy": round(med[key] / med["copy_18Bpx"], 3), "copy_spread": round(spread, 3),
-                "counts_equal_restatement": bool(same), "device": nat.device_name()}))
-            print(lines[-1], flush=True)
+                "counts_equal_restatement": bool(same), "device": nat.device_name()})
         # the route this replaces, one pair: both fields over PCIe, then NumPy
         d_est = dev.DeviceFlow(sets[0]["est"].view(0, px1 * 8), sets[0]["em"].view(0, px1), (h, w), 't')
         d_gt = dev.DeviceFlow(sets[0]["gt"].view(0, px1 * 8), sets[0]["gm"].view(0, px1), (h, w), 't')
@@ -137,15 +106,12 @@ def main():
         t1 = time.perf_counter()
         error_ref.flow_error(ev, em, gv, gm, thr, out_abs, out_rel, edges)
         t2 = time.perf_counter()
-        lines.append(json.dumps({"key": "host_route_%s" % name, "shape": [h, w], "pairs": 1, "to_host_ms": round((t1 - t0) * 1e3, 1),
-                                 "numpy_ms": round((t2 - t1) * 1e3, 1), "wall_ms_per_pair": round((t2 - t0) * 1e3, 1),
-                                 "device_ms_per_pair": round(med["error_records"] / n, 4), "device": nat.device_name()}))
-        print(lines[-1], flush=True)
+        report.line({"key": "host_route_%s" % name, "shape": [h, w], "pairs": 1, "to_host_ms": round((t1 - t0) * 1e3, 1),
+                     "numpy_ms": round((t2 - t1) * 1e3, 1), "wall_ms_per_pair": round((t2 - t0) * 1e3, 1),
+                     "device_ms_per_pair": round(med["error_records"] / n, 4), "device": nat.device_name()})
         del sets, q, d_est, d_gt
         dev.empty_cache()
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    report.write(a.out)
 
 
 if __name__ == "__main__":

@@ -21,19 +21,18 @@ the fancy index, to_device().
 
     python tools/bench_fill.py [--repeats 16] [--out profiles/r14_fill_bench.jsonl]
 """
-import argparse
-import ctypes
-import json
 import os
 import sys
 import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
 import numpy as np
 from scipy import ndimage
 import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
+import bench_kit as kit
 
 nat = of.native
 SETS = 2
@@ -65,26 +64,7 @@ def one_source(h, w, rng):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=16)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    nat.ensure_device()
-    lib = nat.load()
-    e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
-    nat.check(lib.ofl_event_create(ctypes.byref(e0)))
-    nat.check(lib.ofl_event_create(ctypes.byref(e1)))
-
-    def one_launch(fn):
-        nat.check(lib.ofl_event_record(e0, None))
-        nat.check(fn())
-        nat.check(lib.ofl_event_record(e1, None))
-        nat.check(lib.ofl_event_sync(e1))
-        ms = ctypes.c_float()
-        nat.check(lib.ofl_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
-        return ms.value
-
-    lines = []
+    a, lib, timer, report = kit.start(16)
     for name, h, w, n in (("4k_x8", 2160, 3840, 8), ("1080p_x16", 1080, 1920, 16)):
         px1, px = h * w, n * h * w
         patterns = [("fill_blobs", blobs), ("fill_kitti", kitti)] + ([("fill_one_source", one_source)] if h == 1080 else [])
@@ -95,48 +75,39 @@ def main():
             q = {"vecs": dev.DeviceBuffer(px * 8), "out_vecs": dev.DeviceBuffer(px * 8), "out_mask": dev.DeviceBuffer(px),
                  "work": dev.DeviceBuffer(nbytes), "c0": dev.DeviceBuffer(px * 9), "c1": dev.DeviceBuffer(px * 9)}
             vecs = rng.standard_normal((h, w, 2), np.float32) * np.float32(8)
-            arrays = [("vecs", vecs, px1 * 8)]
+            arrays = [("vecs", vecs)]
             for key, make in patterns:
                 q[key] = dev.DeviceBuffer(px)
                 mask = make(h, w, rng)
-                arrays.append((key, mask, px1))
+                arrays.append((key, mask))
                 first.setdefault(key, (vecs, mask))
-            for key, arr, step in arrays:
-                nat.check(lib.ofl_upload(q[key].ptr, arr.ctypes.data, step, None))
-                nat.check(lib.ofl_stream_sync(None))
-                for i in range(1, n):
-                    nat.check(lib.ofl_copy_dev(q[key].ptr + i * step, q[key].ptr, step, None))
+            for key, arr in arrays:
+                kit.replicate(q[key], arr, n)
             nat.check(lib.ofl_memset(q["c0"].ptr, 1, px * 9, None))
             sets.append(q)
 
         def fill(q, key, d2=None):
-            return lambda: lib.ofl_fill_dev(q["vecs"].ptr, q[key].ptr, None, h, w, n, -1, q["work"].ptr, nbytes, q["out_vecs"].ptr,
-                                            q["out_mask"].ptr, None, None if d2 is None else d2.ptr, None)
+            return lambda: nat.check(lib.ofl_fill_dev(q["vecs"].ptr, q[key].ptr, None, h, w, n, -1, q["work"].ptr, nbytes, q["out_vecs"].ptr,
+                                                      q["out_mask"].ptr, None, None if d2 is None else d2.ptr, None))
 
         variants = [(key, (lambda key: lambda q: fill(q, key))(key)) for key, _ in patterns]
-        variants.append(("copy_18Bpx", lambda q: (lambda: lib.ofl_copy_dev(q["c1"].ptr, q["c0"].ptr, px * 9, None))))
-        ms = {key: [] for key, _ in variants}
-        for r in range(-2, a.repeats):                      # two warm-up rounds over every variant
-            for key, make in variants:
-                t = one_launch(make(sets[r % SETS]))
-                if r >= 0:
-                    ms[key].append(t)
+        variants.append(("copy_18Bpx", kit.copy_variant(px * 9)))
+        ms = kit.interleaved(timer, variants, sets, a.repeats)
         # the distances of the timed buffers are SciPy's, also at this size (the first field of the first set)
         same = {}
         d2 = dev.DeviceBuffer(px * 4)
         for key, _ in patterns:
-            nat.check(fill(sets[0], key, d2)())
+            fill(sets[0], key, d2)()
             got = d2.to_host((h, w), np.uint32)
             want = np.rint(ndimage.distance_transform_edt(first[key][1] == 0) ** 2).astype(np.int64)
             same[key] = bool(np.array_equal(got.astype(np.int64), want))
             filled = sets[0]["out_mask"].to_host((h, w), np.uint8)
             same[key] = same[key] and bool(filled.all())
         del d2
-        med = {key: float(np.median(v)) for key, v in ms.items()}
-        spread = (max(ms["copy_18Bpx"]) - min(ms["copy_18Bpx"])) / med["copy_18Bpx"]
+        med, spread = kit.median_ms(ms), kit.spread(ms["copy_18Bpx"])
         for key, _ in variants:
             line = {"key": "%s_%s" % (key, name), "shape": [h, w], "fields": n,
-                    "device_ms_median": round(med[key], 4), "device_ms_min": round(min(ms[key]), 4), "device_ms_max": round(max(ms[key]), 4),
+                    **kit.ms_fields(ms[key]),
                     "repeats": a.repeats, "rotating_sets": SETS, "over_copy": round(med[key] / med["copy_18Bpx"], 3),
                     "copy_spread": round(spread, 3), "device": nat.device_name()}
             if key in same:
@@ -144,8 +115,7 @@ def main():
                              "invalid_share": round(float((first[key][1] == 0).mean()), 4), "d2_equal_scipy": same[key]})
             else:
                 line.update({"bytes_per_px": 18, "TBps": round(18 * px / med[key] / 1e9, 3)})
-            lines.append(json.dumps(line))
-            print(lines[-1], flush=True)
+            report.line(line)
         if h == 2160:
             # the route this replaces, one field: over PCIe, SciPy's transform with indices, the fancy index, back over PCIe
             vecs, mask = first["fill_blobs"]
@@ -160,17 +130,14 @@ def main():
             back = dev.DeviceFlow.from_host(filled, 't')
             dev.sync()
             t4 = time.perf_counter()
-            lines.append(json.dumps({"key": "host_route_%s" % name, "shape": [h, w], "fields": 1, "to_host_ms": round((t1 - t0) * 1e3, 1),
-                                     "scipy_edt_ms": round((t2 - t1) * 1e3, 1), "index_ms": round((t3 - t2) * 1e3, 1),
-                                     "to_device_ms": round((t4 - t3) * 1e3, 1), "wall_ms_per_field": round((t4 - t0) * 1e3, 1),
-                                     "device_ms_per_field": round(med["fill_blobs"] / n, 4), "device": nat.device_name()}))
-            print(lines[-1], flush=True)
+            report.line({"key": "host_route_%s" % name, "shape": [h, w], "fields": 1, "to_host_ms": round((t1 - t0) * 1e3, 1),
+                         "scipy_edt_ms": round((t2 - t1) * 1e3, 1), "index_ms": round((t3 - t2) * 1e3, 1),
+                         "to_device_ms": round((t4 - t3) * 1e3, 1), "wall_ms_per_field": round((t4 - t0) * 1e3, 1),
+                         "device_ms_per_field": round(med["fill_blobs"] / n, 4), "device": nat.device_name()})
             del d_flow, back
         del sets, q
         dev.empty_cache()
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    report.write(a.out)
 
 
 if __name__ == "__main__":

@@ -25,7 +25,8 @@ import numpy as np
 import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from bench_ops import n_sets, timed
-from bench_build import wall, copy_rate
+from bench_build import copy_rate
+from bench_kit import wall
 
 nat = of.native
 
@@ -118,7 +119,7 @@ def main():
 
         same = bool(np.array_equal(resident().to_host().view(np.uint16), through_the_host().to_host((2, h, w), np.uint16)))
         t_dev = wall(resident, a.iters, warm=3)
-        t_host = wall(through_the_host, a.host_iters)
+        t_host = wall(through_the_host, a.host_iters, warm=1)
         emit({"key": "roundtrip_%s_f16_planar" % name, "op": "from_external + export vs download, from_host, to_host, upload",
               "shape": [h, w], "resident_wall_ms": round(t_dev * 1e3, 4), "host_route_wall_ms": round(t_host * 1e3, 2),
               "speedup": round(t_host / t_dev, 1), "bit_identical": same,

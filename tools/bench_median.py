@@ -21,21 +21,20 @@ component, to_device().
 
     python tools/bench_median.py [--repeats 16] [--out profiles/r15_median_bench.jsonl]
 """
-import argparse
-import ctypes
-import json
 import os
 import sys
 import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
 import numpy as np
 from scipy import ndimage
 import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from bench_fill import blobs
+import bench_kit as kit
 import median_ref as M
 
 nat = of.native
@@ -53,26 +52,7 @@ def random50(h, w, rng):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=16)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    nat.ensure_device()
-    lib = nat.load()
-    e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
-    nat.check(lib.ofl_event_create(ctypes.byref(e0)))
-    nat.check(lib.ofl_event_create(ctypes.byref(e1)))
-
-    def one_launch(fn):
-        nat.check(lib.ofl_event_record(e0, None))
-        nat.check(fn())
-        nat.check(lib.ofl_event_record(e1, None))
-        nat.check(lib.ofl_event_sync(e1))
-        ms = ctypes.c_float()
-        nat.check(lib.ofl_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
-        return ms.value
-
-    lines = []
+    a, lib, timer, report = kit.start(16)
     for name, h, w, n in (("4k_x8", 2160, 3840, 8), ("1080p_x16", 1080, 1920, 16)):
         px1, px = h * w, n * h * w
         patterns = [("all", all_valid), ("random50", random50), ("blobs", blobs)]
@@ -82,38 +62,30 @@ def main():
             q = {"vecs": dev.DeviceBuffer(px * 8), "out_vecs": dev.DeviceBuffer(px * 8), "out_mask": dev.DeviceBuffer(px),
                  "c0": dev.DeviceBuffer(px * 9), "c1": dev.DeviceBuffer(px * 9)}
             vecs = rng.standard_normal((h, w, 2), np.float32) * np.float32(8)
-            arrays = [("vecs", vecs, px1 * 8)]
+            arrays = [("vecs", vecs)]
             for key, make in patterns:
                 q[key] = dev.DeviceBuffer(px)
                 mask = make(h, w, rng)
-                arrays.append((key, mask, px1))
+                arrays.append((key, mask))
                 first.setdefault(key, (vecs, mask))
-            for key, arr, step in arrays:
-                nat.check(lib.ofl_upload(q[key].ptr, arr.ctypes.data, step, None))
-                nat.check(lib.ofl_stream_sync(None))
-                for i in range(1, n):
-                    nat.check(lib.ofl_copy_dev(q[key].ptr + i * step, q[key].ptr, step, None))
+            for key, arr in arrays:
+                kit.replicate(q[key], arr, n)
             nat.check(lib.ofl_memset(q["c0"].ptr, 1, px * 9, None))
             sets.append(q)
 
         def median(q, key, ksize):
-            return lambda: lib.ofl_median_dev(q["vecs"].ptr, q[key].ptr, None, None, h, w, n, ksize, 1, q["out_vecs"].ptr,
-                                              q["out_mask"].ptr, None)
+            return lambda: nat.check(lib.ofl_median_dev(q["vecs"].ptr, q[key].ptr, None, None, h, w, n, ksize, 1, q["out_vecs"].ptr,
+                                                        q["out_mask"].ptr, None))
 
         variants = [("median%d_%s" % (k, key), (lambda key, k: lambda q: median(q, key, k))(key, k)) for k in KSIZES for key, _ in patterns]
-        variants.append(("copy_18Bpx", lambda q: (lambda: lib.ofl_copy_dev(q["c1"].ptr, q["c0"].ptr, px * 9, None))))
-        ms = {key: [] for key, _ in variants}
-        for r in range(-2, a.repeats):                      # two warm-up rounds over every variant
-            for key, make in variants:
-                t = one_launch(make(sets[r % SETS]))
-                if r >= 0:
-                    ms[key].append(t)
+        variants.append(("copy_18Bpx", kit.copy_variant(px * 9)))
+        ms = kit.interleaved(timer, variants, sets, a.repeats)
         # the timed buffers give the restatement's bytes, also at this size (a corner of the first field of the first set)
         same = {}
         ch, cw = CROP
         for k in KSIZES:
             for key, _ in patterns:
-                nat.check(median(sets[0], key, k)())
+                median(sets[0], key, k)()
                 got_v = sets[0]["out_vecs"].view(0, px1 * 8).to_host((h, w, 2), np.float32)[:ch, :cw]
                 got_m = sets[0]["out_mask"].view(0, px1).to_host((h, w), np.uint8)[:ch, :cw]
                 vecs, mask = first[key]
@@ -121,20 +93,17 @@ def main():
                 want_v, want_m, _ = M.median(vecs[:ch + r, :cw + r], mask[:ch + r, :cw + r], k)
                 same["median%d_%s" % (k, key)] = bool(got_v.tobytes() == np.ascontiguousarray(want_v[:ch, :cw]).tobytes()
                                                       and np.array_equal(got_m, want_m[:ch, :cw]))
-        med = {key: float(np.median(v)) for key, v in ms.items()}
-        lo, hi = min(ms["copy_18Bpx"]), max(ms["copy_18Bpx"])
-        spread = (hi - lo) / med["copy_18Bpx"]
+        med, spread = kit.median_ms(ms), kit.spread(ms["copy_18Bpx"])
         for key, _ in variants:
             line = {"key": "%s_%s" % (key, name), "shape": [h, w], "fields": n,
-                    "device_ms_median": round(med[key], 4), "device_ms_min": round(min(ms[key]), 4), "device_ms_max": round(max(ms[key]), 4),
+                    **kit.ms_fields(ms[key]),
                     "repeats": a.repeats, "rotating_sets": SETS, "over_copy": round(med[key] / med["copy_18Bpx"], 3),
                     "copy_spread": round(spread, 3), "bytes_per_px": 18, "TBps": round(18 * px / med[key] / 1e9, 3),
                     "device": nat.device_name()}
             if key in same:
                 line.update({"within_copy_spread": bool(med[key] <= med["copy_18Bpx"] * (1 + spread)),
                              "valid_share": round(float(first[key.split("_", 1)[1]][1].mean()), 4), "equal_restatement": same[key]})
-            lines.append(json.dumps(line))
-            print(lines[-1], flush=True)
+            report.line(line)
         if h == 2160:
             # the route this replaces, one field: over PCIe, SciPy's median filter per component (no masks), back over PCIe
             d_flow = dev.DeviceFlow(sets[0]["vecs"].view(0, px1 * 8), sets[0]["all"].view(0, px1), (h, w), 't')
@@ -146,17 +115,14 @@ def main():
             back = dev.DeviceFlow.from_host(filtered, 't')
             dev.sync()
             t3 = time.perf_counter()
-            lines.append(json.dumps({"key": "host_route_%s" % name, "shape": [h, w], "fields": 1, "ksize": 5, "to_host_ms": round((t1 - t0) * 1e3, 1),
-                                     "scipy_median_filter_ms": round((t2 - t1) * 1e3, 1), "to_device_ms": round((t3 - t2) * 1e3, 1),
-                                     "wall_ms_per_field": round((t3 - t0) * 1e3, 1),
-                                     "device_ms_per_field": round(med["median5_all"] / n, 4), "device": nat.device_name()}))
-            print(lines[-1], flush=True)
+            report.line({"key": "host_route_%s" % name, "shape": [h, w], "fields": 1, "ksize": 5, "to_host_ms": round((t1 - t0) * 1e3, 1),
+                         "scipy_median_filter_ms": round((t2 - t1) * 1e3, 1), "to_device_ms": round((t3 - t2) * 1e3, 1),
+                         "wall_ms_per_field": round((t3 - t0) * 1e3, 1),
+                         "device_ms_per_field": round(med["median5_all"] / n, 4), "device": nat.device_name()})
             del d_flow, back
         del sets, q
         dev.empty_cache()
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    report.write(a.out)
 
 
 if __name__ == "__main__":

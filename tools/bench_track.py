@@ -19,7 +19,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
@@ -29,21 +28,10 @@ import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
 from oflibnumpy_amd.batch import DeviceFlowBatch
 from bench_ops import timed
+from bench_kit import wall
 
 nat = of.native
 COUNTS = (10 ** 4, 10 ** 5, 10 ** 6)
-
-
-def wall(fn, iters, warm=2):
-    """seconds per call by the host clock, every call followed by a device synchronise"""
-    for _ in range(warm):
-        fn()
-        dev.sync()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-        dev.sync()
-    return (time.perf_counter() - t0) / iters
 
 
 def main():
@@ -68,7 +56,7 @@ def main():
         for n in COUNTS:
             pts = rng.random((n, 2)) * (np.array([h, w]) - 1.0)
             dp = dev.DevicePoints.from_host(pts)
-            t_dev = wall(lambda: d.track(dp), a.iters)
+            t_dev = wall(lambda: d.track(dp), a.iters, warm=2)
             t_host = wall(lambda: flow.track(pts), a.host_iters, warm=1)
             out, outside = dev.DeviceBuffer(n * 16), dev.DeviceBuffer.zeros(16)
             k_s, _, _ = timed(lambda: dev.track_bilinear_launch(d.vecs.ptr, 1, d.shape, False, dp, d._stats_word(), None, False, out, None,
@@ -78,7 +66,7 @@ def main():
                   "speedup": round(t_host / t_dev, 1), "kernel_ms": round(k_s * 1e3, 4), "kernel_Mpoints_per_s": round(n / k_s / 1e6, 1),
                   "kernel": "track_bilinear_kernel<false>", "bit_identical": bool(np.array_equal(d.track(dp).to_host(), flow.track(pts))),
                   "note": "wall clock per call including a device synchronise; the device route reads back the 4-byte outside counter"})
-            t_dev = wall(lambda: d.track(dp, get_valid_status=True), a.iters)
+            t_dev = wall(lambda: d.track(dp, get_valid_status=True), a.iters, warm=2)
             t_host = wall(lambda: flow.track(pts, get_valid_status=True), a.host_iters, warm=1)
             (gp, gs), (wp, ws) = d.track(dp, get_valid_status=True), flow.track(pts, get_valid_status=True)
             same = np.array_equal(gp.to_host(), wp) and np.array_equal(gs.to_host((n,), np.uint8), ws.view(np.uint8))
@@ -114,8 +102,8 @@ def main():
                 p = f.track(p)
             return p
 
-        t_seq = wall(lambda: batch.track_sequence(dp), a.iters)
-        t_chain = wall(chained, a.iters)
+        t_seq = wall(lambda: batch.track_sequence(dp), a.iters, warm=2)
+        t_chain = wall(chained, a.iters, warm=2)
         t_host = wall(host_loop, a.host_iters, warm=1)
         got, lost = batch.track_sequence(dp)
         want = host_loop()

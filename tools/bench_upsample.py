@@ -19,18 +19,17 @@ byte for byte.
 
     python tools/bench_upsample.py [--repeats 16] [--out profiles/r16_upsample_bench.jsonl]
 """
-import argparse
-import ctypes
-import json
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
 import numpy as np
 import oflibnumpy_amd as of
 from oflibnumpy_amd import device as dev
+import bench_kit as kit
 import upsample_ref as U
 
 nat = of.native
@@ -41,33 +40,7 @@ LAYOUTS = (("chw", nat.TENSOR_NCHW), ("hwc", nat.TENSOR_NHWC))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=16)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    nat.ensure_device()
-    lib = nat.load()
-    e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
-    nat.check(lib.ofl_event_create(ctypes.byref(e0)))
-    nat.check(lib.ofl_event_create(ctypes.byref(e1)))
-
-    def one_launch(fn):
-        nat.check(lib.ofl_event_record(e0, None))
-        nat.check(fn())
-        nat.check(lib.ofl_event_record(e1, None))
-        nat.check(lib.ofl_event_sync(e1))
-        ms = ctypes.c_float()
-        nat.check(lib.ofl_event_elapsed_ms(e0, e1, ctypes.byref(ms)))
-        return ms.value
-
-    def replicate(buf, arr, n):
-        arr = np.ascontiguousarray(arr)
-        nat.check(lib.ofl_upload(buf.ptr, arr.ctypes.data, arr.nbytes, None))
-        nat.check(lib.ofl_stream_sync(None))
-        for i in range(1, n):
-            nat.check(lib.ofl_copy_dev(buf.ptr + i * arr.nbytes, buf.ptr, arr.nbytes, None))
-
-    lines = []
+    a, lib, timer, report = kit.start(16)
     for name, h, w, f, n in (("1080p_f8_x8", 136, 240, 8, 8), ("4k_f8_x8", 270, 480, 8, 8), ("4k_f4_x8", 540, 960, 4, 8)):
         c1, ch = h * w, 9 * f * f
         fine1 = c1 * f * f
@@ -80,60 +53,51 @@ def main():
             vecs = rng.standard_normal((h, w, 2), np.float32) * np.float32(3)
             mask = (rng.random((h, w)) < 0.95).astype(np.uint8)
             x = (rng.standard_normal((ch, h, w), np.float32) * np.float32(4)).astype(np.float16)      # float16 values in both types
-            replicate(q["vecs"], vecs, n)
-            replicate(q["mask"], mask, n)
+            kit.replicate(q["vecs"], vecs, n)
+            kit.replicate(q["mask"], mask, n)
             for en, dt, _ in ELEMS:
                 for ln, _ in LAYOUTS:
                     q[en, ln] = dev.DeviceBuffer(n * ch * c1 * np.dtype(dt).itemsize)
-                    replicate(q[en, ln], U.to_layout(x.astype(dt), ln), n)
+                    kit.replicate(q[en, ln], U.to_layout(x.astype(dt), ln), n)
             nat.check(lib.ofl_memset(q["c0"].ptr, 1, q["c0"].nbytes, None))
             first.setdefault("in", (vecs, mask, x))
             sets.append(q)
             del x
 
         def upsample(q, en, ec, ln, lc):
-            return lambda: lib.ofl_upsample_convex_dev(q["vecs"].ptr, q["mask"].ptr, q[en, ln].ptr, ec, lc, h, w, n, f,
-                                                       q["out_vecs"].ptr, q["out_mask"].ptr, None)
+            return lambda: nat.check(lib.ofl_upsample_convex_dev(q["vecs"].ptr, q["mask"].ptr, q[en, ln].ptr, ec, lc, h, w, n, f,
+                                                                 q["out_vecs"].ptr, q["out_mask"].ptr, None))
 
         variants = [("upsample_%s_%s" % (en, ln), en, (lambda en, ec, ln, lc: lambda q: upsample(q, en, ec, ln, lc))(en, ec, ln, lc))
                     for en, _, ec in ELEMS for ln, lc in LAYOUTS]
-        variants += [("copy_%s" % en, en, (lambda en: lambda q: (lambda: lib.ofl_copy_dev(q["c1"].ptr, q["c0"].ptr, total[en] // 2, None)))(en))
-                     for en, _, _ in ELEMS]
-        ms = {key: [] for key, _, _ in variants}
-        for r in range(-2, a.repeats):                      # two warm-up rounds over every variant
-            for key, _, make in variants:
-                t = one_launch(make(sets[r % SETS]))
-                if r >= 0:
-                    ms[key].append(t)
+        variants += [("copy_%s" % en, en, kit.copy_variant(total[en] // 2)) for en, _, _ in ELEMS]
+        ms = kit.interleaved(timer, [(key, make) for key, _, make in variants], sets, a.repeats)
         # the timed buffers give the restatement's bytes, also at this size (a corner of the first item of the first set)
         same = {}
         vecs, mask, x = first["in"]
         yy, xx = min(CROP[0], h - 1), min(CROP[1], w - 1)
         want_v, want_m = U.upsample(vecs[:yy + 1, :xx + 1], mask[:yy + 1, :xx + 1], np.ascontiguousarray(x[:, :yy + 1, :xx + 1]), f)
         for key, en, make in variants[:4]:
-            nat.check(make(sets[0])())
+            make(sets[0])()
             got_v = sets[0]["out_vecs"].view(0, fine1 * 8).to_host((f * h, f * w, 2), np.float32)[:f * yy, :f * xx]
             got_m = sets[0]["out_mask"].view(0, fine1).to_host((f * h, f * w), np.uint8)[:f * yy, :f * xx]
             same[key] = bool(np.ascontiguousarray(got_v).tobytes() == np.ascontiguousarray(want_v[:f * yy, :f * xx]).tobytes()
                              and np.array_equal(got_m, want_m[:f * yy, :f * xx]))
-        med = {key: float(np.median(v)) for key, v in ms.items()}
+        med = kit.median_ms(ms)
         for key, en, _ in variants:
             ref = "copy_%s" % en
-            spread = (max(ms[ref]) - min(ms[ref])) / med[ref]
+            spread = kit.spread(ms[ref])
             line = {"key": "%s_%s" % (key, name), "coarse": [h, w], "factor": f, "fine": [f * h, f * w], "items": n,
-                    "device_ms_median": round(med[key], 4), "device_ms_min": round(min(ms[key]), 4), "device_ms_max": round(max(ms[key]), 4),
+                    **kit.ms_fields(ms[key]),
                     "repeats": a.repeats, "rotating_sets": SETS, "over_copy": round(med[key] / med[ref], 3),
                     "copy_spread": round(spread, 3), "bytes": int(total[en]), "TBps": round(total[en] / med[key] / 1e9, 3),
                     "device": nat.device_name()}
             if key in same:
                 line.update({"within_copy_spread": bool(med[key] <= med[ref] * (1 + spread)), "equal_restatement": same[key]})
-            lines.append(json.dumps(line))
-            print(lines[-1], flush=True)
+            report.line(line)
         del sets, q
         dev.empty_cache()
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    report.write(a.out)
 
 
 if __name__ == "__main__":
