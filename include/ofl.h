@@ -940,6 +940,60 @@ int ofl_corr_lookup_dev(const void *f1, int elem1, const void *f2_l, int elem2, 
 int ofl_corr_lookup(const void *f1, int elem1, const void *f2, int elem2, int N, int C, int H, int W, int levels,
                     const float *flow, int flow_shared, int sign, int r, float scale, int order, int quant, float *out);
 
+/* ------------------------------------------------------------------ K19: global matching of two feature tensors
+ * The first flow of a GMFlow / UniMatch- or FlowFormer-style matcher, and of a classical forward / backward pair that K13,
+ * K15 and K16 then clean up: every pixel of f1 is dotted with every pixel of f2, a softmax runs over all H W candidates and
+ * the flow is the expected coordinate minus the pixel's own.  The (H W)^2 volume of the textbook formulation
+ * (f1 @ f2^T, softmax(dim=-1), @ grid) is never stored.  Per item:
+ *     f1, f2   C channels on an H x W grid, channels last [H][W][C], both of ONE element type: OFL_EL_F16, OFL_EL_BF16 or
+ *              OFL_EL_F32.  The keys are the pixels of f2, numbered k = ky W + kx.
+ * For the query pixel q = (x, y) of f1:
+ *     D_k  = sum_c f1[q, c] * f2[k, c]     on the matrix core, float32 accumulation from 0, channels ascending through the K
+ *            steps (C is padded to the step with zeros).  16-bit: mfma_f32_32x32x16_{f16,bf16}, 16 channels a step; the order
+ *            inside one instruction is the hardware's and is not stated.  float32: mfma_f32_32x32x2f32, 2 channels a step.
+ *     s_k  = D_k * scale                   float32, rounded once
+ *     m    = max_k s_k                     exact, no order
+ *     idx  = the smallest k with s_k == m  (ties: the first in row-major order); always in [0, H W)
+ *     t_k  = s_k - m
+ *     e_k  = t_k < -87 ? 0 : exp32(t_k)    K17's exp32 above, the stated float32 sequence; exp32(0) = 1
+ *     l = sum_k e_k,  ax = sum_k e_k * (float)kx,  ay = sum_k e_k * (float)ky      products rounded once, no FMA; the ORDER:
+ *            the keys go in tiles of T = OFL_MATCH_TILE = 32 consecutive keys; tile j belongs to group w = j mod G,
+ *            G = OFL_MATCH_WAVES = 4; inside a tile, key offset o belongs to half h = (o >> 2) & 1 (o = 0 .. 3, 8 .. 11,
+ *            16 .. 19, 24 .. 27: h = 0; the others: h = 1).  Each of the 2 G partial sums P[w][h] starts at +0 and adds its
+ *            keys in ascending k.  Then S_w = P[w][0] + P[w][1] and the sum is ((S_0 + S_1) + S_2) + S_3.  A partial sum without
+ *            a key is +0, and since no term is negative no sum is ever -0.0, so adding it -- like adding any e_k = 0 --
+ *            changes no bit.  T and G do not depend on N, C, the element type, alignment, the position in a batch or the
+ *            number of CUs: the 32 x 32 accumulator tile holds a query on a lane and 16 keys in each lane half's registers,
+ *            and four waves share the keys of a query.
+ *     mx = ax / l,  my = ay / l            IEEE division
+ *     u  = mx - (float)x,  v = my - (float)y
+ *     out_vecs = sign * (u, v)             sign +1: 's' (q + flow is the match); -1: 't'
+ *     out_conf = 1.0f / l                  the softmax probability of the best candidate
+ *     out_mask = conf >= min_conf          min_conf = 0 sets every pixel
+ *     out_index = idx                      int32
+ * Two sweeps over the keys: the first forms every D_k and keeps m and idx, the second forms every D_k again by the same
+ * instruction sequence -- so t_k <= 0 everywhere and = 0 at idx -- and accumulates l, ax, ay; a tile whose every t_k < -87
+ * is skipped after its dots, which changes no bit (above).  Keys beyond H W in the last tile take part in nothing; queries
+ * beyond H W write nothing.  No address depends on a feature value: NaN / Inf features give unspecified values, an index in
+ * range and no fault.  `N` items lie back to back; offsets are 64-bit.  One launch; no atomics, no workspace.
+ *     out_vecs float32 [H][W][2], out_mask uint8 [H][W], out_conf float32 [H][W] or NULL, out_index int32 [H][W] or NULL
+ * f1 / f2 aligned to their element: 16-byte-aligned bases with C % 8 == 0 (16-bit) or C % 4 == 0 (float32) are read 16 bytes
+ * a load, anything else element by element.  out_vecs 8-byte, out_conf and out_index 4-byte aligned.  A bad argument -- a
+ * NULL f1, f2, out_vecs or out_mask, an element other than the three (OFL_EL_F64 included), a sign other than +-1, a negative
+ * or NaN min_conf, N outside [1, 65535], C outside [1, 512], H or W outside [1, 32766], an output that overlaps an input or
+ * another output, a misaligned pointer -- returns OFL_E_INVALID with a message before any launch.  The _dev entry is
+ * asynchronous; the host entry takes host pointers, uploads, launches, downloads and synchronises.
+ * Not built: a mask over the keys (padded frames), a local-window softmax (K18's output plus a softmax), returning the
+ * probabilities themselves, a key split across workgroups with a merge pass for very small frames, a backward pass, fp8,
+ * mixed element types.
+ */
+#define OFL_MATCH_TILE 32
+#define OFL_MATCH_WAVES 4
+int ofl_global_match_dev(const void *f1, const void *f2, int elem, int N, int C, int H, int W, float scale, int sign,
+                         float min_conf, float *out_vecs, uint8_t *out_mask, float *out_conf, int32_t *out_index, void *stream);
+int ofl_global_match(const void *f1, const void *f2, int elem, int N, int C, int H, int W, float scale, int sign,
+                     float min_conf, float *out_vecs, uint8_t *out_mask, float *out_conf, int32_t *out_index);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

@@ -26,6 +26,7 @@ EL_F16, EL_BF16, EL_F32, EL_F64 = 0, 1, 2, 3
 TENSOR_NCHW, TENSOR_NHWC = 0, 1
 CORR_XY, CORR_YX = 0, 1
 CORR_V, CORR_L = 4, 16
+MATCH_TILE, MATCH_WAVES = 32, 4
 
 
 class MeshCert(ctypes.Structure):
@@ -156,6 +157,8 @@ SIGNATURES = {
     "ofl_corr_lookup_dev": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _ci, _cf, _ci, _ci,
                                   _vp, _ci, _ci, _vp]),
     "ofl_corr_lookup": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _ci, _cf, _ci, _ci, _vp]),
+    "ofl_global_match_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cf, _ci, _cf, _vp, _vp, _vp, _vp, _vp]),
+    "ofl_global_match": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cf, _ci, _cf, _vp, _vp, _vp, _vp]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

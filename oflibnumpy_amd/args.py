@@ -456,6 +456,51 @@ def corr_host_array(a, name):
     return np.ascontiguousarray(np.moveaxis(a, 0, -1))[None], tuple(a.shape)
 
 
+# -- global matching (K19)
+MATCH_MAX_CHANNELS = 512
+
+
+def _float32_arg(value, name, prefix):
+    """a finite number -> float32 (TypeError for a bool or a non-number, ValueError where float32 cannot hold it)"""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise TypeError("{}{} must be a number or None, got {}".format(prefix, name, type(value).__name__))
+    with np.errstate(over='ignore'):
+        value = np.float32(float(value)) if abs(value) < 1e300 else np.float32(np.inf)
+    if not np.isfinite(value):
+        raise ValueError("{}{} must be finite as float32".format(prefix, name))
+    return value
+
+
+def match_args(scale, min_confidence, channels, dtype1, dtype2):
+    """Validation of a global matching (K19) on the host before any device work -> (scale, min_confidence) as float32.
+    scale: None for float32(1 / sqrt(float64(channels))), or a finite number; min_confidence: None for 0 (every pixel of the
+    mask is set), or a number in [0, 1]; channels: at most 512; dtype1, dtype2: the element types of the two feature maps,
+    which must be the same.  A bool or a non-number is a TypeError, a value outside its set a ValueError."""
+    prefix = "Error matching features: "
+    if dtype1 != dtype2:
+        raise ValueError("{}the feature maps need the same dtype, got {} and {}".format(prefix, dtype1, dtype2))
+    if not 1 <= channels <= MATCH_MAX_CHANNELS:
+        raise ValueError("{}the feature maps must have 1 ... {} channels, got {}".format(prefix, MATCH_MAX_CHANNELS, channels))
+    scale = np.float32(1.0 / np.sqrt(np.float64(channels))) if scale is None else _float32_arg(scale, "scale", prefix)
+    min_confidence = np.float32(0.0) if min_confidence is None else _float32_arg(min_confidence, "min_confidence", prefix)
+    if not 0.0 <= min_confidence <= 1.0:
+        raise ValueError("{}min_confidence must be in [0, 1], got {}".format(prefix, min_confidence))
+    return scale, min_confidence
+
+
+def match_host_array(a, name):
+    """A feature map given to global_match -> (contiguous channels-last array (1, H, W, C), logical shape): a NumPy array
+    (C, H, W) of float32 or float16 (TypeError for another type or dtype, ValueError for another rank)."""
+    if not isinstance(a, np.ndarray):
+        raise TypeError("Error matching features: {} needs to be a numpy array, got {}".format(name, type(a).__name__))
+    if a.dtype != np.float32 and a.dtype != np.float16:
+        raise TypeError("Error matching features: {} needs to have dtype float32 or float16, got {}".format(name, a.dtype))
+    if a.ndim != 3:
+        raise ValueError("Error matching features: {} needs to have shape (C, H, W), got {}".format(name, a.shape))
+    tensor_args(a.shape, 'chw', a.dtype.name)
+    return np.ascontiguousarray(np.moveaxis(a, 0, -1))[None], tuple(a.shape)
+
+
 # -- many-channel float tensors (K12)
 def tensor_dtype(array_dtype, dtype=None):
     """The element type of a tensor -> 'float32', 'float16' or 'bfloat16'.  `array_dtype`: the dtype of the array that holds

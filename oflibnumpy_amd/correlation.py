@@ -9,12 +9,16 @@ without the all-pairs volume of (H W)^2 floats.
 `build` holds fmap1 and the pyramid of fmap2 channels-last -- a planar tensor is permuted once by K12's permute kernel (one
 read and one write of it), level l >= 1 is the float32 2 x 2 mean of level l - 1 -- and `lookup` issues one launch per level on
 the library's stream.  Nothing synchronises.
+
+The same two buffers answer "where is the best match anywhere?" (K19, csrc/ofl_match.hip): `corr.match()` dots every pixel of
+fmap1 with every pixel of fmap2 on the matrix cores, runs the softmax over all H W candidates and returns the expected
+displacement as a DeviceFlow -- the first flow of a GMFlow-style matcher -- again without the all-pairs volume.
 """
 from . import _native as nat
-from .args import corr_args
+from .args import corr_args, match_args, optional_bool
 from .batch import DeviceFlowBatch
 from .device import DeviceFlow, DeviceTensor
-from .kernels import avgpool2_launch, corr_lookup_launch, tensor_permute_launch
+from .kernels import avgpool2_launch, corr_lookup_launch, match_launch, tensor_permute_launch
 
 
 def _channels_last(tensor):
@@ -81,3 +85,26 @@ class DeviceCorrelation:
         channels = self.levels * (2 * radius + 1) ** 2
         shape = (self.n, channels, self.h, self.w) if self.batched else (channels, self.h, self.w)
         return DeviceTensor(out, shape, 'float32', 'chw')
+
+    def match(self, ref='s', scale=None, reverse=False, min_confidence=None, return_confidence=False, return_index=False):
+        """The global match of every pixel of fmap1 among ALL pixels of fmap2 (level 0): the softmax over the H W dot
+        products times `scale` (None: float32(1 / sqrt(C))), the expected coordinate minus the pixel's own as the flow --
+        with ref 's' pixel + flow is the match, 't' is its exact negation.  reverse=True matches the pixels of fmap2 into
+        fmap1 (the two buffers swapped): the backward field for DeviceFlow.consistency.  The mask is set where the
+        confidence, the softmax probability of the best candidate, is at least `min_confidence` (None: 0, every pixel).
+        Both feature maps need one dtype.  -> a DeviceFlow, or a DeviceFlowBatch for (N, C, H, W); with return_confidence /
+        return_index a tuple that also holds the float32 confidence [N][H][W] and the int32 row-major index of the best
+        candidate [N][H][W] as DeviceBuffers.  One launch; nothing synchronises."""
+        from .utils import get_valid_ref
+        ref = get_valid_ref(ref)
+        flags = [optional_bool(v, False, "Error matching features: {} needs to be a boolean".format(name))
+                 for name, v in (("reverse", reverse), ("return_confidence", return_confidence), ("return_index", return_index))]
+        f2, dtype2 = self.pyramid[0]
+        scale, min_conf = match_args(scale, min_confidence, self.channels, self.dtype1, dtype2)
+        a, b = (f2, self.f1) if flags[0] else (self.f1, f2)
+        vecs, mask, conf, index = match_launch(a, b, self.dtype1, self.n, self.channels, self.h, self.w, scale,
+                                               1 if ref == 's' else -1, min_conf, flags[1], flags[2])
+        shape = (self.h, self.w)
+        flow = DeviceFlowBatch.wrap(self.n, shape, ref, vecs, mask) if self.batched else DeviceFlow(vecs, mask, shape, ref)
+        extra = tuple(x for x, wanted in ((conf, flags[1]), (index, flags[2])) if wanted)
+        return (flow,) + extra if extra else flow

@@ -26,6 +26,7 @@
 #include <stddef.h>
 #include "ofl_common.h"
 #include "ofl_elem.h"
+#include "ofl_exp32.h"
 #include "ofl_host_stage.h"
 
 #pragma clang fp contract(off)
@@ -56,26 +57,6 @@ struct UArgs {
     uint8_t       *out_mask;
     int            h, w;
 };
-
-// exp(t) for t in [-87, 0]: Cody-Waite reduction t = n ln2 + r with a two-part ln2 (n * kLn2Hi is exact: 9 x 7 bits), the
-// degree-7 Taylor polynomial in Horner form with separate multiplies and adds, and n added to the exponent field
-// (p * 2^n >= exp(-87) > 2^-126, so the field stays positive).  exp32(0) = 1 exactly.
-__device__ __forceinline__ float exp32(float t)
-{
-    constexpr float kLog2e = 1.44269504f, kLn2Hi = 0.693359375f, kLn2Lo = -2.12194440e-4f;
-    const float n = __builtin_rintf(__fmul_rn(t, kLog2e));
-    float r = __fsub_rn(t, __fmul_rn(n, kLn2Hi));
-    r = __fsub_rn(r, __fmul_rn(n, kLn2Lo));
-    float p = 1.0f / 5040.0f;
-    p = __fadd_rn(__fmul_rn(p, r), 1.0f / 720.0f);
-    p = __fadd_rn(__fmul_rn(p, r), 1.0f / 120.0f);
-    p = __fadd_rn(__fmul_rn(p, r), 1.0f / 24.0f);
-    p = __fadd_rn(__fmul_rn(p, r), 1.0f / 6.0f);
-    p = __fadd_rn(__fmul_rn(p, r), 0.5f);
-    p = __fadd_rn(__fmul_rn(p, r), 1.0f);
-    p = __fadd_rn(__fmul_rn(p, r), 1.0f);
-    return __uint_as_float(__float_as_uint(p) + ((uint32_t)__float2int_rz(n) << 23));
-}
 
 // one fine pixel: the logits of tap k at p[k * step], the taps' scaled vectors in u, v.  The nine loads are unconditional, so
 // that they are issued together and waited for once (a lane outside the frame is given the address of column 0).

@@ -32,14 +32,14 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rul
                    percentile_ranks, matrix_args, validate_transforms, valid_mask_array, scale_operand, crop_args,
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
                    consistency_args, error_args, fill_args, median_args, upsample_args, upsample_weights_array, corr_args,
-                   corr_host_array, optional_bool, mask_array_arg)
+                   corr_host_array, optional_bool, mask_array_arg, match_args, match_host_array)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
                       track_bilinear_launch, track_query_points, track_query_epilogue, gather_tensor, tensor_import_launch,
                       tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
                       FlowErrorStats, fill_launch, fill_host, median_launch, median_host, upsample_launch,
-                      upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host)
+                      upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host, match_launch, match_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -275,6 +275,12 @@ class DeviceTensor:
         -> a planar float32 DeviceTensor of levels (2 radius + 1)^2 channels."""
         from .correlation import DeviceCorrelation
         return DeviceCorrelation.build(self, other, levels).lookup(flow, radius, scale, order, quant)
+
+    def match(self, other, ref='s', scale=None, reverse=False, min_confidence=None, return_confidence=False, return_index=False):
+        """The global match of this tensor's features in those of `other`, in one call:
+        DeviceCorrelation.build(self, other, levels=1).match(...) (correlation.py, K19)."""
+        from .correlation import DeviceCorrelation
+        return DeviceCorrelation.build(self, other, 1).match(ref, scale, reverse, min_confidence, return_confidence, return_index)
 
 
 # ------------------------------------------------------------------------------ the launch wrappers that hand back a DeviceImage

@@ -11,7 +11,7 @@ from .flow_class import Flow
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
            'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow',
-           'upsample_flow_convex', 'correlation_lookup']
+           'upsample_flow_convex', 'correlation_lookup', 'global_match']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -123,3 +123,28 @@ def correlation_lookup(fmap1: nd, fmap2: nd, flow: nd = None, ref: str = 's', ra
             raise ValueError("Error looking up correlation: flow needs to have shape {}, got {}".format(shape1[1:] + (2,), flow.shape))
         flow = np.ascontiguousarray(flow, np.float32)
     return dev.corr_lookup_host(f1, f2, flow, sign, radius, levels, scale, order, quant)[0]
+
+
+def global_match(fmap1: nd, fmap2: nd, ref: str = 's', scale: float = None, min_confidence: float = None,
+                 return_confidence: bool = False, return_index: bool = False):
+    """The global match of the feature maps `fmap1` and `fmap2`, arrays (C, H, W) of ONE dtype, float32 or float16: every
+    pixel of fmap1 is dotted with every pixel of fmap2, a softmax runs over all H W candidates and the flow is the expected
+    coordinate minus the pixel's own -- GMFlow's global matching without the all-pairs volume; DeviceCorrelation.match.
+    ref 's': pixel + flow is the match; 't': its negation.  scale: None for 1 / sqrt(C).  The mask of the returned Flow is set
+    where the confidence (the softmax probability of the best candidate) is at least `min_confidence` (None: everywhere).
+    -> a Flow; with return_confidence / return_index a tuple that also holds the float32 (H, W) confidence and the int32
+    (H, W) row-major index of the best candidate.  One upload, one launch, one download."""
+    from . import device as dev
+    from .utils import get_valid_ref
+    ref = get_valid_ref(ref)
+    want = [dev.optional_bool(v, False, "Error matching features: {} needs to be a boolean".format(name))
+            for name, v in (("return_confidence", return_confidence), ("return_index", return_index))]
+    f1, shape1 = dev.match_host_array(fmap1, "fmap1")
+    f2, shape2 = dev.match_host_array(fmap2, "fmap2")
+    if shape1 != shape2:
+        raise ValueError("Error matching features: the feature maps need the same shape, got {} and {}".format(shape1, shape2))
+    scale, min_conf = dev.match_args(scale, min_confidence, shape1[0], f1.dtype.name, f2.dtype.name)
+    vecs, mask, conf, index = dev.match_host(f1, f2, scale, 1 if ref == 's' else -1, min_conf, want[0], want[1])
+    flow = Flow(vecs[0], ref, mask[0])
+    extra = tuple(x[0] for x, wanted in ((conf, want[0]), (index, want[1])) if wanted)
+    return (flow,) + extra if extra else flow

@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling and K18 correlation lookup.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup and K19 global matching.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -515,3 +515,30 @@ def corr_lookup_host(f1, f2, flow, sign, radius, levels, scale, order, quant):
     nat.check(_lib().ofl_corr_lookup(f1.ctypes.data, _TENSOR_EL[f1.dtype.name], f2.ctypes.data, _TENSOR_EL[f2.dtype.name], n, c, h, w,
                                      levels, _host_ptr(flow), 1, sign, radius, scale, order, quant, out.ctypes.data))
     return out
+
+
+# ------------------------------------------------------------------------------ K19: global matching
+def match_launch(f1, f2, dtype, n, c, h, w, scale, sign, min_conf, want_conf=False, want_index=False, stream=None):
+    """K19 (ofl_global_match_dev) on `n` pairs of channels-last tensors [n][h][w][c] of `dtype` stored back to back;
+    asynchronous, one launch.  scale, min_conf: from args.match_args.  -> (vecs, mask, confidence or None, index or None):
+    float32 [n][h][w][2], uint8, float32 and int32 [n][h][w], still in HBM."""
+    px = n * h * w
+    vecs, mask = DeviceBuffer(px * 8), DeviceBuffer(px)
+    conf = DeviceBuffer(px * 4) if want_conf else None
+    index = DeviceBuffer(px * 4) if want_index else None
+    nat.check(_lib().ofl_global_match_dev(f1.ptr, f2.ptr, _TENSOR_EL[dtype], n, c, h, w, scale, sign, min_conf, vecs.ptr, mask.ptr,
+                                          _ptr(conf), _ptr(index), stream))
+    return vecs, mask, conf, index
+
+
+def match_host(f1, f2, scale, sign, min_conf, want_conf=False, want_index=False):
+    """K19 for host arrays through ofl_global_match (upload, launch, download): f1, f2 contiguous channels-last (n, h, w, c)
+    of one dtype, float32 or float16 -> (vecs float32 (n, h, w, 2), mask bool (n, h, w), confidence float32 (n, h, w) or
+    None, index int32 (n, h, w) or None)."""
+    n, h, w, c = f1.shape
+    vecs, mask = np.empty((n, h, w, 2), np.float32), np.empty((n, h, w), np.uint8)
+    conf = np.empty((n, h, w), np.float32) if want_conf else None
+    index = np.empty((n, h, w), np.int32) if want_index else None
+    nat.check(_lib().ofl_global_match(f1.ctypes.data, f2.ctypes.data, _TENSOR_EL[f1.dtype.name], n, c, h, w, scale, sign, min_conf,
+                                      vecs.ctypes.data, mask.ctypes.data, _host_ptr(conf), _host_ptr(index)))
+    return vecs, mask.view(np.bool_), conf, index
