@@ -490,7 +490,9 @@ int ofl_resize_flow_dev(const float *vecs, const uint8_t *mask, int H, int W, in
  *                            initialisation needed.  flow 8-byte aligned.  Nothing is synchronised.
  *   ofl_visualise_dev        the image.  range_dev: float32[batch] on the device (from ofl_visualise_range_dev), or
  *                            NULL -- then range_const (> 0, +inf allowed) serves every field.  mask may be NULL (all
- *                            valid).  flow 16-byte, mask and out 4-byte aligned.
+ *                            valid).  flow 8-byte, out 4-byte aligned, mask at any address: vectors on the 16-byte and a
+ *                            mask on the 4-byte grid are read four pixels a load pair, anything else pixel by pixel --
+ *                            the same pixels per thread, the same bytes out.
  * A field holding NaN / Inf gives an unspecified image but never reads or writes out of bounds.
  */
 enum { OFL_VIS_HSV = 0, OFL_VIS_RGB = 1, OFL_VIS_BGR = 2 };
@@ -523,7 +525,9 @@ int ofl_visualise_dev(const float *flow, const uint8_t *mask, int H, int W, int 
  * GATE: the sum entries take gate_model (host, 9 doubles, or NULL = no gate) and gate_thr; only correspondences with
  * residual(gate_model) <= gate_thr contribute -- "refit on the inliers" is the same kernel as "fit on everything".
  * Models, origins and normalisations are HOST pointers (they travel as kernel arguments); flow, mask, workspace and
- * every output are DEVICE pointers.  flow 16-byte, mask 4-byte aligned; H * W < 2^31.  Nothing is synchronised.
+ * every output are DEVICE pointers.  flow 8-byte aligned, mask at any address; H * W < 2^31.  Nothing is synchronised.
+ * Vectors on the 16-byte and a mask on the 4-byte grid are read 16 and 4 bytes a load, anything else 8 bytes and 1 byte a
+ * load: the pixels of a thread and the order of every addition are the same, so the results do not depend on alignment.
  *
  * SUMS (device float64): one workgroup per 4096 px writes its partial sums to the workspace -- per thread its <= 19 terms in
  * pixel order, per wave a six-level butterfly, then ((w0 + w1) + w2) + w3 -- and one thread per sum adds the
@@ -580,8 +584,9 @@ int ofl_fit_gather_dev(const float *flow, const uint8_t *mask, int H, int W, con
  * The constructors and element-wise / shape operations of Flow that had no device form: Flow.from_matrix /
  * from_transforms (flow_class.py:173-234 over utils.flow_from_matrix, utils.py:91-111, and from_matrix :319-344),
  * Flow.__mul__ / __truediv__ (flow_class.py:377-443), Flow.pad (:508-526) and Flow.__getitem__ (:297-308).  Streaming
- * kernels; every entry only enqueues work.  Vector buffers that are written (and ofl_scale_dev's source) are 16-byte
- * aligned, written masks 2-byte aligned; outputs must not alias inputs.
+ * kernels; every entry only enqueues work.  Vector buffers that are written are 16-byte aligned, written masks 2-byte
+ * aligned -- except ofl_scale_dev, whose source and result need 8 bytes only (below 16 it moves 8 bytes a load); outputs
+ * must not alias inputs.
  *
  *   ofl_flow_from_matrix_dev  n fields out_vecs [n][H][W][2] from n row-major 3x3 float64 matrices in DEVICE memory
  *                             (mats_dev [n][9]), one launch; n in [1, 65535].  Per pixel (x, y), every operation a float64

@@ -17,6 +17,7 @@ int stream_grid(size_t n_items)
 }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 // ---------------------------------------------------------------------------------------------- fields from matrices
 // utils.flow_from_matrix (reference utils.py:91-111) per pixel: np.matmul of the float64 matrix with the float32 column
@@ -75,21 +76,45 @@ __device__ __forceinline__ float scale1(float v, double k)
     return DIVIDE ? __fdiv_rn(v, (float)k) : __fmul_rn(v, (float)k);
 }
 
-template <int WIDE, int DIVIDE>
+// PAIR 1: one float4 per lane, vectors and result on the 16-byte grid.  PAIR 0: a field 8 bytes off it (every second field
+// of a batch of odd fields, a view) -- the same pixel pair per lane as two float2, so the bytes do not depend on the route.
+template <int WIDE, int DIVIDE, int PAIR>
 __global__ __launch_bounds__(256)
 void scale_kernel(const float *__restrict__ vecs, double k0, double k1, size_t n_px, float *__restrict__ out)
 {
     const size_t n2 = n_px / 2, stride = (size_t)gridDim.x * blockDim.x;
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n2; p += stride) {
-        const float4 v = reinterpret_cast<const float4 *>(vecs)[p];
-        reinterpret_cast<float4 *>(out)[p] = make_float4(scale1<WIDE, DIVIDE>(v.x, k0), scale1<WIDE, DIVIDE>(v.y, k1),
-                                                         scale1<WIDE, DIVIDE>(v.z, k0), scale1<WIDE, DIVIDE>(v.w, k1));
+        float4 v;
+        if (PAIR) {
+            v = reinterpret_cast<const float4 *>(vecs)[p];
+        } else {
+            const float2 a = reinterpret_cast<const float2 *>(vecs)[2 * p], b = reinterpret_cast<const float2 *>(vecs)[2 * p + 1];
+            v = make_float4(a.x, a.y, b.x, b.y);
+        }
+        const float4 r = make_float4(scale1<WIDE, DIVIDE>(v.x, k0), scale1<WIDE, DIVIDE>(v.y, k1),
+                                     scale1<WIDE, DIVIDE>(v.z, k0), scale1<WIDE, DIVIDE>(v.w, k1));
+        if (PAIR) {
+            reinterpret_cast<float4 *>(out)[p] = r;
+        } else {
+            reinterpret_cast<float2 *>(out)[2 * p] = make_float2(r.x, r.y);
+            reinterpret_cast<float2 *>(out)[2 * p + 1] = make_float2(r.z, r.w);
+        }
     }
     if ((n_px & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const size_t i = n_px - 1;
         out[2 * i] = scale1<WIDE, DIVIDE>(vecs[2 * i], k0);
         out[2 * i + 1] = scale1<WIDE, DIVIDE>(vecs[2 * i + 1], k1);
     }
+}
+
+template <int PAIR>
+void launch_scale(const float *vecs, double k0, double k1, int divide, int wide, size_t n_px, float *out, hipStream_t s)
+{
+    const dim3 grid(stream_grid(n_px / 2)), block(256);
+    if (wide && divide)  hipLaunchKernelGGL((scale_kernel<1, 1, PAIR>), grid, block, 0, s, vecs, k0, k1, n_px, out);
+    else if (wide)       hipLaunchKernelGGL((scale_kernel<1, 0, PAIR>), grid, block, 0, s, vecs, k0, k1, n_px, out);
+    else if (divide)     hipLaunchKernelGGL((scale_kernel<0, 1, PAIR>), grid, block, 0, s, vecs, k0, k1, n_px, out);
+    else                 hipLaunchKernelGGL((scale_kernel<0, 0, PAIR>), grid, block, 0, s, vecs, k0, k1, n_px, out);
 }
 
 // ---------------------------------------------------------------------------------------------- padding and cropping
@@ -182,14 +207,10 @@ int ofl_scale_dev(const float *vecs, double k0, double k1, int divide, int wide,
 {
     OFL_TRY(need_device());
     if (!vecs || !out) return fail(OFL_E_INVALID, "ofl_scale: NULL pointer");
-    if (!aligned16(vecs) || !aligned16(out)) return fail(OFL_E_INVALID, "ofl_scale: vecs and out must be 16-byte aligned");
+    if (!aligned8(vecs) || !aligned8(out)) return fail(OFL_E_INVALID, "ofl_scale: vecs and out must be 8-byte aligned");
     if (n_px == 0) return OFL_OK;
-    const dim3 grid(stream_grid(n_px / 2)), block(256);
-    hipStream_t s = stream_of(stream);
-    if (wide && divide)  hipLaunchKernelGGL((scale_kernel<1, 1>), grid, block, 0, s, vecs, k0, k1, n_px, out);
-    else if (wide)       hipLaunchKernelGGL((scale_kernel<1, 0>), grid, block, 0, s, vecs, k0, k1, n_px, out);
-    else if (divide)     hipLaunchKernelGGL((scale_kernel<0, 1>), grid, block, 0, s, vecs, k0, k1, n_px, out);
-    else                 hipLaunchKernelGGL((scale_kernel<0, 0>), grid, block, 0, s, vecs, k0, k1, n_px, out);
+    if (aligned16(vecs) && aligned16(out)) launch_scale<1>(vecs, k0, k1, divide, wide, n_px, out, stream_of(stream));
+    else                                   launch_scale<0>(vecs, k0, k1, divide, wide, n_px, out, stream_of(stream));
     OFL_HIP(hipGetLastError());
     return OFL_OK;
 }

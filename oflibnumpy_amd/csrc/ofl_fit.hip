@@ -37,19 +37,37 @@ struct FitTile {
     int x[kFitUnroll], y[kFitUnroll];          // position of pixel 0
 };
 
-// every load of the tile is issued before the first value is looked at
+// every load of the tile is issued before the first value is looked at.  WIDE 1: vectors on the 16-byte, mask on the 4-byte
+// grid.  WIDE 0 (a view inside a batch of odd fields): the same groups per lane from 8-byte and 1-byte loads, so that every
+// sum adds the same terms in the same order.
+template <int WIDE>
 __device__ __forceinline__ void fit_load(const FitField &A, uint32_t chunk, FitTile &T)
 {
     const uint32_t groups = A.n / 4;
     const float4 *f4 = reinterpret_cast<const float4 *>(A.flow);
+    const float2 *f2 = reinterpret_cast<const float2 *>(A.flow);
     const uint32_t *mw = reinterpret_cast<const uint32_t *>(A.mask);
 #pragma unroll
     for (int k = 0; k < kFitUnroll; ++k) {
         const uint32_t g = chunk * kFitGroups + (uint32_t)k * 256 + threadIdx.x;
         const bool in = g < groups;
-        T.a[k] = in ? f4[2 * (size_t)g] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        T.b[k] = in ? f4[2 * (size_t)g + 1] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        T.m[k] = in ? (mw ? mw[g] : 0x01010101u) : 0u;
+        if (WIDE) {
+            T.a[k] = in ? f4[2 * (size_t)g] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            T.b[k] = in ? f4[2 * (size_t)g + 1] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            T.m[k] = in ? (mw ? mw[g] : 0x01010101u) : 0u;
+        } else {
+            const float2 z = make_float2(0.0f, 0.0f);
+            const float2 p0 = in ? f2[4 * (size_t)g] : z, p1 = in ? f2[4 * (size_t)g + 1] : z;
+            const float2 p2 = in ? f2[4 * (size_t)g + 2] : z, p3 = in ? f2[4 * (size_t)g + 3] : z;
+            T.a[k] = make_float4(p0.x, p0.y, p1.x, p1.y);
+            T.b[k] = make_float4(p2.x, p2.y, p3.x, p3.y);
+            uint32_t m = in ? 0x01010101u : 0u;
+            if (in && A.mask) {
+                const uint8_t *mb = A.mask + 4 * (size_t)g;
+                m = (uint32_t)mb[0] | ((uint32_t)mb[1] << 8) | ((uint32_t)mb[2] << 16) | ((uint32_t)mb[3] << 24);
+            }
+            T.m[k] = m;
+        }
         const uint32_t p = 4 * g;
         T.y[k] = (int)(p / (uint32_t)A.W);
         T.x[k] = (int)(p - (uint32_t)T.y[k] * (uint32_t)A.W);
@@ -186,7 +204,7 @@ __device__ __forceinline__ void fit_terms(const FitSumArgs &P, const Corr &c, do
 
 // One chunk per workgroup.  Per thread: its <= 16 (+ 3 tail) terms in pixel order; per wave: a six-level xor butterfly
 // (a + b == b + a, so every lane holds the same bits); per workgroup: ((w0 + w1) + w2) + w3 -> partial[chunk][s].
-template <int KIND>
+template <int KIND, int WIDE>
 __global__ __launch_bounds__(256)
 void fit_sum_kernel(FitSumArgs P, double *__restrict__ partial)
 {
@@ -201,7 +219,7 @@ void fit_sum_kernel(FitSumArgs P, double *__restrict__ partial)
         if (fit_pass(P.g, c)) fit_terms<KIND>(P, c, acc);
     };
     FitTile T;
-    fit_load(P.f, blockIdx.x, T);
+    fit_load<WIDE>(P.f, blockIdx.x, T);
     fit_each(P.f, T, take);
     fit_tail(P.f, blockIdx.x, take);
 #pragma unroll
@@ -241,6 +259,7 @@ __global__ void fit_finish_kernel(const double *__restrict__ partial, uint32_t c
 constexpr int kScoreMax = 32;
 struct FitModels { double m[kScoreMax][9]; };
 
+template <int WIDE>
 __global__ __launch_bounds__(256)
 void fit_score_kernel(FitField A, FitModels M, int K, float thr, uint32_t chunks, uint32_t *__restrict__ counts)
 {
@@ -249,7 +268,7 @@ void fit_score_kernel(FitField A, FitModels M, int K, float thr, uint32_t chunks
     __syncthreads();
     for (uint32_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
         FitTile T;
-        fit_load(A, chunk, T);
+        fit_load<WIDE>(A, chunk, T);
 #pragma unroll 1
         for (int k = 0; k < K; ++k) {
             const double *Mk = M.m[k];
@@ -307,6 +326,7 @@ __global__ void fit_med_init_kernel(uint32_t *__restrict__ ws, uint32_t lo, uint
 
 // One pass for nm models: LDS histograms of this pass's digit over the residuals whose higher digits equal the prefix of
 // rank lo (histogram 0) or of rank hi (histogram 1, only while the prefixes differ), merged with one atomic per used bin.
+template <int WIDE>
 __global__ __launch_bounds__(256)
 void fit_med_hist_kernel(FitField A, FitModels3 M, int nm, int pass, uint32_t chunks, uint32_t *__restrict__ ws)
 {
@@ -317,7 +337,7 @@ void fit_med_hist_kernel(FitField A, FitModels3 M, int nm, int pass, uint32_t ch
     const uint32_t dmask = pass == 2 ? 0x3ffu : 0x7ffu;
     for (uint32_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
         FitTile T;
-        fit_load(A, chunk, T);
+        fit_load<WIDE>(A, chunk, T);
 #pragma unroll 1
         for (int k = 0; k < nm; ++k) {
             const uint32_t *st = ws + (size_t)k * kModelWords + 2 * kBins;
@@ -512,13 +532,15 @@ FitLayout fit_layout(size_t n)
     return L;
 }
 
-int fit_field(const char *who, const float *flow, const uint8_t *mask, int H, int W, int sign, FitField &A)
+// wide: vectors on the 16-byte and mask on the 4-byte grid, what the float4 / mask-word loads of fit_load<1> need; the
+// sampling kernels (count, pick, gather) load 8-byte vectors and mask bytes in either case
+int fit_field(const char *who, const float *flow, const uint8_t *mask, int H, int W, int sign, FitField &A, bool *wide = nullptr)
 {
     if (!flow || H <= 0 || W <= 0) return fail(OFL_E_INVALID, "%s: bad arguments", who);
     if (sign != 1 && sign != -1) return fail(OFL_E_INVALID, "%s: sign must be +1 or -1", who);
     if ((size_t)H * W > 0x7fffffffu) return fail(OFL_E_INVALID, "%s: fields of more than 2^31 - 1 px are not supported", who);
-    if ((reinterpret_cast<uintptr_t>(flow) & 15) || (reinterpret_cast<uintptr_t>(mask) & 3))
-        return fail(OFL_E_INVALID, "%s: flow must be 16-byte, mask 4-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(flow) & 7) return fail(OFL_E_INVALID, "%s: flow must be 8-byte aligned", who);
+    if (wide) *wide = !(reinterpret_cast<uintptr_t>(flow) & 15) && !(reinterpret_cast<uintptr_t>(mask) & 3);
     A.flow = flow; A.mask = mask; A.n = (uint32_t)((size_t)H * W); A.W = W; A.sign = sign;
     return OFL_OK;
 }
@@ -539,7 +561,8 @@ int fit_sums(const char *who, const float *flow, const uint8_t *mask, int H, int
 {
     OFL_TRY(need_device());
     FitSumArgs P;
-    OFL_TRY(fit_field(who, flow, mask, H, W, sign, P.f));
+    bool wide;
+    OFL_TRY(fit_field(who, flow, mask, H, W, sign, P.f, &wide));
     OFL_TRY(fit_gate(who, gate_model, gate_thr, P.g));
     if (!norm || !out || !workspace || (KIND == FIT_GN && !model)) return fail(OFL_E_INVALID, "%s: NULL pointer", who);
     const FitLayout L = fit_layout(P.f.n);
@@ -548,7 +571,8 @@ int fit_sums(const char *who, const float *flow, const uint8_t *mask, int H, int
     for (int i = 0; i < 9; ++i) P.model[i] = model ? model[i] : 0.0;
     hipStream_t s = stream_of(stream);
     double *partial = reinterpret_cast<double *>((char *)workspace + L.partial_off);
-    hipLaunchKernelGGL((fit_sum_kernel<KIND>), dim3(L.chunks), dim3(256), 0, s, P, partial);
+    if (wide) hipLaunchKernelGGL((fit_sum_kernel<KIND, 1>), dim3(L.chunks), dim3(256), 0, s, P, partial);
+    else      hipLaunchKernelGGL((fit_sum_kernel<KIND, 0>), dim3(L.chunks), dim3(256), 0, s, P, partial);
     hipLaunchKernelGGL(fit_finish_kernel, dim3(1), dim3(64), 0, s, (const double *)partial, L.chunks, FitSums<KIND>::S, out);
     OFL_HIP(hipGetLastError());
     return OFL_OK;
@@ -599,7 +623,8 @@ int ofl_fit_score_dev(const float *flow, const uint8_t *mask, int H, int W, int 
 {
     OFL_TRY(need_device());
     FitField A;
-    OFL_TRY(fit_field("ofl_fit_score", flow, mask, H, W, sign, A));
+    bool wide;
+    OFL_TRY(fit_field("ofl_fit_score", flow, mask, H, W, sign, A, &wide));
     if (!models || !counts || K < 1 || K > kScoreMax) return fail(OFL_E_INVALID, "ofl_fit_score: K must be in [1, %d]", kScoreMax);
     FitModels M;
     memset(&M, 0, sizeof(M));
@@ -607,7 +632,9 @@ int ofl_fit_score_dev(const float *flow, const uint8_t *mask, int H, int W, int 
     hipStream_t s = stream_of(stream);
     OFL_HIP(hipMemsetAsync(counts, 0, (size_t)K * sizeof(uint32_t), s));
     const uint32_t chunks = fit_chunks(A.n);
-    hipLaunchKernelGGL(fit_score_kernel, dim3(fit_stream_grid(chunks, 2)), dim3(256), 0, s, A, M, K, thr, chunks, counts);
+    const dim3 grid(fit_stream_grid(chunks, 2)), block(256);
+    if (wide) hipLaunchKernelGGL((fit_score_kernel<1>), grid, block, 0, s, A, M, K, thr, chunks, counts);
+    else      hipLaunchKernelGGL((fit_score_kernel<0>), grid, block, 0, s, A, M, K, thr, chunks, counts);
     OFL_HIP(hipGetLastError());
     return OFL_OK;
 }
@@ -617,7 +644,8 @@ int ofl_fit_median_dev(const float *flow, const uint8_t *mask, int H, int W, int
 {
     OFL_TRY(need_device());
     FitField A;
-    OFL_TRY(fit_field("ofl_fit_median", flow, mask, H, W, sign, A));
+    bool wide;
+    OFL_TRY(fit_field("ofl_fit_median", flow, mask, H, W, sign, A, &wide));
     if (!models || !out || !workspace || K < 1) return fail(OFL_E_INVALID, "ofl_fit_median: bad arguments");
     if (rank_lo > rank_hi || rank_hi >= A.n) return fail(OFL_E_INVALID, "ofl_fit_median: ranks %zu, %zu outside a field of %u px", rank_lo, rank_hi, A.n);
     const FitLayout L = fit_layout(A.n);
@@ -632,7 +660,8 @@ int ofl_fit_median_dev(const float *flow, const uint8_t *mask, int H, int W, int
         memcpy(M.m, models + (size_t)k0 * 9, (size_t)nm * 9 * sizeof(double));
         hipLaunchKernelGGL(fit_med_init_kernel, dim3(nm), dim3(256), 0, s, ws, (uint32_t)rank_lo, (uint32_t)rank_hi);
         for (int pass = 0; pass < 3; ++pass) {
-            hipLaunchKernelGGL(fit_med_hist_kernel, dim3(grid), dim3(256), 0, s, A, M, nm, pass, L.chunks, ws);
+            if (wide) hipLaunchKernelGGL((fit_med_hist_kernel<1>), dim3(grid), dim3(256), 0, s, A, M, nm, pass, L.chunks, ws);
+            else      hipLaunchKernelGGL((fit_med_hist_kernel<0>), dim3(grid), dim3(256), 0, s, A, M, nm, pass, L.chunks, ws);
             hipLaunchKernelGGL(fit_med_select_kernel, dim3(nm), dim3(256), 0, s, ws, pass, out + 2 * (size_t)k0);
         }
     }

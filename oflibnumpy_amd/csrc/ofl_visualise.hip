@@ -295,15 +295,32 @@ __device__ __forceinline__ uint32_t vis_one(const VisArgs &A, float u, float v, 
 }
 
 // Four pixels per lane and step: two 16-byte loads of vectors, one mask word, three dwords of output.  The batch is one
-// linear run of batch * H * W pixels; a group of four may straddle rows and fields.
+// linear run of batch * H * W pixels; a group of four may straddle rows and fields.  WIDE 0 serves vectors 8 bytes off the
+// 16-byte grid or a mask off the 4-byte grid (a view inside a batch of odd fields): the same four pixels per lane from
+// four 8-byte loads and four mask bytes.
+template <int WIDE>
 __global__ __launch_bounds__(256)
 void vis_render_kernel(VisArgs A)
 {
     const size_t groups = A.total / 4, stride = (size_t)gridDim.x * blockDim.x;
     const float4 *f4 = reinterpret_cast<const float4 *>(A.flow);
+    const float2 *f2 = reinterpret_cast<const float2 *>(A.flow);
     for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
-        const float4 a = f4[2 * g], b = f4[2 * g + 1];
-        const uint32_t mw = A.mask ? reinterpret_cast<const uint32_t *>(A.mask)[g] : 0x01010101u;
+        float4 a, b;
+        uint32_t mw = 0x01010101u;
+        if (WIDE) {
+            a = f4[2 * g];
+            b = f4[2 * g + 1];
+            if (A.mask) mw = reinterpret_cast<const uint32_t *>(A.mask)[g];
+        } else {
+            const float2 p0 = f2[4 * g], p1 = f2[4 * g + 1], p2 = f2[4 * g + 2], p3 = f2[4 * g + 3];
+            a = make_float4(p0.x, p0.y, p1.x, p1.y);
+            b = make_float4(p2.x, p2.y, p3.x, p3.y);
+            if (A.mask) {
+                const uint8_t *m = A.mask + 4 * g;
+                mw = (uint32_t)m[0] | ((uint32_t)m[1] << 8) | ((uint32_t)m[2] << 16) | ((uint32_t)m[3] << 24);
+            }
+        }
         const size_t p0 = 4 * g;
         size_t f = p0 / A.n;
         const size_t r = p0 - f * A.n;
@@ -381,15 +398,18 @@ int ofl_visualise_dev(const float *flow, const uint8_t *mask, int H, int W, int 
     if (!flow || !out || H <= 0 || W <= 0 || batch <= 0) return fail(OFL_E_INVALID, "ofl_visualise: bad arguments");
     if (mode != OFL_VIS_HSV && mode != OFL_VIS_RGB && mode != OFL_VIS_BGR) return fail(OFL_E_INVALID, "ofl_visualise: mode %d", mode);
     if (flags & ~(OFL_VIS_SHOW_MASK | OFL_VIS_MASK_BORDERS)) return fail(OFL_E_INVALID, "ofl_visualise: flags 0x%x", flags);
-    if ((reinterpret_cast<uintptr_t>(flow) & 15) || (reinterpret_cast<uintptr_t>(out) & 3) || (reinterpret_cast<uintptr_t>(mask) & 3))
-        return fail(OFL_E_INVALID, "ofl_visualise: flow must be 16-byte, mask and out 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(flow) & 7) || (reinterpret_cast<uintptr_t>(out) & 3))
+        return fail(OFL_E_INVALID, "ofl_visualise: flow must be 8-byte, out 4-byte aligned");
+    const bool wide = !(reinterpret_cast<uintptr_t>(flow) & 15) && !(reinterpret_cast<uintptr_t>(mask) & 3);
     if (!range_dev && !(range_const > 0.0f)) return fail(OFL_E_INVALID, "ofl_visualise: range_const must be > 0");
     VisArgs A;
     A.flow = flow; A.mask = mask; A.H = H; A.W = W;
     A.n = (size_t)H * W; A.total = A.n * batch;
     A.th = threshold; A.range_dev = range_dev; A.range_const = range_const;
     A.mode = mode; A.flags = flags; A.out = out;
-    hipLaunchKernelGGL(vis_render_kernel, dim3(vis_stream_grid(A.total / 4)), dim3(256), 0, stream_of(stream), A);
+    const dim3 grid(vis_stream_grid(A.total / 4)), block(256);
+    if (wide) hipLaunchKernelGGL((vis_render_kernel<1>), grid, block, 0, stream_of(stream), A);
+    else      hipLaunchKernelGGL((vis_render_kernel<0>), grid, block, 0, stream_of(stream), A);
     OFL_HIP(hipGetLastError());
     return OFL_OK;
 }
