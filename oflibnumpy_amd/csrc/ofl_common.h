@@ -20,6 +20,7 @@ Runtime &rt();
 int  fail(int code, const char *fmt, ...);          // records the message, returns `code`
 int  hip_fail(hipError_t e, const char *what);      // OFL_E_HIP (or OFL_E_NOMEM) with the HIP text
 int  need_device();                                  // OFL_OK or OFL_E_NODEVICE
+int  check_field_dims(const char *who, int H, int W);   // OFL_OK, or OFL_E_INVALID unless H and W are in [1, 32766]
 
 inline hipStream_t stream_of(void *s) { return s ? (hipStream_t)s : rt().stream; }
 

@@ -137,7 +137,7 @@ int check_consistency_args(const char *who, const void *f, const void *fm, const
 {
     if (!f || !fm || !b || !bm || !consistent) return fail(OFL_E_INVALID, "%s: NULL pointer (f, fm, b, bm and consistent are required)", who);
     // the taps are int16 inside cv2.remap, as for ofl_compose3
-    if (H <= 0 || W <= 0 || H > 32766 || W > 32766) return fail(OFL_E_INVALID, "%s: H, W must be in [1, 32766] (got %d x %d)", who, H, W);
+    OFL_TRY(check_field_dims(who, H, W));
     if (batch < 1 || batch > 65535) return fail(OFL_E_INVALID, "%s: batch must be in [1, 65535], got %d", who, batch);
     if (sign != 1 && sign != -1) return fail(OFL_E_INVALID, "%s: sign must be +1 or -1", who);
     if (!(alpha >= 0.0f) || !(beta >= 0.0f) || !__builtin_isfinite(alpha) || !__builtin_isfinite(beta))

@@ -264,9 +264,7 @@ int check_dims(const char *who, int N, int C, int H, int W)
 {
     if (N < 1 || N > 65535 || C < 1 || C > 65535)
         return fail(OFL_E_INVALID, "%s: N and C must be in [1, 65535] (got %d and %d)", who, N, C);
-    if (H < 1 || W < 1 || H > 32766 || W > 32766)
-        return fail(OFL_E_INVALID, "%s: H, W must be in [1, 32766] (got %d x %d)", who, H, W);
-    return OFL_OK;
+    return check_field_dims(who, H, W);
 }
 
 // everything of a lookup but the pointers

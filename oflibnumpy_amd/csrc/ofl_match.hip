@@ -305,7 +305,7 @@ int check_match_settings(const char *who, int elem, int N, int C, int H, int W, 
         return fail(OFL_E_INVALID, "%s: elem must be OFL_EL_F16, OFL_EL_BF16 or OFL_EL_F32 (got %d)", who, elem);
     if (N < 1 || N > 65535) return fail(OFL_E_INVALID, "%s: N must be in [1, 65535] (got %d)", who, N);
     if (C < 1 || C > kMaxC) return fail(OFL_E_INVALID, "%s: C must be in [1, %d] (got %d)", who, kMaxC, C);
-    if (H < 1 || W < 1 || H > 32766 || W > 32766) return fail(OFL_E_INVALID, "%s: H, W must be in [1, 32766] (got %d x %d)", who, H, W);
+    OFL_TRY(check_field_dims(who, H, W));
     if (sign != 1 && sign != -1) return fail(OFL_E_INVALID, "%s: sign must be +1 or -1", who);
     if (!(min_conf >= 0.0f)) return fail(OFL_E_INVALID, "%s: min_conf must be >= 0 and not NaN", who);
     return OFL_OK;

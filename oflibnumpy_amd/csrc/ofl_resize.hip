@@ -5,6 +5,7 @@
 // the vector L1 / L2), every output pixel is written once with 16-byte stores.
 #include "ofl_common.h"
 #include "ofl_host_stage.h"
+#include "ofl_pairs.h"
 #include <stdlib.h>
 
 #pragma clang fp contract(off)
@@ -12,8 +13,6 @@
 using namespace ofl;
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct ResizeCoef { int s0, s1; float w0, w1; };
 
@@ -110,8 +109,6 @@ void resize_flow_kernel(const float2 *__restrict__ src, const uint8_t *__restric
 // of one load pair per pixel -- 9 to 13 memory instructions per four pixels instead of 20; the values are picked from the
 // loaded run by index.  Same arithmetic per pixel as resize_px: bit-identical output.
 struct __attribute__((aligned(8))) Pair2f { float2 lo, hi; };
-struct __attribute__((packed, aligned(1))) U32u { uint32_t v; };
-struct __attribute__((packed, aligned(1))) U16u { uint16_t v; };
 
 __device__ __forceinline__ float2 pick6(int i, const float2 (&v)[6])
 {

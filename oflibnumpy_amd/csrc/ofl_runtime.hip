@@ -45,6 +45,14 @@ int need_device()
     return OFL_OK;
 }
 
+int check_field_dims(const char *who, int H, int W)
+{
+    // cv2.remap asserts src/dst dims < SHRT_MAX (coordinates are int16 inside OpenCV)
+    if (H < 1 || W < 1 || H > 32766 || W > 32766)
+        return fail(OFL_E_INVALID, "%s: H, W must be in [1, 32766] (got %d x %d)", who, H, W);
+    return OFL_OK;
+}
+
 }  // namespace ofl
 
 using namespace ofl;

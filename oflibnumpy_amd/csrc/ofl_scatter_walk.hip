@@ -13,6 +13,7 @@
 // next) and interpolates with SciPy's inclusion rule and float64 barycentric coordinates.  Every affine field of the
 // reference's tests and of BASELINE configs 1-4 is certified; anything else goes to the exact path (ofl_delaunay.hip).
 #include "ofl_scatter_dev.h"
+#include "ofl_pairs.h"
 #include <math.h>
 
 
@@ -243,9 +244,6 @@ void scatter_certify_kernel(const float *__restrict__ flow, int sign, const uint
 
 // ------------------------------------------------------------------------------------------------ walk
 struct Hit { uint32_t vi[3]; double c0, c1, c2; };
-
-
-struct __attribute__((aligned(8))) Pair2 { float lo_u, lo_v, hi_u, hi_v; };    // two adjacent vectors: ONE 16-byte load
 
 template <int SP>          // SP = sign with the point precision folded in: +-1 float64 positions, +-2 rounded to float32
 __device__ __forceinline__ D2 warp_pt(int x, int y, float u, float v)

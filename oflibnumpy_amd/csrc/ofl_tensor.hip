@@ -232,8 +232,7 @@ int check_tensor_dims(const char *who, int N, int C, int H, int W)
     if (N < 1 || N > 65535) return fail(OFL_E_INVALID, "%s: N must be in [1, 65535], got %d", who, N);
     if (C < 1 || C > 65535) return fail(OFL_E_INVALID, "%s: C must be in [1, 65535], got %d", who, C);
     // cv2.remap asserts src/dst dims < SHRT_MAX, as K1 does
-    if (H <= 0 || W <= 0 || H > 32766 || W > 32766) return fail(OFL_E_INVALID, "%s: H, W must be in [1, 32766] (got %d x %d)", who, H, W);
-    return OFL_OK;
+    return check_field_dims(who, H, W);
 }
 
 template <int E>

@@ -3,7 +3,8 @@ flow generators the `Flow` class builds on.
 
 Mirrors the public names, argument meaning and exception types of the reference's
 src/oflibnumpy/utils.py; the numerics of the warp itself run in hand-written HIP kernels
-(csrc/ofl_gather.hip, csrc/ofl_scatter.hip) reached through the C ABI of include/ofl.h.
+(csrc/ofl_gather.hip for 't', csrc/ofl_scatter.hip for 's'; the fused composition of two fields is
+csrc/ofl_compose3.hip) reached through the C ABI of include/ofl.h.
 """
 import math
 from typing import Any, Union

@@ -1,5 +1,5 @@
 """NumPy statement of the streaming kernels of oflibnumpy_amd/csrc/ofl_stats.hip (K4 statistics, K5 axpy, flow extent,
-mask and, dtype conversion, grid offset, point sampling) and of the mask packing of ofl_gather.hip -- a helper of
+mask and, dtype conversion, grid offset, point sampling) and of the mask packing of ofl_compose3.hip -- a helper of
 test_stream_host.py and test_gpu_stream.py, not a test.
 
 Every function is the definition of include/ofl.h in explicit float32 / float64 NumPy operations, in the order of the

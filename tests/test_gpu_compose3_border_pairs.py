@@ -17,7 +17,7 @@ import pytest
 
 QUANT_OPENCV, QUANT_EXACT = 0, 1
 SHAPES = [(2, 16, 256), (2, 13, 130), (1, 1, 128), (1, 9, 2)]
-TILE_W, TILE_H, XPOSE_ROWS = 128, 8, 6       # kC3TileW, kC3TileH, kXposeRows (ofl_gather.hip)
+TILE_W, TILE_H, XPOSE_ROWS = 128, 8, 6       # kC3TileW, kC3TileH (ofl_compose3.hip), kXposeRows (ofl_pairs.h)
 COLUMN_CLASSES = ("left", "d-1", "d0", "d+1", "right")
 
 

@@ -1,5 +1,5 @@
 """The streaming kernels of ofl_stats.hip (K4 statistics, K5 axpy, flow extent, mask and, dtype conversion, grid offset, point
-sampling) and the mask packing of ofl_gather.hip against tests/stream_ref.py, bit for bit.  Nothing here has a tolerance:
+sampling) and the mask packing of ofl_compose3.hip against tests/stream_ref.py, bit for bit.  Nothing here has a tolerance:
 words, mask bytes and the bits of every float -- NaN results with their sign and payload included -- are compared with
 array_equal.  One thing is left open because NumPy leaves it open: the sign of a zero extreme of the flow extent (np.min does
 not define it), so the extent alone is compared by value.

@@ -15,13 +15,13 @@ from oflibnumpy_amd import build_native as bn
 import kernel_resources
 from kernel_resources import FIELDS
 
-GATHER = os.path.join(bn.CSRC, "ofl_gather.hip")
+COMPOSE3 = os.path.join(bn.CSRC, "ofl_compose3.hip")
 KERNEL = re.compile(r"compose3_xpose_kernelILi([01])ELb([01])ELb0E")
 
 
 def _waves():
-    m = re.search(r"^constexpr int kC3Waves = (\d+);", open(GATHER).read(), re.M)
-    assert m, "kC3Waves not found in ofl_gather.hip"
+    m = re.search(r"^constexpr int kC3Waves = (\d+);", open(COMPOSE3).read(), re.M)
+    assert m, "kC3Waves not found in ofl_compose3.hip"
     return int(m.group(1))
 
 
@@ -32,7 +32,7 @@ def _key(name):
 
 @pytest.fixture(scope="module")
 def usage():
-    return kernel_resources.usage(GATHER, _key)
+    return kernel_resources.usage(COMPOSE3, _key)
 
 
 @pytest.mark.parametrize("quant", [0, 1])

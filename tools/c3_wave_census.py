@@ -4,7 +4,7 @@
     python tools/c3_wave_census.py [--height H] [--width W] [--variant V] [--ref t|s]
 
 CPU only (NumPy; no device, no oracle).  The fields are those of bench.py::make_pair (host Flow.from_transforms); the
-kernel's rules are restated here, each next to the name it has in oflibnumpy_amd/csrc/ofl_gather.hip:
+kernel's rules are restated here, each next to the name it has in oflibnumpy_amd/csrc/ofl_compose3.hip:
 
   c3_pos       position = float32(x -/+ u), one float32 operation
   c3_tap       QUANT_OPENCV: top-left tap = rint(32 p) >> 5
