@@ -10,7 +10,10 @@
 //               piecewise-affine map: one kernel, no atomics, no owner map.  All affine fields take this path.
 //   Delaunay    (ofl_delaunay.hip)      everything else: the kept points are bucket-sorted, every point builds its
 //               Delaunay star (Voronoi cell by half-plane clipping with a security radius), the stars' triangles are
-//               scan-converted into an owner map and resolved; query positions walk through the stars.
+//               scan-converted into an owner map and resolved; query positions walk through the stars.  That file holds
+//               the map of the path, its driver and the entries; the kernels are in ofl_delaunay_bin.hip (binning, scans,
+//               compaction), ofl_delaunay_stars.hip / ofl_delaunay_far.hip (per-thread / cooperative star passes) and
+//               ofl_delaunay_raster.hip (raster, resolve, query), the workspace they share in ofl_delaunay_ws.h.
 //
 // There is no approximate path: wherever SciPy's triangulation is unique the interpolant is the same function
 // (tests/test_gpu_scatter*.py against outputs of the real reference).

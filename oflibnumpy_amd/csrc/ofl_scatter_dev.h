@@ -8,7 +8,7 @@ namespace ofl_sc {
 
 constexpr double   kEps       = 100.0 * 2.220446049250313e-16;   // scipy _qhull: eps = 100 * DBL_EPSILON
 // Byte offset, in the first 256 bytes of a scatter workspace, of the stamp step 1 of the slab-wise scatter leaves for step 2
-// (ofl_delaunay.hip: DlHead::slab_stamp, static_assert there).  The certificate pass writes its own 144-byte record over the
+// (ofl_delaunay_ws.h: DlHead::slab_stamp, static_assert there).  The certificate pass writes its own 144-byte record over the
 // front of the same header: it clears the stamp, so that a slab state it has trampled on is refused by step 2.
 constexpr size_t   kSlabStampAt = 184;
 
@@ -182,7 +182,8 @@ int walk_query_launch(const float *flow, int sign_pp, const float *vals, int C, 
                       const void *query, size_t n, bool sparse, void *out, uint8_t *valid, int valid_rule,
                       const ofl_mesh_cert *cert, uint32_t *fail_dev, hipStream_t s);
 
-// exact path (ofl_delaunay.hip): Delaunay triangulation of the kept points on the GPU
+// exact path (ofl_delaunay.hip; its stages in ofl_delaunay_{bin,stars,far,raster}.hip): Delaunay triangulation of the kept
+// points on the GPU
 size_t exact_workspace_bytes(int H, int W);
 template <typename VT>
 int exact_scatter(const float *flow, int sign_pp, const uint8_t *pmask, const VT *vals, int C, const uint8_t *vmask,

@@ -298,7 +298,7 @@ def sec_delaunay(it, which=None):
         del v, m
         t = timed([(lambda d=d: d.invert()) for d in ds], max(it // 2, 2 * len(ds)))
         yield entry("k3_{}_4k".format(name), "invert s->s, {} (K3, Delaunay path)".format(name), (h, w), 18, *t,
-                    kernel="dl_* (ofl_delaunay.hip: bins, stars, raster, resolve)", note=DELAUNAY_NOTES[name])
+                    kernel="dl_* (ofl_delaunay_{bin,stars,far,raster}.hip: bins, stars, raster, resolve)", note=DELAUNAY_NOTES[name])
         del ds
 
 
