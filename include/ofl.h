@@ -132,6 +132,17 @@ int         ofl_mem_info(size_t *free_bytes, size_t *total_bytes);
  * raw = inflated IDAT stream (height rows of 1 filter byte + stride bytes), out [height][stride]; no device needed */
 int         ofl_png_unfilter(const uint8_t *raw, size_t raw_bytes, int height, int stride, int bpp, uint8_t *out);
 
+/* ------------------------------------------------------------------ non-finite flow vectors in K1, K2, K12 and K13
+ * These four turn a flow vector into an address.  A vector with a non-finite component samples nothing: value 0, invalid --
+ * every tap is outside the source, as for a vector that points beyond int32 (cvtss2si gives INT_MIN for all of them, which
+ * is what cv2.remap and oracle/ofl_oracle.c see), and no address depends on it.  "Invalid" is mout / valid / covered /
+ * consistent = 0.  "Value 0" is the sampled term: K2 and K13 go on to add it to the vector itself, which is not finite.  Under
+ * OFL_QUANT_EXACT a NaN or Inf coordinate has no fraction either: the four weights are NaN and the sampled term, four zero taps
+ * times NaN, is NaN as in the oracle.  NaN / Inf in the SAMPLED data travel through the blend unchanged, a tap of weight 0
+ * included (0 * NaN); the host Flow refuses such fields, device-resident chains may carry them.
+ * tests/test_gpu_nonfinite.py.
+ */
+
 /* ------------------------------------------------------------------ K2: fused mode-3 composition
  * Replaces Flow.combine_with(mode=3) numerics, flow_class.py:1412-1422 (+ Flow.apply :632-684,
  * apply_flow 't' utils.py:231-236, Flow.__add__ :332-334):

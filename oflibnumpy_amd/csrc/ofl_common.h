@@ -83,13 +83,19 @@ __device__ __forceinline__ int sat_s16(int v) { return min(max(v, -32768), 32767
 // ends land outside every admissible image (dims <= 32766) after the int16 saturation.
 __device__ __forceinline__ int cv_round(float v) { return __float2int_rn(v); }
 
+// cvRound of a sample COORDINATE (already times 32).  NaN is where the two conversions part: cvtss2si makes it INT_MIN, a tap
+// outside every image, v_cvt_i32_f32 makes it 0, a tap on column or row 0.  fmaxf returns its other operand for a NaN one
+// (v_max_f32; a product is never a signalling NaN), so NaN becomes the -2^31 that converts to INT_MIN, and nothing else
+// changes: below -2^31 the conversion saturates to INT_MIN as before.  A vector with a NaN component samples nothing.
+__device__ __forceinline__ int cv_round_coord(float v) { return cv_round(fmaxf(v, -2147483648.0f)); }
+
 template <int QUANT>
 __device__ __forceinline__ Tap make_tap(float px, float py)
 {
     Tap t;
     if (QUANT == OFL_QUANT_OPENCV) {
-        int sx = cv_round(__fmul_rn(px, 32.0f));
-        int sy = cv_round(__fmul_rn(py, 32.0f));
+        int sx = cv_round_coord(__fmul_rn(px, 32.0f));
+        int sy = cv_round_coord(__fmul_rn(py, 32.0f));
         t.ax = sx & 31;
         t.ay = sy & 31;
         t.ix = sat_s16(sx >> 5);

@@ -90,7 +90,7 @@ __device__ __forceinline__ C3Pos c3_pos(int gx, int gy, float fu, float fv, int 
 {
     const float px = sign >= 0 ? __fadd_rn((float)gx, fu) : __fsub_rn((float)gx, fu);
     const float py = sign >= 0 ? __fadd_rn((float)gy, fv) : __fsub_rn((float)gy, fv);
-    if (QUANT == OFL_QUANT_OPENCV) return { cv_round(__fmul_rn(px, 32.0f)), cv_round(__fmul_rn(py, 32.0f)) };
+    if (QUANT == OFL_QUANT_OPENCV) return { cv_round_coord(__fmul_rn(px, 32.0f)), cv_round_coord(__fmul_rn(py, 32.0f)) };
     return { __float_as_int(px), __float_as_int(py) };
 }
 
@@ -396,7 +396,10 @@ __device__ __forceinline__ void c3_classify(const C3Pos &p, int H, int W, bool a
 {
     const int ix = c3_tap<QUANT>(p.x), iy = c3_tap<QUANT>(p.y);
     const bool in_j  = (unsigned)ix <= (unsigned)(W - 2) && (unsigned)iy <= (unsigned)(H - 2);
-    const bool out_j = ix < -1 || ix >= W || iy < -1 || iy >= H;
+    bool out_j = ix < -1 || ix >= W || iy < -1 || iy >= H;
+    // QUANT_EXACT: a NaN or Inf coordinate has no fraction, its weights are NaN and so is its blend of four zeros (the oracle's
+    // 0 * NaN); such a pixel takes the border path, which multiplies, and never the shortcut that writes 0 for a whole wave
+    if (QUANT == OFL_QUANT_EXACT) out_j = out_j && __builtin_isfinite(__int_as_float(p.x)) && __builtin_isfinite(__int_as_float(p.y));
     inside  = inside && (in_j || !act);
     outside = outside && (out_j || !act);
 }

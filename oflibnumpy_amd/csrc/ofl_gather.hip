@@ -376,7 +376,10 @@ __device__ __forceinline__ void gather2_core(const T *__restrict__ src, const ui
             wi[j][2] = __float2int_rn(tp[j].w2 * 32768.0f); wi[j][3] = __float2int_rn(tp[j].w3 * 32768.0f);
         }
         const bool in_j  = (unsigned)tp[j].ix <= (unsigned)(W - 2) && (unsigned)tp[j].iy <= (unsigned)(H - 2);
-        const bool out_j = tp[j].ix < -1 || tp[j].ix >= W || tp[j].iy < -1 || tp[j].iy >= H;
+        bool out_j = tp[j].ix < -1 || tp[j].ix >= W || tp[j].iy < -1 || tp[j].iy >= H;
+        // un-snapped weights of a NaN or Inf coordinate are NaN, and so is their blend of four zeros (the oracle's 0 * NaN): such a
+        // pixel takes the border path, which multiplies, and never the shortcut that writes 0 for a whole wave
+        if (quant != OFL_QUANT_OPENCV) out_j = out_j && (tp[j].w0 == tp[j].w0) && (tp[j].w3 == tp[j].w3);
         inside  = inside && (in_j || !act4[j]);
         outside = outside && (out_j || !act4[j]);
     }

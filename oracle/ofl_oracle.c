@@ -105,9 +105,11 @@ static inline void make_tap(float px, float py, int quant, tap_t *t)
     } else {
         float flx = floorf(px), fly = floorf(py);
         float fx = px - flx, fy = py - fly;
-        /* clamp to the int16 range the snapped path uses */
-        flx = flx < -32768.0f ? -32768.0f : (flx > 32767.0f ? 32767.0f : flx);
-        fly = fly < -32768.0f ? -32768.0f : (fly > 32767.0f ? 32767.0f : fly);
+        /* clamp to the int16 range the snapped path uses.  fmaxf returns its other operand for a NaN one, so a NaN
+         * coordinate becomes -32768, a tap outside every image, before the cast (the device's clamp, and the snapped
+         * path's INT_MIN); its fraction stays NaN, so the weights and the blend of the four zero taps are NaN. */
+        flx = fminf(fmaxf(flx, -32768.0f), 32767.0f);
+        fly = fminf(fmaxf(fly, -32768.0f), 32767.0f);
         t->ix = (int)flx; t->iy = (int)fly;
         float x0 = 1.0f - fx, y0 = 1.0f - fy;
         t->w[0] = y0 * x0; t->w[1] = y0 * fx; t->w[2] = fy * x0; t->w[3] = fy * fx;

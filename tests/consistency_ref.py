@@ -19,6 +19,13 @@ QUANTS = [O.QUANT_OPENCV, O.QUANT_EXACT]
 F32 = np.float32
 
 
+def _same_floats(a, b):
+    """identical bits, except that a NaN may carry any payload: which operand's payload a sum of two NaNs hands on depends on the
+    order the compiler gives the operands"""
+    nan = np.isnan(b)
+    return np.array_equal(np.isnan(a), nan) and np.array_equal(a.view(np.uint32)[~nan], b.view(np.uint32)[~nan])
+
+
 def consistency(f, fm, b, bm, sign, alpha=ALPHA, beta=BETA, quant=O.QUANT_OPENCV):
     """-> (consistent bool, covered bool, residual float32, (n_covered, n_consistent))"""
     f, b = np.ascontiguousarray(f, F32), np.ascontiguousarray(b, F32)
@@ -28,7 +35,7 @@ def consistency(f, fm, b, bm, sign, alpha=ALPHA, beta=BETA, quant=O.QUANT_OPENCV
     covered = fm & whole
     ru, rv = fu + bu, fv + bv
     out, mout = O.compose3_raw(b, bm, f, fm, sign, quant)
-    assert np.array_equal(np.stack([ru, rv], -1).view(np.uint32), out.view(np.uint32)) and np.array_equal(covered, mout)
+    assert _same_floats(np.stack([ru, rv], -1), out) and np.array_equal(covered, mout)
     r2 = ru * ru + rv * rv
     s2 = (fu * fu + fv * fv) + (bu * bu + bv * bv)
     lim = F32(alpha) * s2 + F32(beta)

@@ -97,8 +97,8 @@ def make_tap(px, py, quant):
     """make_tap of ofl_common.h -> (ix, iy as int64, [w0, w1, w2, w3] as float32)"""
     with np.errstate(all="ignore"):
         if quant == QUANT_OPENCV:
-            def snap(p):                                            # cvRound of a float: round half even, saturating
-                s = np.nan_to_num(np.rint(p * F32(32.0)).astype(np.float64), nan=0.0, posinf=2.0 ** 31, neginf=-2.0 ** 31)
+            def snap(p):                                            # cv_round_coord: round half even, saturating, NaN -> INT_MIN
+                s = np.nan_to_num(np.rint(p * F32(32.0)).astype(np.float64), nan=-2.0 ** 31, posinf=2.0 ** 31, neginf=-2.0 ** 31)
                 s = np.clip(s, -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64)
                 return np.clip(s >> 5, -32768, 32767), (s & 31).astype(np.float32) * F32(1.0 / 32.0)
             (ix, fx), (iy, fy) = snap(px), snap(py)

@@ -604,6 +604,26 @@ def test_resize_matches_oracle(gpu, oracle):
             dv, dm = f.to_device().resize(scale).to_host()
             np.testing.assert_array_equal(dv, ev)
             np.testing.assert_array_equal(dm, em)
+    # One field with NaN, Inf and out-of-int32 vectors (device-resident chains carry them; the host Flow refuses them), through
+    # the raw entry.  K6's addresses do not depend on the values: NaN where the oracle has NaN -- the payload is the processor's
+    # own -- and identical bits everywhere else.
+    import nonfinite_cases as NF
+    from oflibnumpy_amd import device as dev
+    nat, lib = of.native, of.native.load()
+    bad = NF.case((2, 13, 131), 'random', 'sprinkle')
+    vecs, mask = bad['fb'][0], bad['mb'][0]
+    assert np.isnan(vecs).any() and np.isinf(vecs).any()
+    h, w = vecs.shape[:2]
+    d_vecs, d_mask = dev.DeviceBuffer.from_host(vecs), dev.DeviceBuffer.from_host(mask)
+    for fy, fx in ((0.5, 0.5), (1.5, 1.5), (2, 0.5)):
+        ev, em = O.resize_flow(vecs, (fy, fx), mask)
+        ho, wo = em.shape
+        assert np.isnan(ev).any()
+        d_out, d_mout = dev.DeviceBuffer(ev.nbytes), dev.DeviceBuffer(em.size)
+        nat.check(lib.ofl_resize_flow_dev(d_vecs.ptr, d_mask.ptr, h, w, ho, wo, 1.0 / fy, 1.0 / fx, float(np.float32(fx)), float(np.float32(fy)),
+                                          d_out.ptr, d_mout.ptr, None))
+        assert NF.same_floats(d_out.to_host(ev.shape, np.float32), ev), (fy, fx)
+        np.testing.assert_array_equal(d_mout.to_host(em.shape, np.uint8).astype(bool), em)
     small, large = (20, 40), (30, 80)
     m_small = np.ones(small, bool)
     m_small[:6, :20] = False
