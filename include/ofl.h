@@ -1010,6 +1010,68 @@ int ofl_global_match_dev(const void *f1, const void *f2, int elem, int N, int C,
 int ofl_global_match(const void *f1, const void *f2, int elem, int N, int C, int H, int W, float scale, int sign,
                      float min_conf, float *out_vecs, uint8_t *out_mask, float *out_conf, int32_t *out_index);
 
+/* ------------------------------------------------------------------ K20: forward warp by splatting
+ * The forward warp of a network pipeline (Niklaus & Liu, Softmax Splatting, CVPR 2020): every source pixel adds its value to
+ * the four pixels around where an 's'-reference field sends it, with bilinear weights times an importance factor.  Summation,
+ * average and softmax splatting; the weight plane alone (C = 0) is the range map "how many source pixels land here".  This is
+ * NOT the reference's 's' apply (griddata on the Delaunay path, K3) and does not replace it.
+ *     src    N items of C channels of OFL_EL_F32, OFL_EL_F16 or OFL_EL_BF16, (N, C, H, W) or (N, H, W, C) (K12's layouts)
+ *     flow   [H][W][2] float32 with fmask [H][W]: ONE field and mask for all items when flow_shared != 0, else N back to back
+ *     z      float32 [H][W] per field, the importance (OFL_SPLAT_SOFTMAX only; otherwise ignored, may be NULL);  alpha float
+ *     N in [1, 65535], C in [0, 65535], H and W as K12 allows; element offsets are 64-bit
+ * The sums are INTEGERS: int64 accumulators filled by 64-bit integer atomic adds (ordinary vector memory instructions), and
+ * the softmax shift is an integer atomic max.  Both commute, so the result is a function of the inputs alone and
+ * tests/splat_ref.py restates it with np.add.at / np.maximum.at byte for byte.
+ * Per source pixel (x, y); every float operation is float32 and rounded once (no FMA):
+ *   1. skipped if fmask == 0, or u or v is not finite, or px = float(x) + u or py = float(y) + v has magnitude >= 2^30, or --
+ *      softmax -- zs = alpha * z is not finite.  A skipped pixel contributes nothing and adds 1 to counters[0] (once per
+ *      pixel of a FIELD: a shared field counts once, not once per item).
+ *   2. x0 = floorf(px), fx = px - x0, likewise y; the four taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) have the
+ *      weights w = (1 - fx) * (1 - fy), fx * (1 - fy), (1 - fx) * fy, fx * fy.  A tap whose weight is exactly 0 or whose pixel
+ *      lies outside the frame does not exist: an integer landing touches one pixel.
+ *   3. e = 1 for OFL_SPLAT_SUM and OFL_SPLAT_AVERAGE.  OFL_SPLAT_SOFTMAX: a first launch records PER TARGET PIXEL the maximum
+ *      zs over all taps that exist there -- an integer atomic max on the order-preserving int32 key of the float
+ *      (b ^ ((b >> 31) & 0x7fffffff) of the bit pattern b), the plane initialised to the smallest key -- and the accumulate
+ *      launch forms t = zs - zmax[target] (<= 0) and e = t < -87 ? 0 : exp32(t), K17's exp32.  The shift cancels in the
+ *      ratio: this is softmax splatting exactly.  Because the shift is per target pixel and not per field, the largest
+ *      weight at every covered pixel has e = 1: no region whose importances are all low can be wiped out by the fixed point.
+ *   4. we = w * e; the tap pixel's weight accumulator gains the integer nearest to we * 2^32 (ties to even).
+ *   5. per channel val = we * float(I_c); the accumulator gains the integer nearest to val * 2^frac_bits (ties to even),
+ *      frac_bits in [0, 40], 24 by default.  A val that is NaN or has |val| * 2^frac_bits >= 2^62 contributes 0 and adds 1 to
+ *      counters[1].  The caller's precondition, not checked: landings per pixel * max |val| < 2^(63 - frac_bits).
+ * Per target pixel, with D the weight accumulator and A_c the channel accumulators, each converted to float64 to nearest:
+ *     weight = float32(D * 2^-32)                        valid = D >= the integer nearest to min_weight * 2^32
+ *     SUM:               out_c = float32(A_c * 2^-frac_bits)                          (valid is informational)
+ *     AVERAGE, SOFTMAX:  out_c = valid ? float32((A_c / D) * 2^(32 - frac_bits)) : 0
+ * 16-bit outputs are then rounded to storage with ofl_export_flow_dev's rounding: a SECOND rounding.  min_weight in
+ * [2^-20, 1], 2^-10 by default.  Consequence: every finite float16 is a multiple of 2^-24, so with frac_bits = 24 a float16
+ * tensor under an integer translation comes back byte for byte in AVERAGE and SUM; so does integer-valued float32 / bfloat16.
+ *     dst     as src (NULL allowed when C = 0)
+ *     valid   uint8, weight float32 (each may be NULL): [H][W] when flow_shared != 0, else [N][H][W]
+ *     counters  device uint32[2] or NULL, ADDED to by integer atomics: the caller zeroes it
+ *     workspace ofl_splat_workspace_bytes = 8 (C + 1) H W per item, plus 4 H W per field for softmax; 8-byte aligned; the
+ *               entry zeroes it on the stream.  Accumulators are channels-last [N][H][W][C + 1], the weight last.
+ * Launches: [the max pass,] accumulate, finish.  No loop depends on the data: a field that contracts everything into one
+ * pixel costs contention, not iterations.  flow 8-byte aligned, src / dst aligned to their element, z / weight / counters
+ * 4-byte, masks at any address; src may be the field's own vector buffer (C = 2, channels-last: the projection of a field).
+ * Outputs must not overlap inputs.  A bad argument -- a NULL flow or fmask, a NULL src or dst with C > 0, C = 0 without valid
+ * or weight, another elem, layout or mode, softmax without z or with a non-finite alpha, frac_bits or min_weight out of
+ * range, sizes out of range, an overlap, a misaligned pointer, a short workspace -- returns OFL_E_INVALID with a message
+ * before any launch.  The _dev entry is asynchronous; the host entry takes host pointers (counters_host: host uint32[2] or
+ * NULL, written, not added to), uploads, launches, downloads and synchronises.
+ * Not built: linear splatting, a backward pass, kernels other than bilinear, float accumulators, channel chunking to cap
+ * the workspace, combining the taps of neighbouring lanes before the atomic.
+ */
+enum { OFL_SPLAT_SUM = 0, OFL_SPLAT_AVERAGE = 1, OFL_SPLAT_SOFTMAX = 2 };
+int ofl_splat_workspace_bytes(int N, int C, int H, int W, int flow_shared, int mode, size_t *bytes);
+int ofl_splat_dev(const void *src, int elem, int layout, int N, int C, int H, int W,
+                  const float *flow, const uint8_t *fmask, int flow_shared, const float *z, float alpha,
+                  int mode, int frac_bits, float min_weight, void *workspace, size_t workspace_bytes,
+                  void *dst, uint8_t *valid, float *weight, uint32_t *counters, void *stream);
+int ofl_splat(const void *src, int elem, int layout, int N, int C, int H, int W,
+              const float *flow, const uint8_t *fmask, int flow_shared, const float *z, float alpha,
+              int mode, int frac_bits, float min_weight, void *dst, uint8_t *valid, float *weight, uint32_t *counters_host);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

@@ -27,6 +27,7 @@ TENSOR_NCHW, TENSOR_NHWC = 0, 1
 CORR_XY, CORR_YX = 0, 1
 CORR_V, CORR_L = 4, 16
 MATCH_TILE, MATCH_WAVES = 32, 4
+SPLAT_SUM, SPLAT_AVERAGE, SPLAT_SOFTMAX = 0, 1, 2
 
 
 class MeshCert(ctypes.Structure):
@@ -159,6 +160,10 @@ SIGNATURES = {
     "ofl_corr_lookup": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _ci, _cf, _ci, _ci, _vp]),
     "ofl_global_match_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cf, _ci, _cf, _vp, _vp, _vp, _vp, _vp]),
     "ofl_global_match": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cf, _ci, _cf, _vp, _vp, _vp, _vp]),
+    "ofl_splat_workspace_bytes": (_ci, [_ci, _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(_cs)]),
+    "ofl_splat_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _cf, _ci, _ci, _cf, _vp, _cs,
+                            _vp, _vp, _vp, _vp, _vp]),
+    "ofl_splat": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _cf, _ci, _ci, _cf, _vp, _vp, _vp, _vp]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

@@ -501,6 +501,63 @@ def match_host_array(a, name):
     return np.ascontiguousarray(np.moveaxis(a, 0, -1))[None], tuple(a.shape)
 
 
+# -- forward warp by splatting (K20)
+SPLAT_MODES = {'sum': nat.SPLAT_SUM, 'average': nat.SPLAT_AVERAGE, 'softmax': nat.SPLAT_SOFTMAX}
+SPLAT_MIN_WEIGHT = 2.0 ** -10
+SPLAT_FRAC_BITS = 24
+
+
+def splat_args(mode='average', has_importance=False, alpha=1.0, min_weight=None, frac_bits=None):
+    """Validation of the settings of a splat (K20) on the host before any device work -> (mode code, alpha, min_weight,
+    frac_bits): alpha and min_weight as float32, frac_bits a Python int.  mode: 'sum', 'average' or 'softmax'; softmax needs
+    an importance and the two others take none (`has_importance`); alpha: a finite number; min_weight: None for 2^-10, or a
+    number in [2^-20, 1]; frac_bits: None for 24, or an int in [0, 40].  A bool or a value of the wrong type is a TypeError,
+    a value outside its set a ValueError."""
+    prefix = "Error splatting: "
+    if not isinstance(mode, str):
+        raise TypeError("{}mode must be a string, got {}".format(prefix, type(mode).__name__))
+    if mode not in SPLAT_MODES:
+        raise ValueError("{}mode must be 'sum', 'average' or 'softmax', got {!r}".format(prefix, mode))
+    if mode == 'softmax' and not has_importance:
+        raise ValueError("{}mode 'softmax' needs an importance".format(prefix))
+    if mode != 'softmax' and has_importance:
+        raise ValueError("{}an importance is used by mode 'softmax' only, got mode {!r}".format(prefix, mode))
+    alpha = _float32_arg(alpha, "alpha", prefix)
+    min_weight = np.float32(SPLAT_MIN_WEIGHT) if min_weight is None else _float32_arg(min_weight, "min_weight", prefix)
+    if not 2.0 ** -20 <= min_weight <= 1.0:
+        raise ValueError("{}min_weight must be in [2^-20, 1], got {}".format(prefix, min_weight))
+    frac_bits = SPLAT_FRAC_BITS if frac_bits is None else frac_bits
+    if not _is_integer(frac_bits):
+        raise TypeError("{}frac_bits must be an integer or None, got {}".format(prefix, type(frac_bits).__name__))
+    if not 0 <= frac_bits <= 40:
+        raise ValueError("{}frac_bits must be in [0, 40], got {}".format(prefix, frac_bits))
+    return SPLAT_MODES[mode], alpha, min_weight, int(frac_bits)
+
+
+def splat_host_array(a, layout, field_shape):
+    """A tensor given to Flow.splat / splat_flow -> (contiguous array, n, c, batched): a NumPy array of float32 or float16 in
+    the memory order of `layout` -- (C, H, W) / (N, C, H, W) for 'chw', (H, W, C) / (N, H, W, C) for 'hwc' -- with the height
+    and width of the flow (TypeError for another type or dtype, the ValueErrors of tensor_args)."""
+    if not isinstance(a, np.ndarray):
+        raise TypeError("Error splatting: the tensor needs to be a numpy array, got {}".format(type(a).__name__))
+    if a.dtype != np.float32 and a.dtype != np.float16:
+        raise TypeError("Error splatting: the tensor needs to have dtype float32 or float16, got {}".format(a.dtype))
+    n, c, _, _, batched = tensor_args(tensor_logical_shape(a.shape, layout), layout, a.dtype.name, field_shape)
+    return np.ascontiguousarray(a), n, c, batched
+
+
+def splat_importance_array(z, shape):
+    """The importance given to a host splat -> None, or a contiguous float32 (H, W) array (TypeError for another type,
+    ValueError for another shape)."""
+    if z is None:
+        return None
+    if not isinstance(z, np.ndarray):
+        raise TypeError("Error splatting: importance needs to be a numpy array or None, got {}".format(type(z).__name__))
+    if z.shape != (shape[0], shape[1]):
+        raise ValueError("Error splatting: importance needs the shape of the flow {}, got {}".format(tuple(shape), z.shape))
+    return np.ascontiguousarray(z, np.float32)
+
+
 # -- many-channel float tensors (K12)
 def tensor_dtype(array_dtype, dtype=None):
     """The element type of a tensor -> 'float32', 'float16' or 'bfloat16'.  `array_dtype`: the dtype of the array that holds

@@ -190,6 +190,33 @@ class DeviceFlowBatch:
                                                  factor, batch=self.n)
         return DeviceFlowBatch.wrap(self.n, (factor * self.shape[0], factor * self.shape[1]), self.ref, out_vecs, out_mask)
 
+    def splat(self, tensor, mode='average', importance=None, alpha=1.0, min_weight=None, frac_bits=None, return_weight=False,
+              return_counters=False):
+        """self[i].splat(item i of `tensor`, ...) for every i in ONE set of launches of K20 (DeviceFlow.splat; ref 's'
+        batches): `tensor` a DeviceTensor (n, C, H, W) in either layout, `importance` a float32 DeviceBuffer [n][H][W] or
+        None.  -> (DeviceTensor, valid uint8 DeviceBuffer [n][H][W]); return_weight appends the float32 DeviceBuffer
+        [n][H][W], return_counters (skipped source pixels, dropped values) summed over the batch as Python ints -- the only
+        option that synchronises.  A packed batch is read through its byte masks."""
+        if self.ref != 's':
+            raise ValueError("Error splatting: splat pushes values forward along 's'-reference fields; 't'-reference fields "
+                             "warp backward, with apply_tensors")
+        if not isinstance(tensor, dev.DeviceTensor):
+            raise TypeError("Error splatting: tensor needs to be a DeviceTensor, got {}".format(type(tensor).__name__))
+        code, alpha, min_weight, frac_bits = dev.splat_args(mode, importance is not None, alpha, min_weight, frac_bits)
+        n, c, h, w, batched = dev.tensor_args(tensor.shape, tensor.layout, tensor.dtype, self.shape)
+        if not batched or n != self.n:
+            raise ValueError("Error splatting: a batch of {} fields takes a tensor of shape ({}, C, H, W), got {}"
+                             .format(self.n, self.n, tensor.shape))
+        z = dev.splat_importance(importance, self.n * h * w)
+        dst, valid, weight, counters = dev.splat_launch(tensor.buf, tensor.dtype, tensor.layout, n, c, self.shape, self.vecs,
+                                                        self.mask, False, code, alpha, min_weight, frac_bits, z=z,
+                                                        want_weight=bool(return_weight), want_counters=bool(return_counters))
+        res = (dev.DeviceTensor(dst, tensor.shape, tensor.dtype, tensor.layout), valid) + ((weight,) if return_weight else ())
+        if return_counters:
+            k = counters.to_host((2,), np.uint32)
+            res += ((int(k[0]), int(k[1])),)
+        return res
+
     def apply_images(self, images, dtype, channels, shared=False, target_masks=None, shared_masks=False, quant=nat.QUANT_OPENCV):
         """self[i].apply(image_i, target_mask_i, return_valid_area=True) for every i in ONE launch of the gather kernel
         (ref 't' batches; Flow.apply, flow_class.py:604-695 without padding).  `images`: a DeviceBuffer holding [n][H][W][C] of

@@ -32,14 +32,15 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rul
                    percentile_ranks, matrix_args, validate_transforms, valid_mask_array, scale_operand, crop_args,
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
                    consistency_args, error_args, fill_args, median_args, upsample_args, upsample_weights_array, corr_args,
-                   corr_host_array, optional_bool, mask_array_arg, match_args, match_host_array)
+                   corr_host_array, optional_bool, mask_array_arg, match_args, match_host_array, splat_args, splat_host_array,
+                   splat_importance_array)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
                       track_bilinear_launch, track_query_points, track_query_epilogue, gather_tensor, tensor_import_launch,
                       tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
                       FlowErrorStats, fill_launch, fill_host, median_launch, median_host, upsample_launch,
-                      upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host, match_launch, match_host)
+                      upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host, match_launch, match_host, splat_launch, splat_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -364,6 +365,15 @@ def mask_buffer_arg(buf, n_bytes, prefix, name):
         raise TypeError("{}{} needs to be a DeviceBuffer of uint8 or None, got {}".format(prefix, name, type(buf).__name__))
     if buf is not None and buf.nbytes < n_bytes:
         raise ValueError("{}{} needs to hold {} bytes, got {}".format(prefix, name, n_bytes, buf.nbytes))
+    return buf
+
+
+def splat_importance(buf, n_px):
+    """The `importance` of the splat methods: None, or a float32 buffer (DeviceBuffer or a view) of at least n_px values."""
+    if buf is not None and not isinstance(buf, (DeviceBuffer, _BufferView)):
+        raise TypeError("Error splatting: importance needs to be a DeviceBuffer of float32 or None, got {}".format(type(buf).__name__))
+    if buf is not None and buf.nbytes < 4 * n_px:
+        raise ValueError("Error splatting: importance needs to hold {} bytes, got {}".format(4 * n_px, buf.nbytes))
     return buf
 
 
@@ -735,6 +745,72 @@ class DeviceFlow:
         out_vecs, out_mask = upsample_launch(self.vecs, self.mask, weights.buf, weights.dtype, weights.layout, self.shape, factor)
         return DeviceFlow(out_vecs, out_mask, (factor * self.shape[0], factor * self.shape[1]), self.ref)
 
+    # -- forward warp by splatting (K20)
+    def _splat_field(self, what):
+        if self.ref != 's':
+            raise ValueError("Error splatting: {} pushes values forward along an 's'-reference field; a 't'-reference field "
+                             "warps backward, with apply_tensor".format(what))
+
+    def splat(self, tensor, mode='average', importance=None, alpha=1.0, min_weight=None, frac_bits=None, return_weight=False,
+              return_counters=False):
+        """Forward-warp an HBM-resident DeviceTensor -- (C, H, W) or (N, C, H, W), either layout, float32 / float16 /
+        bfloat16 -- by splatting (K20, include/ofl.h): every source pixel adds its channels to the four pixels around where
+        this 's'-reference field sends it, with bilinear weights.  mode 'sum' leaves the sums, 'average' divides by the summed
+        weight, 'softmax' weights source pixel p by exp(alpha * importance[p]) first -- `importance` a float32 DeviceBuffer
+        [H][W], e.g. `residual` out of consistency with a negative alpha, so that among colliding sources the consistent
+        one wins.  The sums are int64 fixed point with `frac_bits` fraction bits (None: 24), so the result does not depend
+        on the order the atomics arrive in; a target pixel is valid where its summed weight reaches `min_weight` (None:
+        2^-10), and an invalid pixel of 'average' / 'softmax' is 0.  This one field splats every item of a batched tensor.
+        -> (DeviceTensor of the input's shape, dtype and layout, valid uint8 DeviceBuffer [H][W]); return_weight appends the
+        float32 DeviceBuffer [H][W] of summed weights, return_counters appends (skipped source pixels, dropped values) as
+        Python ints -- the only option that synchronises.  A 't'-reference field raises ValueError (apply_tensor gathers
+        with those).  Not the reference's 's' apply: see apply_image for that.  The inputs are not modified."""
+        self._splat_field("splat")
+        if not isinstance(tensor, DeviceTensor):
+            raise TypeError("Error splatting: tensor needs to be a DeviceTensor, got {}".format(type(tensor).__name__))
+        code, alpha, min_weight, frac_bits = splat_args(mode, importance is not None, alpha, min_weight, frac_bits)
+        n, c, h, w, _ = tensor_args(tensor.shape, tensor.layout, tensor.dtype, self.shape)
+        z = splat_importance(importance, self.n_px)
+        dst, valid, weight, counters = splat_launch(tensor.buf, tensor.dtype, tensor.layout, n, c, self.shape, self.vecs, self.mask,
+                                                    True, code, alpha, min_weight, frac_bits, z=z, want_weight=bool(return_weight),
+                                                    want_counters=bool(return_counters))
+        res = (DeviceTensor(dst, tensor.shape, tensor.dtype, tensor.layout), valid) + ((weight,) if return_weight else ())
+        if return_counters:
+            k = counters.to_host((2,), np.uint32)
+            res += ((int(k[0]), int(k[1])),)
+        return res
+
+    def coverage(self, importance=None, alpha=1.0, min_weight=None):
+        """The range map of this 's'-reference field: how much bilinear weight lands on every pixel -- about 1 where the
+        field is a translation, above 1 where it contracts (occlusion), below where it expands, 0 where nothing arrives
+        (disocclusion) -- from K20 without channels.  With `importance` (float32 DeviceBuffer [H][W]) the weights are those of
+        softmax splatting, relative to the largest importance that reaches the pixel.  -> (weight float32 DeviceBuffer
+        [H][W], valid uint8 DeviceBuffer [H][W] = weight >= min_weight).  Nothing synchronises."""
+        self._splat_field("coverage")
+        mode = 'average' if importance is None else 'softmax'
+        code, alpha, min_weight, frac_bits = splat_args(mode, importance is not None, alpha, min_weight, None)
+        z = splat_importance(importance, self.n_px)
+        _, valid, weight, _ = splat_launch(None, 'float32', 'hwc', 1, 0, self.shape, self.vecs, self.mask, True, code, alpha,
+                                           min_weight, frac_bits, z=z, want_weight=True)
+        return weight, valid
+
+    def project(self, mode='average', importance=None, alpha=1.0, min_weight=None):
+        """This 's'-reference field carried to the other frame: the 't'-reference DeviceFlow whose vector at a pixel is the
+        splat (K20; `mode` 'average' or 'softmax' with `importance`) of the vectors of the source pixels that land there --
+        the vector buffer is read as an (H, W, 2) float32 tensor, without a copy -- and whose mask is `valid`; fill() closes
+        the holes.  Unlike switch_ref, which interpolates exactly over the Delaunay triangulation of the displaced grid (K3)
+        and so fills every triangle, this averages what arrives: it is a few streaming launches, it leaves holes where
+        nothing lands, and where the field folds it blends the colliding vectors (or, with softmax, prefers the important
+        ones) instead of choosing a triangle.  Nothing synchronises."""
+        self._splat_field("project")
+        if mode == 'sum':
+            raise ValueError("Error splatting: project takes mode 'average' or 'softmax': a sum of vectors is not a flow")
+        code, alpha, min_weight, frac_bits = splat_args(mode, importance is not None, alpha, min_weight, None)
+        z = splat_importance(importance, self.n_px)
+        dst, valid, _, _ = splat_launch(self.vecs, 'float32', 'hwc', 1, 2, self.shape, self.vecs, self.mask, True, code, alpha,
+                                        min_weight, frac_bits, z=z)
+        return DeviceFlow(dst, valid, self.shape, 't')
+
     # -- warping
     def apply(self, target, consider_mask=True, quant=nat.QUANT_OPENCV, target_mask=None):
         """Flow.apply with a Flow target (flow_class.py:600-603, 632-684): the target's vectors and mask
@@ -794,11 +870,11 @@ class DeviceFlow:
         propagate validity: every channel is Flow.apply of that plane (flow_class.py:604-695, without padding) from ONE set
         of taps per pixel, one launch of K12; 16-bit tensors are blended in float32 and rounded once.  This one field warps
         every item of a batched tensor.  -> (DeviceTensor, valid-area DeviceBuffer [H][W]).  `target_mask`: uint8
-        DeviceBuffer [H][W] or None (all valid).  Reference 't' only: 's'-reference (scatter) warps of tensors are not
-        supported."""
+        DeviceBuffer [H][W] or None (all valid).  Reference 't' only: an 's'-reference field pushes a tensor forward with
+        splat (K20)."""
         if self.ref != 't':
-            raise ValueError("apply_tensor warps with 't'-reference fields only: 's'-reference (scatter) warps of tensors are "
-                             "not supported")
+            raise ValueError("apply_tensor warps with 't'-reference fields only: an 's'-reference field warps a tensor forward "
+                             "with splat")
         n, c, h, w, _ = tensor_args(tensor.shape, tensor.layout, tensor.dtype, self.shape)
         if self.is_zero(thresholded=True, masked=False):        # identity short cut, utils.py:215-216
             valid = DeviceBuffer(self.n_px)

@@ -497,6 +497,55 @@ class Flow(object):
         vecs, mask = dev.upsample_host(self._vecs, self._mask, weights, factor)
         return Flow(vecs, self._ref, mask)
 
+    def _splat_host(self, what, array, layout, mode, importance, alpha, min_weight, frac_bits, want_weight, want_counters):
+        """the host half of splat / coverage / project: checks, then one upload, the launches of K20, one download"""
+        if self._ref != 's':
+            raise ValueError("Error splatting: {} pushes values forward along an 's'-reference flow; a 't'-reference flow "
+                             "warps backward, with apply".format(what))
+        code, alpha, min_weight, frac_bits = dev.splat_args(mode, importance is not None, alpha, min_weight, frac_bits)
+        z = dev.splat_importance_array(importance, self.shape)
+        n, c = 1, 0
+        if array is not None:
+            array, n, c, _ = dev.splat_host_array(array, layout, self.shape)
+        return dev.splat_host(array, layout, n, c, self._vecs, self._mask, code, alpha, min_weight, frac_bits, z,
+                              want_weight, want_counters)
+
+    def splat(self, array: np.ndarray, mode: str = 'average', importance: np.ndarray = None, alpha: float = 1.0,
+              min_weight: float = None, frac_bits: int = None, layout: str = 'chw', return_weight: bool = None,
+              return_counters: bool = None) -> Tuple[np.ndarray, ...]:
+        """Forward-warp `array`, a float32 or float16 array (C, H, W) or (N, C, H, W) -- with layout='hwc' (H, W, C) or
+        (N, H, W, C) -- by splatting along this 's'-reference flow: every source pixel adds its channels to the four pixels
+        around where the flow sends it, with bilinear weights.  mode 'sum', 'average' or 'softmax' (which needs
+        `importance`, a float (H, W) array, and weights source pixel p by exp(alpha * importance[p])).  -> (array of the
+        input's shape and dtype, valid bool (H, W)), plus the float32 (H, W) summed weight with `return_weight` and
+        (skipped source pixels, dropped values) with `return_counters`.  The definition, with its fixed-point sums, is
+        DeviceFlow.splat's; this is not the reference's 's' apply.  One upload, two or three launches, one download."""
+        return_weight = dev.optional_bool(return_weight, False, "Error splatting: Return_weight needs to be a boolean")
+        return_counters = dev.optional_bool(return_counters, False, "Error splatting: Return_counters needs to be a boolean")
+        if array is None:
+            raise TypeError("Error splatting: the tensor needs to be a numpy array, got NoneType")
+        out, valid, weight, counters = self._splat_host("splat", array, layout, mode, importance, alpha, min_weight, frac_bits,
+                                                        return_weight, return_counters)
+        return (out, valid) + ((weight,) if return_weight else ()) + ((counters,) if return_counters else ())
+
+    def coverage(self, importance: np.ndarray = None, alpha: float = 1.0, min_weight: float = None) -> Tuple[np.ndarray, np.ndarray]:
+        """The range map of this 's'-reference flow: (weight float32 (H, W), valid bool (H, W)) -- how much bilinear weight
+        lands on every pixel, and where that reaches `min_weight` (None: 2^-10).  With `importance` the weights are those
+        of softmax splatting.  The definition is DeviceFlow.coverage's."""
+        _, valid, weight, _ = self._splat_host("coverage", None, 'hwc', 'average' if importance is None else 'softmax', importance,
+                                               alpha, min_weight, None, True, False)
+        return weight, valid
+
+    def project(self, mode: str = 'average', importance: np.ndarray = None, alpha: float = 1.0, min_weight: float = None) -> FlowAlias:
+        """This 's'-reference flow carried to the other frame by splatting its own vectors: a 't'-reference Flow whose mask
+        is set where enough weight arrived; fill() closes the holes.  Cheaper than switch_ref and not the same function: see
+        DeviceFlow.project."""
+        if mode == 'sum':
+            raise ValueError("Error splatting: project takes mode 'average' or 'softmax': a sum of vectors is not a flow")
+        vecs = np.ascontiguousarray(self._vecs, np.float32)
+        out, valid, _, _ = self._splat_host("project", vecs, 'hwc', mode, importance, alpha, min_weight, None, False, False)
+        return Flow(out, 't', valid)
+
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
         """flow_1 (+) flow_2 = flow_3: mode k returns flow_k from the other two (`self` comes first in
         that formula among the two given).  Reference flow_class.py:1247-1424."""

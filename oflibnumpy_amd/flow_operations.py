@@ -11,7 +11,7 @@ from .flow_class import Flow
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
            'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow',
-           'upsample_flow_convex', 'correlation_lookup', 'global_match']
+           'upsample_flow_convex', 'correlation_lookup', 'global_match', 'splat_flow']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -148,3 +148,13 @@ def global_match(fmap1: nd, fmap2: nd, ref: str = 's', scale: float = None, min_
     flow = Flow(vecs[0], ref, mask[0])
     extra = tuple(x[0] for x, wanted in ((conf, want[0]), (index, want[1])) if wanted)
     return (flow,) + extra if extra else flow
+
+
+def splat_flow(flow: nd, target: nd, mask: nd = None, mode: str = 'average', importance: nd = None, alpha: float = 1.0,
+               min_weight: float = None, frac_bits: int = None, layout: str = 'chw') -> tuple:
+    """(array, valid) of `target`, a float32 or float16 array (C, H, W) or (N, C, H, W) -- with layout='hwc' (H, W, C) or
+    (N, H, W, C) --, forward-warped by splatting along the 's'-reference flow array `flow` (H, W, 2) with the mask `mask`
+    (None: all valid) -- Flow.splat: mode 'sum', 'average' or 'softmax' with the float (H, W) array `importance`.  Not the
+    reference's 's' apply."""
+    return Flow(flow, 's', mask).splat(target, mode=mode, importance=importance, alpha=alpha, min_weight=min_weight,
+                                       frac_bits=frac_bits, layout=layout)

@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup and K19 global matching.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching and K20 splatting.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -542,3 +542,43 @@ def match_host(f1, f2, scale, sign, min_conf, want_conf=False, want_index=False)
     nat.check(_lib().ofl_global_match(f1.ctypes.data, f2.ctypes.data, _TENSOR_EL[f1.dtype.name], n, c, h, w, scale, sign, min_conf,
                                       vecs.ctypes.data, mask.ctypes.data, _host_ptr(conf), _host_ptr(index)))
     return vecs, mask.view(np.bool_), conf, index
+
+
+# ------------------------------------------------------------------------------ K20: forward warp by splatting
+def splat_launch(src, dtype, layout, n, c, shape, flow, fmask, flow_shared, mode, alpha, min_weight, frac_bits, z=None,
+                 want_valid=True, want_weight=False, want_counters=False, stream=None):
+    """K20 (ofl_splat_dev) on `n` items of `c` channels in `layout` ('chw' / 'hwc') of `dtype`; asynchronous: [the max pass,]
+    accumulate, finish.  src None with c = 0: only the weight plane is accumulated.  mode, alpha, min_weight, frac_bits: from
+    args.splat_args; z: the float32 importance buffer or None.  The workspace comes from the buffer pool and goes back to it
+    on return (one stream).  -> (dst or None, valid or None, weight or None, counters or None): valid uint8 and weight
+    float32 are ONE [H][W] plane when the field is shared, else [n][H][W]; counters the zeroed-then-added uint32[2], all
+    still in HBM."""
+    lib, (h, w) = _lib(), shape
+    shared = 1 if flow_shared else 0
+    planes = h * w * (1 if flow_shared else n)
+    nbytes = _size_query(lib.ofl_splat_workspace_bytes, n, c, h, w, shared, mode)
+    work = DeviceBuffer(nbytes)
+    dst = DeviceBuffer(n * c * h * w * _tensor_bytes(dtype)) if c else None
+    valid = DeviceBuffer(planes) if want_valid else None
+    weight = DeviceBuffer(planes * 4) if want_weight else None
+    counters = DeviceBuffer.zeros(8, stream) if want_counters else None
+    nat.check(lib.ofl_splat_dev(_ptr(src), _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, h, w, flow.ptr, fmask.ptr, shared,
+                                _ptr(z), alpha, mode, frac_bits, min_weight, work.ptr, nbytes, _ptr(dst), _ptr(valid),
+                                _ptr(weight), _ptr(counters), stream))
+    return dst, valid, weight, counters
+
+
+def splat_host(src, layout, n, c, vecs, mask, mode, alpha, min_weight, frac_bits, z=None, want_weight=False, want_counters=False):
+    """K20 for host arrays through ofl_splat (upload, launches, download): src a contiguous float32 or float16 array in the
+    memory order of `layout` (None with c = 0), ONE field (vecs (H, W, 2), mask) for all `n` items, z float32 (H, W) or None
+    -> (dst or None, valid bool (H, W), weight float32 (H, W) or None, counters (skipped, dropped) or None)."""
+    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(mask)
+    h, w = vecs.shape[:2]
+    dst = None if src is None else np.empty_like(src)
+    valid = np.empty((h, w), np.uint8)
+    weight = np.empty((h, w), np.float32) if want_weight else None
+    counters = np.zeros(2, np.uint32) if want_counters else None
+    nat.check(_lib().ofl_splat(_host_ptr(src), _TENSOR_EL['float32' if src is None else src.dtype.name], _TENSOR_LAYOUT[layout],
+                               n, c, h, w, vecs.ctypes.data, m.ctypes.data, 1, _host_ptr(z), alpha, mode, frac_bits, min_weight,
+                               _host_ptr(dst), valid.ctypes.data, _host_ptr(weight), _host_ptr(counters)))
+    return dst, valid.view(np.bool_), weight, None if counters is None else (int(counters[0]), int(counters[1]))
