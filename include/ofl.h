@@ -159,6 +159,9 @@ int         ofl_png_unfilter(const uint8_t *raw, size_t raw_bytes, int height, i
  *         non-zero / at or above the 1e-3 threshold, i.e. fa is certainly not (thresholded-)zero.  A clear
  *         word means "not observed": the caller confirms with ofl_flow_stats_dev before taking one of the
  *         reference's early exits (flow_class.py:1339-1354).  stats[b][2..3] are not written.
+ *     In every word a NaN component counts as non-zero AND as at or above the threshold, as the reference's comparisons
+ *     have it (`v != 0`, `!(v < th && v > -th)`, utils.py:310-315, 527-544); +-Inf does too, -0.0 is zero, a subnormal is
+ *     non-zero.  The words equal the OFL_STAT_* bits of ofl_flow_stats_dev on every input, finite or not.
  * The host entry returns exact OFL_STAT_* bit masks: stats_host[2*b] for fa, stats_host[2*b+1] for fb.
  * out / mout must not alias the inputs.
  */

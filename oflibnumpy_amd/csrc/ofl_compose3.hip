@@ -195,9 +195,26 @@ struct C3Stream {          // one lane's share of a tile row of the streamed fie
     uint32_t m[2];
 };
 
-struct C3Stat {            // running maxima for the zero-flow predicates of one field pair
-    float amax_m, bmax, bmax_m;
+// Running maxima for the zero-flow predicates of one field pair, kept as the BIT PATTERNS of |u|, |v|: non-negative floats
+// order like their bits, and every NaN pattern orders above Inf, so that a NaN component counts as non-zero and as >= th
+// exactly as stat_bits' `v != 0` and `!(v < th && v > -th)` have it (a float maximum would drop it: fmaxf(x, NaN) == x).
+struct C3Stat {
+    uint32_t amax_m, bmax, bmax_m;
 };
+
+__device__ __forceinline__ uint32_t c3_abs_bits(float u, float v)
+{
+    return max(__float_as_uint(u) & 0x7fffffffu, __float_as_uint(v) & 0x7fffffffu);
+}
+
+// the six predicates of a lane's maxima: fa masked, fb masked, fb anywhere; each non-zero / >= th (th > 0, as bits)
+__device__ __forceinline__ void c3_stat_predicates(const C3Stat &st, float th, bool (&c)[6])
+{
+    const uint32_t tb = __float_as_uint(th);
+    c[0] = st.amax_m != 0u; c[1] = st.amax_m >= tb;
+    c[2] = st.bmax_m != 0u; c[3] = st.bmax_m >= tb;
+    c[4] = st.bmax != 0u;   c[5] = st.bmax >= tb;
+}
 
 template <bool BITS = false>
 __device__ __forceinline__ C3Stream c3_load_stream(const C3Args &a, const C3Field &F, int y, const int (&xg)[2])
@@ -251,8 +268,8 @@ __device__ __forceinline__ uint32_t c3_clear_flags(uint32_t seen) { return (uint
 
 __device__ __forceinline__ void c3_flush_stats(const C3Args &a, int b, const C3Stat &st, uint32_t clear)
 {
-    const bool c[6] = { st.amax_m > 0.0f, st.amax_m >= a.th, st.bmax_m > 0.0f, st.bmax_m >= a.th,
-                        st.bmax > 0.0f, st.bmax >= a.th };
+    bool c[6];
+    c3_stat_predicates(st, a.th, c);
     uint32_t need = 0;                        // wave-uniform: bit k = some lane saw predicate k
 #pragma unroll
     for (int k = 0; k < 6; ++k) need |= (__ballot(c[k]) != 0ull) ? 1u << k : 0u;
@@ -267,8 +284,8 @@ __device__ __forceinline__ void c3_flush_stats(const C3Args &a, int b, const C3S
 // register allocator spills two of them in the interior gather, with or without the early read (HISTORY round 6).
 __device__ __forceinline__ void c3_flush_stats_late(const C3Args &a, int b, const C3Stat &st)
 {
-    const bool c[6] = { st.amax_m > 0.0f, st.amax_m >= a.th, st.bmax_m > 0.0f, st.bmax_m >= a.th,
-                        st.bmax > 0.0f, st.bmax >= a.th };
+    bool c[6];
+    c3_stat_predicates(st, a.th, c);
     const int  slot[6] = { 0, 1, 4, 5, 6, 7 };
     uint32_t need = 0;
 #pragma unroll
@@ -310,9 +327,9 @@ __device__ __forceinline__ void c3_finish(const C3Args &a, const C3Field &F, int
                 const v4f t = { o4.x, o4.y, o4.z, o4.w };
                 __builtin_nontemporal_store(t, c3_elem(reinterpret_cast<v4f *>(F.out), (row + xg[g]) >> 1));
                 if (STATS) {
-                    const float a0 = fmaxf(fabsf(bu[j]), fabsf(bv[j])), a1 = fmaxf(fabsf(bu[j + 1]), fabsf(bv[j + 1]));
-                    st.bmax   = fmaxf(st.bmax, fmaxf(a0, a1));
-                    st.bmax_m = fmaxf(st.bmax_m, fmaxf(bm[j] ? a0 : 0.0f, bm[j + 1] ? a1 : 0.0f));
+                    const uint32_t a0 = c3_abs_bits(bu[j], bv[j]), a1 = c3_abs_bits(bu[j + 1], bv[j + 1]);
+                    st.bmax   = max(st.bmax, max(a0, a1));
+                    st.bmax_m = max(st.bmax_m, max(bm[j] ? a0 : 0u, bm[j + 1] ? a1 : 0u));
                 }
             }
             // (lane 0 / 16 of a row: its pair starts the word, so its own `act` says whether the word exists -- x < W, y < H)
@@ -343,9 +360,9 @@ __device__ __forceinline__ void c3_finish(const C3Args &a, const C3Field &F, int
                 __builtin_nontemporal_store((uint16_t)mine, c3_elem(reinterpret_cast<uint16_t *>(F.mout), o >> 1));
             }
             if (STATS) {
-                const float a0 = fmaxf(fabsf(bu[j]), fabsf(bv[j])), a1 = fmaxf(fabsf(bu[j + 1]), fabsf(bv[j + 1]));
-                st.bmax   = fmaxf(st.bmax, fmaxf(a0, a1));
-                st.bmax_m = fmaxf(st.bmax_m, fmaxf(bm[j] ? a0 : 0.0f, bm[j + 1] ? a1 : 0.0f));
+                const uint32_t a0 = c3_abs_bits(bu[j], bv[j]), a1 = c3_abs_bits(bu[j + 1], bv[j + 1]);
+                st.bmax   = max(st.bmax, max(a0, a1));
+                st.bmax_m = max(st.bmax_m, max(bm[j] ? a0 : 0u, bm[j + 1] ? a1 : 0u));
             }
         }
     }
@@ -387,7 +404,7 @@ __device__ __forceinline__ void c3_border_px(const C3Args &a, const C3Field &F, 
     const C3Tap w = c3_weights<QUANT>(p);
     v = make_float2(c3_blend(u00, u01, u10, u11, w), c3_blend(v00, v01, v10, v11, w));
     k = c3_valid<QUANT>(a00 != 0.0f, a01 != 0.0f, a10 != 0.0f, a11 != 0.0f, w) ? 1 : 0;
-    if (STATS) st.amax_m = fmaxf(st.amax_m, (a00 != 0.0f && act) ? fmaxf(fabsf(u00), fabsf(v00)) : 0.0f);
+    if (STATS) st.amax_m = max(st.amax_m, (a00 != 0.0f && act) ? c3_abs_bits(u00, v00) : 0u);
 }
 
 // interior and outside tests of one pixel's taps, accumulated over a lane's pixels
@@ -469,7 +486,7 @@ __device__ __forceinline__ void c3_border_pair(const C3Args &a, const C3Field &F
         su[i] = c3_blend(u00, u01, u10, u11, w);
         sv[i] = c3_blend(v00, v01, v10, v11, w);
         ok |= c3_valid<QUANT>(a00 != 0.0f, a01 != 0.0f, a10 != 0.0f, a11 != 0.0f, w) ? 1u << (8 * i) : 0u;
-        if (STATS) st.amax_m = fmaxf(st.amax_m, (a00 != 0.0f && act) ? fmaxf(fabsf(u00), fabsf(v00)) : 0.0f);
+        if (STATS) st.amax_m = max(st.amax_m, (a00 != 0.0f && act) ? c3_abs_bits(u00, v00) : 0u);
     }
     *reinterpret_cast<float4 *>(v) = make_float4(su[0], sv[0], su[1], sv[1]);
     *reinterpret_cast<uint16_t *>(k) = (uint16_t)ok;
@@ -585,7 +602,7 @@ __device__ __forceinline__ void c3_tile(const C3Args &a, const C3Field &F, int y
             const bool m00 = (m0[j] & (BITS ? 1u : 0xffu)) != 0, m01 = (m0[j] & (BITS ? 2u : 0xff00u)) != 0;
             const bool m10 = (m1[j] & (BITS ? 1u : 0xffu)) != 0, m11 = (m1[j] & (BITS ? 2u : 0xff00u)) != 0;
             ok[j] = c3_valid<QUANT>(m00, m01, m10, m11, w);
-            if (STATS) st.amax_m = fmaxf(st.amax_m, (m00 && act[j >> 1]) ? fmaxf(fabsf(p0[j].lo_u), fabsf(p0[j].lo_v)) : 0.0f);
+            if (STATS) st.amax_m = max(st.amax_m, (m00 && act[j >> 1]) ? c3_abs_bits(p0[j].lo_u, p0[j].lo_v) : 0u);
         }
         const float4 b01 = *reinterpret_cast<const float4 *>(v), b23 = *reinterpret_cast<const float4 *>(v + 64);
         bu[0] = b01.x; bu[1] = b01.z; bu[2] = b23.x; bu[3] = b23.z;
@@ -676,7 +693,7 @@ __device__ __forceinline__ void c3_sample_block(const C3Args &a, const C3Field &
             const bool m10 = (m1[j] & (BITS ? 1u : 0xffu)) != 0, m11 = (m1[j] & (BITS ? 2u : 0xff00u)) != 0;
             k[8 * j] = c3_valid<QUANT>(m00, m01, m10, m11, w) ? 1 : 0;
             const bool act = gy < H && gx0 + 8 * j < W;
-            if (STATS) st.amax_m = fmaxf(st.amax_m, (m00 && act) ? fmaxf(fabsf(p0[j].lo_u), fabsf(p0[j].lo_v)) : 0.0f);
+            if (STATS) st.amax_m = max(st.amax_m, (m00 && act) ? c3_abs_bits(p0[j].lo_u, p0[j].lo_v) : 0u);
         }
         return;
     }
@@ -706,7 +723,7 @@ void compose3_xpose_kernel(const C3Args a)
     const int xg[2] = { tx * kC3TileW + 2 * lx, tx * kC3TileW + 2 * lx + 2 * kC3LanesX };
     const bool act[2] = { y < H && xg[0] < W, y < H && xg[1] < W };
     const C3Field F = c3_field<BITS>(a, b);
-    C3Stat st = { 0.0f, 0.0f, 0.0f };
+    C3Stat st = { 0u, 0u, 0u };
     const C3Stream in = c3_load_stream<BITS>(a, F, y, xg);
     constexpr bool early = STATS && (BITS || QUANT != OFL_QUANT_EXACT);      // (c3_flush_stats_late: the one instantiation without)
     const uint32_t seen = early ? c3_load_flags(a, b) : 1u;      // the field's flag row, in flight with the stream (c3_flush_stats)

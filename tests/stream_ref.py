@@ -51,9 +51,10 @@ def stats_word(vecs, mask, th=TH):
     word = ((NONZERO_MASKED if (nz & m).any() else 0) | (NONZERO_TH_MASKED if (nzt & m).any() else 0) |
             (NONZERO if nz.any() else 0) | (NONZERO_TH if nzt.any() else 0) | (0 if finite else NONFINITE) |
             (MASK_HAS_ZERO if mask is not None and not m.all() else 0))
-    if finite and n and th == TH:
+    if n and th == TH:
         # the four zero-flow bits are the oracle's predicates: is_zero_flow (utils.py:527-544) over all vectors and,
-        # as Flow.is_zero does (flow_class.py:1244), over vecs[mask]; is_zero_raw is the C form of the same
+        # as Flow.is_zero does (flow_class.py:1244), over vecs[mask]; is_zero_raw is the C form of the same -- on non-finite
+        # input too: a NaN component is non-zero and >= threshold in all three
         for thresholded, bit_all, bit_masked in ((False, NONZERO, NONZERO_MASKED), (True, NONZERO_TH, NONZERO_TH_MASKED)):
             assert bool(word & bit_all) == (not O.is_zero_flow(v[None], thresholded)) == (not O.is_zero_raw(v[None], None, thresholded))
             assert (bool(word & bit_masked) == (not O.is_zero_flow(v[m][None], thresholded))
