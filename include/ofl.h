@@ -1075,6 +1075,62 @@ int ofl_splat(const void *src, int elem, int layout, int N, int C, int H, int W,
               const float *flow, const uint8_t *fmask, int flow_shared, const float *z, float alpha,
               int mode, int frac_bits, float min_weight, void *dst, uint8_t *valid, float *weight, uint32_t *counters_host);
 
+/* ------------------------------------------------------------------ K21: photometric error of a warp
+ * The third check of a field, after a ground truth (K14) and a backward twin (K13): take a pixel of the field's own frame,
+ * find where the field sends it in the other frame, and ask whether it looks the same there -- the brightness- or
+ * feature-constancy error that unsupervised flow, candidate selection and occlusion reasoning are built on, and, negated
+ * and scaled, the importance metric of softmax splatting (K20; Niklaus & Liu: -alpha |I0 - backwarp(I1, F0->1)|).  The
+ * tensor analogue of K13: K12's taps and blend, but the C warped channels are reduced to ONE float per pixel and never stored.
+ *     near   the tensor of the field's own frame, far the tensor of the other frame: N items of C channels, both of ONE
+ *            element type (OFL_EL_F32, OFL_EL_F16, OFL_EL_BF16) and ONE layout ((N, C, H, W) or (N, H, W, C), K12's)
+ *     flow   [H][W][2] float32 with fmask [H][W]; near_mask, far_mask [H][W] or NULL (all valid).  flow_shared != 0: ONE
+ *            field and one of each mask serve all N items; otherwise N of each lie back to back
+ *     sign   +1 for an 's' field, -1 for a 't' field, as in K13;  N and C in [1, 65535], H and W in [1, 32766]
+ * Per item n and pixel (x, y), every operation float32 and rounded once (no FMA); 16-bit elements are widened exactly:
+ *     tap      = the bilinear tap of (x, y) + sign * flow[y][x]     (map_coord / make_tap, `quant` as in K1 / K12 / K13;
+ *                                                                    a non-finite vector samples what it samples there)
+ *     w_c      = far[n, c]'s four taps blended (0 outside the frame)                == K12's value BEFORE its rounding to storage
+ *     am       = far_mask's four taps blended as 0.0f / 1.0f (NULL: 1 inside the frame, 0 outside)
+ *     covered  = fmask & near_mask (NULL: 1) & (am == 1.0f)                         == K12's valid, ANDed with near_mask
+ *     d_c      = near[n, c] - w_c
+ *     t_c      = |d_c| (OFL_PHOTO_L1)  |  d_c * d_c (OFL_PHOTO_L2)  |  sqrtf(d_c * d_c + eps * eps) (OFL_PHOTO_CHARBONNIER)
+ *     S        = the sum of the t_c in the fixed order below
+ *     e        = S * inv_c,  inv_c = (float)(1.0 / (double)C);  OFL_PHOTO_L2: e = sqrtf(e), the root mean square
+ *     err      = covered ? e : 0.0f                                                 (sqrtf: the correctly rounded one, as in K13)
+ *     within   = covered & (e <= tau)                                               (a NaN error is never within)
+ * The order of the sum depends on C alone -- not on layout or element type, so a planar and a channels-last tensor of the
+ * same values give the same bytes.  It is K18's scheme: the groups of 4 consecutive channels g = c / 4 are dealt to 16
+ * partial sums, p_j = the t_c with (c / 4) % 16 == j, added in ascending c to +0.0f; then p_j += p_(j + 8) for j < 8,
+ * p_j += p_(j + 4) for j < 4, p_j += p_(j + 2) for j < 2, and S = p_0 + p_1.  Every t_c is >= +0 or NaN, so a partial sum
+ * without channels is +0.0f and adding it changes nothing.  tests/photometric_ref.py restates all of this in NumPy.
+ * This is not a function of the reference and the formula is its definition: there is NO zero-flow short cut in either
+ * `quant` mode, as in K13.
+ *     err float32, covered and within uint8: [N][H][W].  One of err / within is required, covered is optional; within is
+ *     computed when it is given, and tau must then be finite and >= 0.  eps (finite, >= 0) is used by CHARBONNIER only.
+ *     counts  device uint32[N][2] = {covered, within} pixels per item, or NULL: ADDED to, the caller zeroes it; each
+ *             workgroup issues at most one integer atomic add per counter.  No other atomics, no workspace.
+ * near / far aligned to their element, flow 8-byte, err and counts 4-byte, masks at any address; element offsets are
+ * 64-bit.  Outputs must not alias inputs.  A bad argument -- a NULL near / far / flow / fmask, another elem, layout, metric
+ * or quant, sizes out of range, sign not +-1, eps or tau negative or not finite, neither err nor within, a misaligned
+ * pointer -- returns OFL_E_INVALID with a message before any launch.  The _dev entry is asynchronous, one launch; the host
+ * entry takes host pointers (counts_host: host uint32[N][2] or NULL), uploads, launches, downloads and synchronises.
+ * Bytes per pixel: reads 2 C elements (near streamed, far gathered) + 8 (flow) + 1 to 3 (masks); writes 4 + 1 + 1, where
+ * K12 plus an elementwise pass writes and re-reads C elements more.
+ * Not built: metrics over a window (census, SSIM, gradient constancy: a second pass), a reduction of the map to a mean or
+ * percentiles, a backward pass, mixed element types or layouts, integer tensors on the device, padding offsets.
+ */
+enum { OFL_PHOTO_L1 = 0, OFL_PHOTO_L2 = 1, OFL_PHOTO_CHARBONNIER = 2 };
+int ofl_photometric_dev(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                        const float *flow, const uint8_t *fmask, int flow_shared, int sign,
+                        const uint8_t *near_mask, const uint8_t *far_mask,
+                        int metric, float eps, float tau,
+                        float *err, uint8_t *covered, uint8_t *within, uint32_t *counts, int quant, void *stream);
+int ofl_photometric(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                    const float *flow, const uint8_t *fmask, int flow_shared, int sign,
+                    const uint8_t *near_mask, const uint8_t *far_mask,
+                    int metric, float eps, float tau,
+                    float *err, uint8_t *covered, uint8_t *within, uint32_t *counts_host, int quant);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

@@ -28,6 +28,7 @@ CORR_XY, CORR_YX = 0, 1
 CORR_V, CORR_L = 4, 16
 MATCH_TILE, MATCH_WAVES = 32, 4
 SPLAT_SUM, SPLAT_AVERAGE, SPLAT_SOFTMAX = 0, 1, 2
+PHOTO_L1, PHOTO_L2, PHOTO_CHARBONNIER = 0, 1, 2
 
 
 class MeshCert(ctypes.Structure):
@@ -164,6 +165,10 @@ SIGNATURES = {
     "ofl_splat_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _cf, _ci, _ci, _cf, _vp, _cs,
                             _vp, _vp, _vp, _vp, _vp]),
     "ofl_splat": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _cf, _ci, _ci, _cf, _vp, _vp, _vp, _vp]),
+    "ofl_photometric_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _cf, _cf,
+                                  _vp, _vp, _vp, _vp, _ci, _vp]),
+    "ofl_photometric": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _cf, _cf,
+                              _vp, _vp, _vp, _vp, _ci]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

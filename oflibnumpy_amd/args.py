@@ -271,6 +271,59 @@ def consistency_args(alpha=None, beta=None):
     return out[0], out[1]
 
 
+# -- photometric error of a warp (K21)
+PHOTO_METRICS = {'l1': nat.PHOTO_L1, 'l2': nat.PHOTO_L2, 'charbonnier': nat.PHOTO_CHARBONNIER}
+PHOTO_EPS = 1e-3                  # the Charbonnier constant when none is given
+
+
+def photometric_args(metric='l1', eps=None, threshold=None):
+    """Validation of the settings of a photometric error (K21) on the host before any device work -> (metric code, eps,
+    threshold): eps as float32, threshold as float32 or None.  metric: 'l1' (mean absolute difference over the channels),
+    'l2' (root mean square) or 'charbonnier' (mean of sqrt(d^2 + eps^2)); eps: None for 1e-3, used by 'charbonnier' only;
+    threshold: None for no `within` output, else the bound err <= threshold.  A bool or a value of the wrong type is a
+    TypeError, an unknown metric or a negative or non-finite value (as given, or once rounded to float32) a ValueError."""
+    prefix = "Error computing photometric error: "
+    if not isinstance(metric, str):
+        raise TypeError("{}metric must be a string, got {}".format(prefix, type(metric).__name__))
+    if metric not in PHOTO_METRICS:
+        raise ValueError("{}metric must be 'l1', 'l2' or 'charbonnier', got {!r}".format(prefix, metric))
+    out = []
+    for name, value in (("eps", PHOTO_EPS if eps is None else eps), ("threshold", threshold)):
+        if value is None:
+            out.append(None)
+            continue
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise TypeError("{}{} must be a number or None, got {}".format(prefix, name, type(value).__name__))
+        with np.errstate(over='ignore'):
+            v32 = np.float32(float(value)) if abs(value) < 1e300 else np.float32(np.inf if value > 0 else -np.inf)
+        if value != value or value < 0 or not np.isfinite(v32):
+            raise ValueError("{}{} must be finite and not negative, got {}".format(prefix, name, value))
+        out.append(v32)
+    return PHOTO_METRICS[metric], out[0], out[1]
+
+
+def photometric_host_array(a, layout, name):
+    """A tensor given to Flow.photometric / photometric_error -> (contiguous array in memory order, layout): a NumPy array
+    of float32 or float16, or of uint8 (an image: converted to float32, which is exact), of shape (H, W) -- one channel --,
+    (H, W, C) with layout 'hwc' or (C, H, W) with layout 'chw'; a leading item axis makes (N, H, W, C) / (N, C, H, W).
+    TypeError for another type or dtype, ValueError for another rank or layout."""
+    prefix = "Error computing photometric error: "
+    if not isinstance(a, np.ndarray):
+        raise TypeError("{}{} needs to be a numpy array, got {}".format(prefix, name, type(a).__name__))
+    if layout not in _TENSOR_LAYOUT:
+        raise ValueError("{}layout must be 'chw' or 'hwc', got {!r}".format(prefix, layout))
+    if a.dtype == np.uint8:
+        a = a.astype(np.float32)
+    if a.dtype != np.float32 and a.dtype != np.float16:
+        raise TypeError("{}{} needs to have dtype float32, float16 or uint8, got {}".format(prefix, name, a.dtype))
+    if a.ndim == 2:
+        a = a[None] if layout == 'chw' else a[..., None]
+    if a.ndim not in (3, 4):
+        raise ValueError("{}{} needs to have shape (H, W), {}, got {}".format(
+            prefix, name, "(C, H, W) or (N, C, H, W)" if layout == 'chw' else "(H, W, C) or (N, H, W, C)", a.shape))
+    return np.ascontiguousarray(a)
+
+
 # -- an estimate against a ground truth (K14)
 ERROR_THRESHOLDS, ERROR_OUTLIER, ERROR_SPEED_EDGES = (1, 3, 5), (3, 0.05), (10, 40)     # px; KITTI's Fl rule; Sintel's speed bins
 

@@ -142,6 +142,25 @@ class DeviceFlowBatch:
         res = (consistent, covered) + ((residual,) if return_residual else ())
         return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
 
+    def photometric(self, near, far, metric='l1', eps=None, threshold=None, near_mask=None, far_mask=None, return_counts=False,
+                    quant=nat.QUANT_OPENCV):
+        """self[i].photometric(item i of `near`, item i of `far`, ...) for every i in ONE launch of K21
+        (DeviceFlow.photometric): near, far DeviceTensors (n, C, H, W) of one layout and dtype, near_mask, far_mask uint8
+        DeviceBuffers [n][H][W] (per item) or None.  -> (error float32, covered uint8) as DeviceBuffers [n][H][W];
+        `threshold` appends within (uint8), return_counts an (n, 2) uint32 array of (covered, within) pixels per item -- the
+        only option that synchronises.  A packed batch is read through its byte masks."""
+        prefix = "Error computing photometric error: "
+        code, eps, threshold = dev.photometric_args(metric, eps, threshold)
+        near, far = dev.photometric_tensors(near, far, self.shape, batch=self.n)
+        n_bytes = self.n * self.shape[0] * self.shape[1]
+        near_mask = dev.mask_buffer_arg(near_mask, n_bytes, prefix, "near_mask")
+        far_mask = dev.mask_buffer_arg(far_mask, n_bytes, prefix, "far_mask")
+        err, covered, within, counts = dev.photometric_launch(
+            near.buf, far.buf, near.dtype, near.layout, self.n, near.channels, self.shape, self.vecs, self.mask, False,
+            1 if self.ref == 's' else -1, code, eps, threshold, near_mask, far_mask, want_counts=bool(return_counts), quant=quant)
+        res = (err, covered) + ((within,) if within is not None else ())
+        return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
+
     def error(self, gt, thresholds=None, outlier=None, speed_edges=None, use_est_mask=True, return_map=False, return_outliers=False):
         """self[i].error(gt[i], ...) for every i in ONE launch of K14 (DeviceFlow.error): `gt` a batch of the same length,
         shape and reference.  -> a DeviceFlowError whose read() gives a list of n FlowErrorStats (the one read-back, 96 bytes

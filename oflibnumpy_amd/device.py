@@ -33,14 +33,15 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rul
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
                    consistency_args, error_args, fill_args, median_args, upsample_args, upsample_weights_array, corr_args,
                    corr_host_array, optional_bool, mask_array_arg, match_args, match_host_array, splat_args, splat_host_array,
-                   splat_importance_array)
+                   splat_importance_array, photometric_args, photometric_host_array)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
                       track_bilinear_launch, track_query_points, track_query_epilogue, gather_tensor, tensor_import_launch,
                       tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
                       FlowErrorStats, fill_launch, fill_host, median_launch, median_host, upsample_launch,
-                      upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host, match_launch, match_host, splat_launch, splat_host)
+                      upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host, match_launch, match_host, splat_launch, splat_host,
+                      photometric_launch, photometric_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -377,6 +378,35 @@ def splat_importance(buf, n_px):
     return buf
 
 
+def photometric_tensors(near, far, field_shape, batch=None):
+    """The `near` and `far` of DeviceFlow.photometric (batch None) or DeviceFlowBatch.photometric (batch n) -> two
+    DeviceTensors of one shape, layout and dtype with the height and width of the field.  A float32 DeviceImage [H][W][C] is
+    taken as the channels-last tensor it is, on the same buffer."""
+    prefix = "Error computing photometric error: "
+    pair = []
+    for name, t in (("near", near), ("far", far)):
+        if isinstance(t, DeviceImage):
+            if t.dtype != np.float32:
+                raise TypeError("{}{} as a DeviceImage needs to be float32, got {}".format(prefix, name, t.dtype))
+            t = DeviceTensor(t.buf, (t.shape[2], t.shape[0], t.shape[1]), 'float32', 'hwc')
+        if not isinstance(t, DeviceTensor):
+            raise TypeError("{}{} needs to be a DeviceTensor or a float32 DeviceImage, got {}".format(prefix, name, type(t).__name__))
+        pair.append(t)
+    near, far = pair
+    if near.shape != far.shape:
+        raise ValueError("{}the tensors need the same shape, got {} and {}".format(prefix, near.shape, far.shape))
+    if near.dtype != far.dtype:
+        raise TypeError("{}the tensors need the same dtype, got {} and {}".format(prefix, near.dtype, far.dtype))
+    if near.layout != far.layout:
+        raise ValueError("{}the tensors need the same layout, got '{}' and '{}'".format(prefix, near.layout, far.layout))
+    if (near.h, near.w) != tuple(field_shape):
+        raise ValueError("{}tensors and flow need the same height and width, got {} and {}"
+                         .format(prefix, (near.h, near.w), tuple(field_shape)))
+    if batch is not None and (not near.batched or near.n != batch):
+        raise ValueError("{}a batch of {} fields takes tensors of shape ({}, C, H, W), got {}".format(prefix, batch, batch, near.shape))
+    return near, far
+
+
 def upsample_weights(weights, factor, shape, batch=None):
     """The `weights` of DeviceFlow.upsample_convex (batch None: logical shape (9 f^2, h, w)) or
     DeviceFlowBatch.upsample_convex (batch n: (n, 9 f^2, h, w)) checked against the coarse field's `shape` -> factor."""
@@ -676,6 +706,38 @@ class DeviceFlow:
         if return_counts:
             n = counts.to_host((2,), np.uint32)
             res += ((int(n[0]), int(n[1])),)
+        return res
+
+    def photometric(self, near, far, metric='l1', eps=None, threshold=None, near_mask=None, far_mask=None, return_counts=False,
+                    quant=nat.QUANT_OPENCV):
+        """The photometric (brightness- or feature-constancy) error of this field in ONE launch of K21 (include/ofl.h):
+        `near`, the tensor of the field's own frame, against `far`, the tensor of the other frame, sampled where this field
+        points -- at x + self for 's', x - self for 't', the taps and blend of apply_tensor -- and reduced over the channels:
+            covered = self.mask & near_mask & [the interpolated far_mask == 1]      (apply_tensor's valid, ANDed with near_mask)
+            error   = mean_c |near_c - warped far_c| ('l1'), its root mean square ('l2') or mean_c sqrt(d_c^2 + eps^2)
+                      ('charbonnier'; eps None: 1e-3) where covered, else 0
+        in float32 with one rounding per operation and a summation order that depends on the channel count alone, so both
+        layouts give the same bytes.  near, far: DeviceTensors of one shape (C, H, W) or (N, C, H, W), one layout and one
+        dtype (float32 / float16 / bfloat16); a float32 DeviceImage is taken as an 'hwc' tensor without a copy.  near_mask,
+        far_mask: uint8 DeviceBuffers [H][W] or None.  This one field and these masks serve every item.  Not a function of
+        the reference and without a zero-flow short cut in either `quant` mode; works for 's' and 't' fields alike, where
+        apply_tensor takes 't' only.
+        -> (error, covered): a float32 and a uint8 DeviceBuffer [N][H][W]; `threshold` appends within = covered &
+        (error <= threshold) as uint8, return_counts appends [(n_covered, n_within)] * N as Python ints -- the only option
+        that synchronises.  `error` is what splat(mode='softmax', importance=error, alpha=-20.0) takes, without a copy.
+        Not built: window metrics (census, SSIM, gradient constancy), a mean or percentiles of the map, a backward pass,
+        mixed dtypes or layouts, integer tensors, padding offsets.  The inputs are not modified."""
+        prefix = "Error computing photometric error: "
+        code, eps, threshold = photometric_args(metric, eps, threshold)
+        near, far = photometric_tensors(near, far, self.shape)
+        near_mask = mask_buffer_arg(near_mask, self.n_px, prefix, "near_mask")
+        far_mask = mask_buffer_arg(far_mask, self.n_px, prefix, "far_mask")
+        err, covered, within, counts = photometric_launch(
+            near.buf, far.buf, near.dtype, near.layout, near.n, near.channels, self.shape, self.vecs, self.mask, True,
+            1 if self.ref == 's' else -1, code, eps, threshold, near_mask, far_mask, want_counts=bool(return_counts), quant=quant)
+        res = (err, covered) + ((within,) if within is not None else ())
+        if return_counts:
+            res += ([(int(a), int(b)) for a, b in counts.to_host((near.n, 2), np.uint32)],)
         return res
 
     def error(self, gt, thresholds=None, outlier=None, speed_edges=None, use_est_mask=True, return_map=False, return_outliers=False):

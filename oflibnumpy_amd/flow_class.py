@@ -431,6 +431,34 @@ class Flow(object):
         return dev.consistency_host(self._vecs, self._mask, backward._vecs, backward._mask, 1 if self._ref == 's' else -1,
                                     alpha, beta, return_residual)
 
+    def photometric(self, near: np.ndarray, far: np.ndarray, metric: str = 'l1', eps: float = None, threshold: float = None,
+                    near_mask: np.ndarray = None, far_mask: np.ndarray = None, layout: str = 'hwc',
+                    quant: int = 0) -> Tuple[np.ndarray, ...]:
+        """The photometric (brightness- or feature-constancy) error of this flow: `near`, the image or feature array of the
+        flow's own frame, against `far`, that of the other frame, sampled where the flow points and reduced over the
+        channels -- the mean absolute difference ('l1'), the root mean square ('l2') or the mean of sqrt(d^2 + eps^2)
+        ('charbonnier', eps None: 1e-3).  near, far: arrays of one shape and dtype, (H, W), (H, W, C) or -- layout='chw' --
+        (C, H, W), a leading item axis allowed; float32, float16, or uint8 images, which are converted to float32 (exact).
+        near_mask, far_mask: bool or uint8 (H, W) arrays or None.  -> (error float32, covered bool), each (H, W) -- or
+        (N, H, W) --, plus within = covered & (error <= threshold) as bool with `threshold`.  Works for 's' and 't' flows.
+        Not a function of the reference; the definition is DeviceFlow.photometric's.  One upload, one launch, one
+        download."""
+        prefix = "Error computing photometric error: "
+        code, eps, threshold = dev.photometric_args(metric, eps, threshold)
+        near, far = dev.photometric_host_array(near, layout, "near"), dev.photometric_host_array(far, layout, "far")
+        if near.shape != far.shape:
+            raise ValueError("{}the arrays need the same shape, got {} and {}".format(prefix, near.shape, far.shape))
+        if near.dtype != far.dtype:
+            raise TypeError("{}the arrays need the same dtype, got {} and {}".format(prefix, near.dtype, far.dtype))
+        n, c, h, w, batched = dev.tensor_args(dev.tensor_logical_shape(near.shape, layout), layout, near.dtype.name)
+        if (h, w) != tuple(self.shape):
+            raise ValueError("{}arrays and flow need the same height and width, got {} and {}".format(prefix, (h, w), tuple(self.shape)))
+        near_mask = None if near_mask is None else dev.mask_array_arg(near_mask, self.shape, prefix, "near_mask")
+        far_mask = None if far_mask is None else dev.mask_array_arg(far_mask, self.shape, prefix, "far_mask")
+        res = dev.photometric_host(near, far, layout, n, c, self._vecs, self._mask, 1 if self._ref == 's' else -1, code, eps,
+                                   threshold, near_mask, far_mask, quant)
+        return res if batched else tuple(r[0] for r in res)
+
     def error(self, gt: FlowAlias, thresholds=None, outlier=None, speed_edges=None, use_est_mask: bool = None,
               return_map: bool = None):
         """How far this (estimated) flow is from the ground truth `gt`, a flow of the same shape and reference: the

@@ -11,7 +11,7 @@ from .flow_class import Flow
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
            'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow',
-           'upsample_flow_convex', 'correlation_lookup', 'global_match', 'splat_flow']
+           'upsample_flow_convex', 'correlation_lookup', 'global_match', 'splat_flow', 'photometric_error']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -158,3 +158,13 @@ def splat_flow(flow: nd, target: nd, mask: nd = None, mode: str = 'average', imp
     reference's 's' apply."""
     return Flow(flow, 's', mask).splat(target, mode=mode, importance=importance, alpha=alpha, min_weight=min_weight,
                                        frac_bits=frac_bits, layout=layout)
+
+
+def photometric_error(flow: nd, near: nd, far: nd, ref: str = None, mask: nd = None, metric: str = 'l1', eps: float = None,
+                      threshold: float = None, near_mask: nd = None, far_mask: nd = None, layout: str = 'hwc') -> tuple:
+    """(error, covered) -- a float32 map and a bool array, plus the bool array `within` with `threshold` -- of the
+    photometric error of the flow array `flow` (H, W, 2) with reference `ref` and mask `mask` (None: all valid): `near`, the
+    image or feature array of the flow's own frame, against `far`, that of the other frame, sampled where the flow points
+    -- Flow.photometric: metric 'l1', 'l2' or 'charbonnier'; arrays (H, W), (H, W, C) or, with layout='chw', (C, H, W)."""
+    return Flow(flow, ref, mask).photometric(near, far, metric=metric, eps=eps, threshold=threshold, near_mask=near_mask,
+                                             far_mask=far_mask, layout=layout)
