@@ -1116,8 +1116,9 @@ int ofl_splat(const void *src, int elem, int layout, int N, int C, int H, int W,
  * entry takes host pointers (counts_host: host uint32[N][2] or NULL), uploads, launches, downloads and synchronises.
  * Bytes per pixel: reads 2 C elements (near streamed, far gathered) + 8 (flow) + 1 to 3 (masks); writes 4 + 1 + 1, where
  * K12 plus an elementwise pass writes and re-reads C elements more.
- * Not built: metrics over a window (census, SSIM, gradient constancy: a second pass), a reduction of the map to a mean or
- * percentiles, a backward pass, mixed element types or layouts, integer tensors on the device, padding offsets.
+ * Not built: the window metrics SSIM and gradient constancy (a second pass; the census distance is K22, below), a reduction
+ * of the map to a mean or percentiles, a backward pass, mixed element types or layouts, integer tensors on the device,
+ * padding offsets.
  */
 enum { OFL_PHOTO_L1 = 0, OFL_PHOTO_L2 = 1, OFL_PHOTO_CHARBONNIER = 2 };
 int ofl_photometric_dev(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
@@ -1130,6 +1131,53 @@ int ofl_photometric(const void *near, const void *far, int elem, int layout, int
                     const uint8_t *near_mask, const uint8_t *far_mask,
                     int metric, float eps, float tau,
                     float *err, uint8_t *covered, uint8_t *within, uint32_t *counts_host, int quant);
+
+/* ------------------------------------------------------------------ K22: census distance of a warp over a window
+ * K21 compares raw values, so a change of exposure or gain between the two frames reads as error everywhere.  The census
+ * distance compares the ORDER of the intensities in a K x K window around the pixel, in `near` and in the warped `far`
+ * (Zabih & Woodfill; the ternary census unsupervised flow trains and selects candidates on): a brightness change that
+ * keeps the order costs nothing.  One fused launch: the warped image is never written.
+ *     near, far, elem, layout, N, C, H, W, flow, fmask, flow_shared, sign, near_mask, far_mask, quant: K21's, but C in [1, 4]
+ *     window    K in {3, 5, 7}, r = K / 2;    mode  OFL_CENSUS_HARD or OFL_CENSUS_SOFT
+ *     p0, p1    HARD: p0 = delta >= 0 (p1 is not read);  SOFT: p0 = noise > 0, p1 = knee > 0 (0.81 and 0.1 in the literature,
+ *               both meant for intensities 0 ... 255)
+ *     min_count in [1, K * K - 1]: the members a window needs;  tau as in K21
+ * Per item n and pixel q, every operation float32 and rounded once (no FMA), exactly as K21 computes them:
+ *     tap(q), w_c(q), am(q);   cov1(q) = fmask & near_mask (NULL: 1) & (am(q) == 1.0f)          == K21's covered
+ *     A(q) = (near_0 + ... + near_(C-1)) * inv_c,  B(q) = (w_0 + ... + w_(C-1)) * inv_c,  inv_c = (float)(1.0 / (double)C),
+ *            each sum started at +0.0f and added in ascending c                                   (K21's order for one group)
+ *     member(q) = q inside the frame & cov1(q)
+ * For the pixel p and every offset d = (dx, dy) with |dx|, |dy| <= r and d != 0:
+ *     a = A(p + d) - A(p);   b = B(p + d) - B(p)
+ *     HARD:  s(v) = v > delta ? 1 : (v < -delta ? -1 : 0)   (a NaN compares false twice: 0);   t_d = s(a) != s(b) ? 1.0f : 0.0f
+ *     SOFT:  rho(v) = v / sqrtf(noise + v * v)   (product, sum, the correctly rounded sqrtf, a correctly rounded division)
+ *            g = rho(a) - rho(b);   q = g * g;   t_d = q / (knee + q)
+ *     t_d is REPLACED by +0.0f where !member(p + d)                 (a select, not a product: a NaN there does not leak)
+ *     R_dy = t_(-r,dy) + ... + t_(r,dy), added in ascending dx to +0.0f;   S = R_(-r) + ... + R_r, in ascending dy to +0.0f
+ *     n = the number of member offsets;   covered(p) = cov1(p) & (n >= min_count)
+ *     e = S / (float)n (correctly rounded);   err = covered ? e : 0.0f;   within = covered & (e <= tau)
+ * min_count = K * K - 1 asks for the full window, the border mask the literature uses.  There is NO zero-flow short cut.
+ * tests/census_ref.py restates all of this in NumPy.
+ *     err, covered, within, counts: K21's ([N][H][W]; one of err / within required; counts uint32[N][2] ADDED to, at most one
+ *     integer atomic add per workgroup and counter; no other atomics, no workspace).
+ * Alignment, 64-bit offsets, aliasing and the two entries (asynchronous _dev, host-staged) as in K21.  A bad argument -- those
+ * of K21, C > 4, another window or mode, min_count outside [1, K * K - 1], delta negative, noise or knee not positive, any
+ * of them or tau (when within is given) not finite -- returns OFL_E_INVALID with a message before any launch.
+ * Not built: C > 4 and a per-channel census, luma weights (pass a reduced plane), SSIM and gradient constancy, windows above
+ * 7 or not square, a reduction of the map, a backward pass, mixed element types or layouts, integer tensors on the device.
+ */
+enum { OFL_CENSUS_HARD = 0, OFL_CENSUS_SOFT = 1 };
+enum { OFL_CENSUS_MAX_C = 4 };
+int ofl_census_dev(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                   const float *flow, const uint8_t *fmask, int flow_shared, int sign,
+                   const uint8_t *near_mask, const uint8_t *far_mask,
+                   int window, int mode, float p0, float p1, int min_count, float tau,
+                   float *err, uint8_t *covered, uint8_t *within, uint32_t *counts, int quant, void *stream);
+int ofl_census(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+               const float *flow, const uint8_t *fmask, int flow_shared, int sign,
+               const uint8_t *near_mask, const uint8_t *far_mask,
+               int window, int mode, float p0, float p1, int min_count, float tau,
+               float *err, uint8_t *covered, uint8_t *within, uint32_t *counts_host, int quant);
 
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`

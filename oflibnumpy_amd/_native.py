@@ -29,6 +29,8 @@ CORR_V, CORR_L = 4, 16
 MATCH_TILE, MATCH_WAVES = 32, 4
 SPLAT_SUM, SPLAT_AVERAGE, SPLAT_SOFTMAX = 0, 1, 2
 PHOTO_L1, PHOTO_L2, PHOTO_CHARBONNIER = 0, 1, 2
+CENSUS_HARD, CENSUS_SOFT = 0, 1
+CENSUS_MAX_C = 4
 
 
 class MeshCert(ctypes.Structure):
@@ -169,6 +171,10 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _ci, _vp]),
     "ofl_photometric": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _cf, _cf,
                               _vp, _vp, _vp, _vp, _ci]),
+    "ofl_census_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _ci, _cf, _cf, _ci, _cf,
+                             _vp, _vp, _vp, _vp, _ci, _vp]),
+    "ofl_census": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _ci, _cf, _cf, _ci, _cf,
+                         _vp, _vp, _vp, _vp, _ci]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

@@ -302,12 +302,11 @@ def photometric_args(metric='l1', eps=None, threshold=None):
     return PHOTO_METRICS[metric], out[0], out[1]
 
 
-def photometric_host_array(a, layout, name):
+def photometric_host_array(a, layout, name, prefix="Error computing photometric error: "):
     """A tensor given to Flow.photometric / photometric_error -> (contiguous array in memory order, layout): a NumPy array
     of float32 or float16, or of uint8 (an image: converted to float32, which is exact), of shape (H, W) -- one channel --,
     (H, W, C) with layout 'hwc' or (C, H, W) with layout 'chw'; a leading item axis makes (N, H, W, C) / (N, C, H, W).
-    TypeError for another type or dtype, ValueError for another rank or layout."""
-    prefix = "Error computing photometric error: "
+    TypeError for another type or dtype, ValueError for another rank or layout; `prefix` starts the messages (K22 passes its own)."""
     if not isinstance(a, np.ndarray):
         raise TypeError("{}{} needs to be a numpy array, got {}".format(prefix, name, type(a).__name__))
     if layout not in _TENSOR_LAYOUT:
@@ -322,6 +321,68 @@ def photometric_host_array(a, layout, name):
         raise ValueError("{}{} needs to have shape (H, W), {}, got {}".format(
             prefix, name, "(C, H, W) or (N, C, H, W)" if layout == 'chw' else "(H, W, C) or (N, H, W, C)", a.shape))
     return np.ascontiguousarray(a)
+
+
+# -- census distance of a warp over a window (K22)
+CENSUS_MODES = {'hard': nat.CENSUS_HARD, 'soft': nat.CENSUS_SOFT}
+CENSUS_WINDOWS = (3, 5, 7)
+CENSUS_DELTA, CENSUS_NOISE, CENSUS_KNEE = 0.0, 0.81, 0.1     # the dead zone; the ternary census' constants, for 0 ... 255
+
+
+def census_args(window=7, mode='soft', delta=None, noise=None, knee=None, min_count=None, threshold=None):
+    """Validation of the settings of a census distance (K22) on the host before any device work -> (window, mode code, p0,
+    p1, min_count, threshold): p0, p1 as float32 -- (delta, 0) for 'hard', (noise, knee) for 'soft' --, threshold as float32
+    or None.  window: 3, 5 or 7; mode: 'hard' (sign census with the dead zone `delta` >= 0, None: 0) or 'soft' (the ternary
+    census with `noise` > 0, None: 0.81, and `knee` > 0, None: 0.1); a parameter of the other mode must stay None;
+    min_count: the valid neighbours a window needs, 1 ... window^2 - 1, None: all of them; threshold: None for no `within`
+    output, else the bound err <= threshold.  A bool or a value of the wrong type is a TypeError, a value out of range or
+    not finite (as given, or once rounded to float32) a ValueError."""
+    prefix = "Error computing census distance: "
+    if isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, np.integer)):
+        raise TypeError("{}window must be an integer, got {}".format(prefix, type(window).__name__))
+    if window not in CENSUS_WINDOWS:
+        raise ValueError("{}window must be 3, 5 or 7, got {}".format(prefix, window))
+    if not isinstance(mode, str):
+        raise TypeError("{}mode must be a string, got {}".format(prefix, type(mode).__name__))
+    if mode not in CENSUS_MODES:
+        raise ValueError("{}mode must be 'hard' or 'soft', got {!r}".format(prefix, mode))
+    for name, value, wanted in (("delta", delta, 'hard'), ("noise", noise, 'soft'), ("knee", knee, 'soft')):
+        if value is not None and mode != wanted:
+            raise ValueError("{}{} belongs to mode '{}' and must be None with mode '{}'".format(prefix, name, wanted, mode))
+    if mode == 'hard':
+        values = (("delta", CENSUS_DELTA if delta is None else delta, False), ("threshold", threshold, False))
+    else:
+        values = (("noise", CENSUS_NOISE if noise is None else noise, True), ("knee", CENSUS_KNEE if knee is None else knee, True),
+                  ("threshold", threshold, False))
+    out = {}
+    for name, value, positive in values:
+        if value is None:
+            out[name] = None
+            continue
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise TypeError("{}{} must be a number or None, got {}".format(prefix, name, type(value).__name__))
+        with np.errstate(over='ignore'):
+            v32 = np.float32(float(value)) if abs(value) < 1e300 else np.float32(np.inf if value > 0 else -np.inf)
+        if value != value or value < 0 or not np.isfinite(v32) or (positive and not v32 > 0):
+            raise ValueError("{}{} must be finite and {}, got {}".format(prefix, name, "positive" if positive else "not negative", value))
+        out[name] = v32
+    full = int(window) * int(window) - 1
+    if min_count is None:
+        min_count = full
+    if isinstance(min_count, (bool, np.bool_)) or not isinstance(min_count, (int, np.integer)):
+        raise TypeError("{}min_count must be an integer or None, got {}".format(prefix, type(min_count).__name__))
+    if not 1 <= min_count <= full:
+        raise ValueError("{}min_count must be in [1, {}] for window {}, got {}".format(prefix, full, window, min_count))
+    p0, p1 = (out["delta"], np.float32(0)) if mode == 'hard' else (out["noise"], out["knee"])
+    return int(window), CENSUS_MODES[mode], p0, p1, int(min_count), out["threshold"]
+
+
+def census_channels(c):
+    """The channel count of a census distance (K22): 1 ... 4, else a ValueError that names the limit."""
+    if not 1 <= c <= nat.CENSUS_MAX_C:
+        raise ValueError("Error computing census distance: the tensors need 1 to {} channels (grey, two-plane, RGB, RGBA), got {}"
+                         .format(nat.CENSUS_MAX_C, c))
+    return c
 
 
 # -- an estimate against a ground truth (K14)

@@ -161,6 +161,26 @@ class DeviceFlowBatch:
         res = (err, covered) + ((within,) if within is not None else ())
         return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
 
+    def census(self, near, far, window=7, mode='soft', delta=None, noise=None, knee=None, min_count=None, threshold=None,
+               near_mask=None, far_mask=None, return_counts=False, quant=nat.QUANT_OPENCV):
+        """self[i].census(item i of `near`, item i of `far`, ...) for every i in ONE launch of K22 (DeviceFlow.census):
+        near, far DeviceTensors (n, C, H, W) of one layout and dtype with 1 to 4 channels, near_mask, far_mask uint8
+        DeviceBuffers [n][H][W] (per item) or None.  -> (error float32, covered uint8) as DeviceBuffers [n][H][W];
+        `threshold` appends within (uint8), return_counts an (n, 2) uint32 array of (covered, within) pixels per item -- the
+        only option that synchronises.  A packed batch is read through its byte masks."""
+        prefix = "Error computing census distance: "
+        settings = dev.census_args(window, mode, delta, noise, knee, min_count, threshold)
+        near, far = dev.photometric_tensors(near, far, self.shape, batch=self.n, prefix=prefix)
+        dev.census_channels(near.channels)
+        n_bytes = self.n * self.shape[0] * self.shape[1]
+        near_mask = dev.mask_buffer_arg(near_mask, n_bytes, prefix, "near_mask")
+        far_mask = dev.mask_buffer_arg(far_mask, n_bytes, prefix, "far_mask")
+        err, covered, within, counts = dev.census_launch(
+            near.buf, far.buf, near.dtype, near.layout, self.n, near.channels, self.shape, self.vecs, self.mask, False,
+            1 if self.ref == 's' else -1, *settings, near_mask=near_mask, far_mask=far_mask, want_counts=bool(return_counts), quant=quant)
+        res = (err, covered) + ((within,) if within is not None else ())
+        return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
+
     def error(self, gt, thresholds=None, outlier=None, speed_edges=None, use_est_mask=True, return_map=False, return_outliers=False):
         """self[i].error(gt[i], ...) for every i in ONE launch of K14 (DeviceFlow.error): `gt` a batch of the same length,
         shape and reference.  -> a DeviceFlowError whose read() gives a list of n FlowErrorStats (the one read-back, 96 bytes

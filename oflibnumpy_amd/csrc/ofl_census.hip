@@ -1,0 +1,331 @@
+// ofl_census.hip -- K22: census distance of a warp over a window (gfx950).
+//
+// K21 asks whether a pixel looks the same where the field sends it and compares raw values; K22 compares the ORDER of the
+// intensities in a K x K window around the pixel, in `near` and in the warped `far`, so a change of exposure or gain that
+// keeps the order costs nothing (Zabih & Woodfill; the ternary census of UnFlow / DDFlow / ARFlow / UFlow / SMURF).
+// Per item n and pixel q, every operation float32 and rounded once, exactly as K21 computes them:
+//     tap(q), w_c(q), am(q);  cov1(q) = f.mask & near_mask & (am == 1.0f)                       -- K21's `covered`
+//     A(q) = (near_0 + ... + near_(C-1)) * inv_c,  B(q) = (w_0 + ... + w_(C-1)) * inv_c           -- ascending c from +0.0f
+//     member(q) = q inside the frame & cov1(q)
+// and for the pixel p and every offset d = (dx, dy), |dx|, |dy| <= r = K / 2, d != 0:
+//     a = A(p + d) - A(p),  b = B(p + d) - B(p)
+//     hard:  s(v) = v > delta ? 1 : (v < -delta ? -1 : 0);  t_d = s(a) != s(b) ? 1.0f : 0.0f
+//     soft:  rho(v) = v / sqrtf(noise + v * v);  g = rho(a) - rho(b);  q = g * g;  t_d = q / (knee + q)
+//     t_d = +0.0f where !member(p + d)                                                            -- a select, not a product
+//     R_dy = t_(-r,dy) + ... + t_(r,dy) from +0.0f;  S = R_(-r) + ... + R_r from +0.0f;  n = the member offsets
+//     covered = cov1(p) & (n >= min_count);  e = S / (float)n;  err = covered ? e : 0.0f;  within = covered & (e <= tau)
+// There is no zero-flow short cut.  16-bit elements are widened exactly.
+//
+// One workgroup of 256 threads per tile of 64 x 16 pixels of one item (K16's shape), lanes along x.
+//   Staging  the (64 + 2r) x (16 + 2r) pixels of the tile and its halo are dealt to the threads, up to 7 each.  A thread first
+//            loads the flow vectors of all its pixels, then per pixel makes the tap and issues the C `near` and 4 C `far` loads
+//            and the mask loads together (unconditional, as in K21: a tap outside the frame reads element 0 and is replaced by
+//            0.0f) and stores A, B and member to LDS: two float planes and one byte plane, kept apart, so a wave reads 64
+//            consecutive words.  Both layouts go through ONE code path, as a pixel stride and a channel stride; the element
+//            type and `quant` are template arguments and end here.  The warped image is never written.
+//   Window   a thread owns 4 consecutive rows of one column.  It walks the K + 3 tile rows its four windows span once; of
+//            each it reads the K values of A, B and member into registers and adds that row's R_dy to every centre whose
+//            window holds the row -- ascending rows are ascending dy for each centre, so the stated order is kept -- which
+//            takes (K + 3) K LDS reads per plane where four separate walks take 4 K^2.  The row loop is a real loop (its
+//            body holds 4 K terms; unrolled it would be 4 K^2 of them, 196 correctly rounded rho pairs at K = 7); every
+//            register array is indexed by unrolled constants only, so nothing goes to scratch.  The centre's own position
+//            adds +0.0f, which is exact because every term is >= +0 or NaN.  A row's member count is formed once and serves
+//            its four centres.  Hard mode counts its terms in an integer and converts once: every partial sum of the stated
+//            order is an integer of at most 48, exact in float32, so the bits are the same, and s(a) != s(b) is four
+//            compares and mask logic.
+// counts: K21's scheme (ballot + popcount, at most one integer atomicAdd per workgroup and counter); no other atomics, no
+// workspace, 64-bit element offsets.  36 instantiations: 3 element types x 2 quant x 3 windows x 2 modes.
+//
+// OUT OF SCOPE: C > 4 and a per-channel census, luma weights, SSIM and gradient constancy, windows above 7 or not square, a
+// reduction of the map, a backward pass, mixed element types or layouts, integer tensors.
+#include "ofl_common.h"
+#include "ofl_elem.h"
+#include "ofl_host_stage.h"
+#include "ofl_photo_dev.h"
+
+#pragma clang fp contract(off)
+
+using namespace ofl;
+
+namespace {
+
+constexpr int kTX = 64, kTY = 16;       // the tile
+constexpr int kRows = 4;                // rows of a column one thread owns: 4 waves x 4 rows
+
+struct CArgs {
+    const void    *near, *far;
+    const float   *flow;
+    const uint8_t *fmask, *near_mask, *far_mask;
+    float         *err;
+    uint8_t       *covered, *within;
+    uint32_t      *counts;
+    int            N, C, H, W, sign, min_count;
+    float          p0, p1, tau, inv_c;      // hard: p0 = delta; soft: p0 = noise, p1 = knee
+    size_t         step;                    // pixels from one item's field and masks to the next (0: shared)
+    size_t         s_px, s_ch;              // elements from a pixel to the next and from a channel to the next
+};
+
+// hard mode: s(a) != s(b).  delta >= 0, so v > delta and v < -delta exclude each other and the two signs are equal exactly when
+// both comparisons agree: four compares and mask logic, no select
+__device__ __forceinline__ bool census_differs(float a, float b, float delta)
+{
+    return ((a > delta) != (b > delta)) | ((a < -delta) != (b < -delta));           // a NaN compares false twice: s = 0
+}
+
+// soft mode: t_d of one offset from a = A(p + d) - A(p) and b = B(p + d) - B(p)
+__device__ __forceinline__ float census_soft(float a, float b, float noise, float knee)
+{
+    const float ra = __fdiv_rn(a, sqrtf(__fadd_rn(noise, __fmul_rn(a, a))));
+    const float rb = __fdiv_rn(b, sqrtf(__fadd_rn(noise, __fmul_rn(b, b))));
+    const float g = __fsub_rn(ra, rb), q = __fmul_rn(g, g);
+    return __fdiv_rn(q, __fadd_rn(knee, q));
+}
+
+template <int E, int QUANT, int K, int MODE>
+__global__ __launch_bounds__(256)
+void census_kernel(const CArgs a)
+{
+    typedef typename Elem<E>::T T;
+    constexpr int R = K / 2, TW = kTX + 2 * R, TH = kTY + 2 * R, NE = TW * TH, NIT = (NE + 255) / 256;
+    __shared__ float   s_a[NE], s_b[NE];
+    __shared__ uint8_t s_m[NE];
+
+    const int H = a.H, W = a.W, C = a.C;
+    const int n = blockIdx.z, x0 = blockIdx.x * kTX, y0 = blockIdx.y * kTY;
+    const size_t hw = (size_t)H * W, field = a.step * n;
+
+    // ------------------------------------------------------------------------------------------ staging
+    {
+        const float *flow = a.flow + 2 * field;
+        float2 f[NIT];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {                  // entry i of the tile; the flow of pixel 0 where there is no pixel
+            const int i = threadIdx.x + 256 * it, ty = i / TW, tx = i - ty * TW, x = x0 - R + tx, y = y0 - R + ty;
+            const bool inside = i < NE && (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
+            f[it] = *reinterpret_cast<const float2 *>(flow + 2 * (inside ? (size_t)y * W + x : (size_t)0));
+        }
+        const T *fp = static_cast<const T *>(a.far) + (size_t)n * C * hw;        // element 0 of item n
+        const T *np = static_cast<const T *>(a.near) + (size_t)n * C * hw;
+        const size_t s_px = a.s_px, s_ch = a.s_ch;
+        const float inv_c = a.inv_c;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int i = threadIdx.x + 256 * it, ty = i / TW, tx = i - ty * TW, x = x0 - R + tx, y = y0 - R + ty;
+            if (i >= NE) break;
+            float A = 0.0f, B = 0.0f;
+            bool member = false;
+            if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) {
+                const size_t pix = (size_t)y * W + x;
+                const Tap tp = make_tap<QUANT>(map_coord(x, f[it].x, a.sign), map_coord(y, f[it].y, a.sign));
+                bool in[4];
+                int  off[4];
+                tap_frame(tp, H, W, in, off);
+                member = photo_covered(a.fmask, a.near_mask, a.far_mask, field, pix, tp, in, off);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (c >= C) break;                                      // uniform
+                    const T *s = fp + (size_t)c * s_ch;
+                    float v[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float t = Elem<E>::to_f32(s[(size_t)off[k] * s_px]);
+                        v[k] = in[k] ? t : 0.0f;
+                    }
+                    A = __fadd_rn(A, Elem<E>::to_f32(np[pix * s_px + (size_t)c * s_ch]));
+                    B = __fadd_rn(B, blend4(v[0], v[1], v[2], v[3], tp));
+                }
+                A = __fmul_rn(A, inv_c);
+                B = __fmul_rn(B, inv_c);
+            }
+            s_a[i] = A;
+            s_b[i] = B;
+            s_m[i] = member ? 1 : 0;
+        }
+    }
+    __syncthreads();
+
+    // ------------------------------------------------------------------------------------------ window
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int top = kRows * wave;                           // the first tile row of this thread's windows
+    float ca[kRows], cb[kRows], S[kRows];
+    int   cnt[kRows], diff[kRows];
+    bool  cm[kRows];
+#pragma unroll
+    for (int j = 0; j < kRows; ++j) {
+        const int at = (top + R + j) * TW + lane + R;
+        ca[j] = s_a[at]; cb[j] = s_b[at]; cm[j] = s_m[at] != 0;
+        S[j] = 0.0f; cnt[j] = 0; diff[j] = 0;
+    }
+    const float p0 = a.p0, p1 = a.p1;
+#pragma unroll 1
+    for (int i = 0; i < K + kRows - 1; ++i) {
+        const int at = (top + i) * TW + lane;
+        float ra[K], rb[K];
+        bool  rm[K];
+        int   members = 0;                                                  // of this tile row: the same for every centre
+#pragma unroll
+        for (int d = 0; d < K; ++d) { ra[d] = s_a[at + d]; rb[d] = s_b[at + d]; rm[d] = s_m[at + d] != 0; members += rm[d] ? 1 : 0; }
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) {
+            if ((unsigned)(i - j) > (unsigned)(2 * R)) continue;            // uniform: dy = i - j - R outside the window
+            const bool mid = i - j == R;                                    // the centre's own row: d = R is the centre itself
+            cnt[j] += members - (mid && rm[R] ? 1 : 0);
+            if constexpr (MODE == OFL_CENSUS_HARD) {
+                // every term is 0 or 1, so every partial sum of the stated order is an integer of at most 48 and exact in
+                // float32: the terms are counted, and the count is converted once -- the same bits
+#pragma unroll
+                for (int d = 0; d < K; ++d)
+                    diff[j] += rm[d] && !(d == R && mid) && census_differs(__fsub_rn(ra[d], ca[j]), __fsub_rn(rb[d], cb[j]), p0) ? 1 : 0;
+            } else {
+                float row = 0.0f;
+#pragma unroll
+                for (int d = 0; d < K; ++d) {
+                    const float t = census_soft(__fsub_rn(ra[d], ca[j]), __fsub_rn(rb[d], cb[j]), p0, p1);
+                    row = __fadd_rn(row, rm[d] && !(d == R && mid) ? t : 0.0f);
+                }
+                S[j] = __fadd_rn(S[j], row);
+            }
+        }
+    }
+    if constexpr (MODE == OFL_CENSUS_HARD) {
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) S[j] = (float)diff[j];
+    }
+
+    uint32_t n_cov = 0, n_wi = 0;
+    const int x = x0 + lane;
+#pragma unroll
+    for (int j = 0; j < kRows; ++j) {
+        const int y = y0 + top + j;
+        const bool act = x < W && y < H;
+        const bool cov = act && cm[j] && cnt[j] >= a.min_count;
+        const float e = __fdiv_rn(S[j], (float)cnt[j]);
+        const bool wi = a.within != nullptr && cov && e <= a.tau;
+        if (act) {
+            const size_t o = (size_t)n * hw + (size_t)y * W + x;
+            if (a.err) a.err[o] = cov ? e : 0.0f;
+            if (a.covered) a.covered[o] = cov ? 1 : 0;
+            if (a.within) a.within[o] = wi ? 1 : 0;
+        }
+        n_cov += (uint32_t)__popcll(__ballot(cov));
+        n_wi += (uint32_t)__popcll(__ballot(wi));
+    }
+    if (a.counts) photo_count(a.counts, n, n_cov, n_wi);
+}
+
+int check_census_args(const char *who, const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                      const void *flow, const void *fmask, int sign, int window, int mode, float p0, float p1, int min_count,
+                      float tau, const void *err, const void *within, int quant)
+{
+    if (!near || !far || !flow || !fmask) return fail(OFL_E_INVALID, "%s: NULL pointer (near, far, flow and fmask are required)", who);
+    if (elem != OFL_EL_F16 && elem != OFL_EL_BF16 && elem != OFL_EL_F32)
+        return fail(OFL_E_INVALID, "%s: elem must be OFL_EL_F16, OFL_EL_BF16 or OFL_EL_F32, got %d", who, elem);
+    if (layout != OFL_TENSOR_NCHW && layout != OFL_TENSOR_NHWC) return fail(OFL_E_INVALID, "%s: bad layout %d", who, layout);
+    if (N < 1 || N > 65535) return fail(OFL_E_INVALID, "%s: N must be in [1, 65535], got %d", who, N);
+    if (C < 1 || C > OFL_CENSUS_MAX_C) return fail(OFL_E_INVALID, "%s: C must be in [1, %d], got %d", who, OFL_CENSUS_MAX_C, C);
+    OFL_TRY(check_field_dims(who, H, W));
+    if (sign != 1 && sign != -1) return fail(OFL_E_INVALID, "%s: sign must be +1 or -1", who);
+    if (window != 3 && window != 5 && window != 7) return fail(OFL_E_INVALID, "%s: window must be 3, 5 or 7, got %d", who, window);
+    if (mode == OFL_CENSUS_HARD) {
+        if (!(p0 >= 0.0f) || !__builtin_isfinite(p0)) return fail(OFL_E_INVALID, "%s: delta must be finite and not negative (got %g)", who, (double)p0);
+    } else if (mode == OFL_CENSUS_SOFT) {
+        if (!(p0 > 0.0f) || !__builtin_isfinite(p0)) return fail(OFL_E_INVALID, "%s: noise must be finite and positive (got %g)", who, (double)p0);
+        if (!(p1 > 0.0f) || !__builtin_isfinite(p1)) return fail(OFL_E_INVALID, "%s: knee must be finite and positive (got %g)", who, (double)p1);
+    } else {
+        return fail(OFL_E_INVALID, "%s: bad mode %d", who, mode);
+    }
+    if (min_count < 1 || min_count > window * window - 1)
+        return fail(OFL_E_INVALID, "%s: min_count must be in [1, %d], got %d", who, window * window - 1, min_count);
+    if (!err && !within) return fail(OFL_E_INVALID, "%s: one of err and within is required", who);
+    if (within && (!(tau >= 0.0f) || !__builtin_isfinite(tau)))
+        return fail(OFL_E_INVALID, "%s: tau must be finite and not negative (got %g)", who, (double)tau);
+    if (quant != OFL_QUANT_OPENCV && quant != OFL_QUANT_EXACT) return fail(OFL_E_INVALID, "%s: bad quant", who);
+    return OFL_OK;
+}
+
+template <int E, int QUANT, int K>
+void launch_census(const CArgs &a, int mode, hipStream_t s)
+{
+    const dim3 grid((unsigned)((a.W + kTX - 1) / kTX), (unsigned)((a.H + kTY - 1) / kTY), (unsigned)a.N);
+    if (mode == OFL_CENSUS_HARD) hipLaunchKernelGGL((census_kernel<E, QUANT, K, OFL_CENSUS_HARD>), grid, dim3(256), 0, s, a);
+    else                         hipLaunchKernelGGL((census_kernel<E, QUANT, K, OFL_CENSUS_SOFT>), grid, dim3(256), 0, s, a);
+}
+
+template <int E, int QUANT>
+void launch_census(const CArgs &a, int window, int mode, hipStream_t s)
+{
+    switch (window) {
+    case 3:  launch_census<E, QUANT, 3>(a, mode, s); break;
+    case 5:  launch_census<E, QUANT, 5>(a, mode, s); break;
+    default: launch_census<E, QUANT, 7>(a, mode, s); break;
+    }
+}
+
+template <int E>
+void launch_census(const CArgs &a, int window, int mode, int quant, hipStream_t s)
+{
+    if (quant == OFL_QUANT_OPENCV) launch_census<E, OFL_QUANT_OPENCV>(a, window, mode, s);
+    else                           launch_census<E, OFL_QUANT_EXACT>(a, window, mode, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ofl_census_dev(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                   const float *flow, const uint8_t *fmask, int flow_shared, int sign,
+                   const uint8_t *near_mask, const uint8_t *far_mask,
+                   int window, int mode, float p0, float p1, int min_count, float tau,
+                   float *err, uint8_t *covered, uint8_t *within, uint32_t *counts, int quant, void *stream)
+{
+    OFL_TRY(need_device());
+    OFL_TRY(check_census_args("ofl_census", near, far, elem, layout, N, C, H, W, flow, fmask, sign, window, mode, p0, p1, min_count, tau,
+                              err, within, quant));
+    const unsigned eb = elem == OFL_EL_F32 ? 4 : 2;
+    if (!host_aligned(near, eb) || !host_aligned(far, eb)) return fail(OFL_E_INVALID, "ofl_census: near and far must be aligned to the element size");
+    if (!host_aligned(flow, 8)) return fail(OFL_E_INVALID, "ofl_census: flow must be 8-byte aligned");
+    if (!host_aligned(err, 4) || !host_aligned(counts, 4)) return fail(OFL_E_INVALID, "ofl_census: err and counts must be 4-byte aligned");
+    CArgs a;
+    a.near = near; a.far = far; a.flow = flow; a.fmask = fmask; a.near_mask = near_mask; a.far_mask = far_mask;
+    a.err = err; a.covered = covered; a.within = within; a.counts = counts;
+    a.N = N; a.C = C; a.H = H; a.W = W; a.sign = sign; a.min_count = min_count;
+    a.p0 = p0; a.p1 = p1; a.tau = tau;
+    a.inv_c = (float)(1.0 / (double)C);
+    a.step = flow_shared ? 0 : (size_t)H * W;
+    a.s_px = layout == OFL_TENSOR_NCHW ? 1 : (size_t)C;
+    a.s_ch = layout == OFL_TENSOR_NCHW ? (size_t)H * W : 1;
+    hipStream_t s = stream_of(stream);
+    switch (elem) {
+    case OFL_EL_F16:  launch_census<OFL_EL_F16>(a, window, mode, quant, s); break;
+    case OFL_EL_BF16: launch_census<OFL_EL_BF16>(a, window, mode, quant, s); break;
+    default:          launch_census<OFL_EL_F32>(a, window, mode, quant, s); break;
+    }
+    OFL_HIP(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_census(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+               const float *flow, const uint8_t *fmask, int flow_shared, int sign,
+               const uint8_t *near_mask, const uint8_t *far_mask,
+               int window, int mode, float p0, float p1, int min_count, float tau,
+               float *err, uint8_t *covered, uint8_t *within, uint32_t *counts_host, int quant)
+{
+    OFL_TRY(need_device());
+    OFL_TRY(check_census_args("ofl_census", near, far, elem, layout, N, C, H, W, flow, fmask, sign, window, mode, p0, p1, min_count, tau,
+                              err, within, quant));
+    const size_t hw = (size_t)H * W, n = (size_t)N * hw, nf = flow_shared ? hw : n;
+    const size_t bytes = n * C * (elem == OFL_EL_F32 ? 4 : 2);
+    HostStage st("ofl_census");
+    auto dn = st.in(near, bytes), df = st.in(far, bytes);
+    auto dfl = st.in(flow, nf * 2);
+    auto dfm = st.in(fmask, nf), dnm = st.in(near_mask, nf), dam = st.in(far_mask, nf);
+    auto de = st.out(err, n);
+    auto dc = st.out(covered, n), dw = st.out(within, n);
+    auto cnt = st.out(counts_host, (size_t)N * 2, true);          // the launch adds to the counts
+    OFL_TRY(st.upload());
+    OFL_TRY(ofl_census_dev(dn, df, elem, layout, N, C, H, W, dfl, dfm, flow_shared, sign, dnm, dam, window, mode, p0, p1, min_count, tau,
+                           de, dc, dw, cnt, quant, st.stream()));
+    return st.download();
+}
+
+}  // extern "C"

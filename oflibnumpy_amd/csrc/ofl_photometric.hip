@@ -36,11 +36,14 @@
 // atomicAdd per counter (integer adds: their order cannot change the result); these are the only atomics.  Every element
 // offset is 64-bit.  No workspace.  A variant with two pixels per lane was not built: no figure, no variant.
 //
-// OUT OF SCOPE: window metrics (census, SSIM, gradient constancy), a reduction of the map, a backward pass, mixed element
-// types or layouts, integer tensors, padding offsets.
+// tap_frame, photo_covered and photo_count are shared with K22 (ofl_photo_dev.h).
+//
+// OUT OF SCOPE: window metrics (SSIM, gradient constancy; the census distance is K22, ofl_census.hip), a reduction of the
+// map, a backward pass, mixed element types or layouts, integer tensors, padding offsets.
 #include "ofl_common.h"
 #include "ofl_elem.h"
 #include "ofl_host_stage.h"
+#include "ofl_photo_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -71,29 +74,6 @@ __device__ __forceinline__ float photo_term(float d, int metric, float eps2)
     return metric == OFL_PHOTO_L2 ? q : sqrtf(__fadd_rn(q, eps2));
 }
 
-// the four in-frame flags and in-plane offsets of a tap (inside one plane: H * W < 2^31)
-__device__ __forceinline__ void tap_frame(const Tap &tp, int H, int W, bool (&in)[4], int (&off)[4])
-{
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int yy = tp.iy + (k >> 1), xx = tp.ix + (k & 1);
-        in[k]  = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
-        off[k] = in[k] ? yy * W + xx : 0;
-    }
-}
-
-// K12's `valid` ANDed with near_mask; masks are those of this pixel's field
-__device__ __forceinline__ bool photo_covered(const PArgs &a, size_t field, size_t pix, const Tap &tp, const bool (&in)[4], const int (&off)[4])
-{
-    const uint8_t *fm = a.far_mask ? a.far_mask + field : nullptr;
-    float m[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) m[k] = in[k] ? ((fm ? fm[off[k]] != 0 : true) ? 1.0f : 0.0f) : 0.0f;
-    bool cov = (blend4(m[0], m[1], m[2], m[3], tp) == 1.0f) & (a.fmask[field + pix] != 0);
-    if (a.near_mask) cov &= a.near_mask[field + pix] != 0;
-    return cov;
-}
-
 // the sum S -> the stores of one pixel; -> (covered, within) for the counts
 __device__ __forceinline__ void photo_finish(const PArgs &a, size_t at, float S, bool cov, bool &wi)
 {
@@ -103,21 +83,6 @@ __device__ __forceinline__ void photo_finish(const PArgs &a, size_t at, float S,
     if (a.err) a.err[at] = cov ? e : 0.0f;
     if (a.covered) a.covered[at] = cov ? 1 : 0;
     if (a.within) a.within[at] = wi ? 1 : 0;
-}
-
-// the block's two counts -> at most one atomicAdd per counter; every thread of the block calls this
-__device__ __forceinline__ void photo_count(const PArgs &a, int n, bool cov, bool wi)
-{
-    __shared__ uint32_t s_n[4][2];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t n_cov = (uint32_t)__popcll(__ballot(cov)), n_wi = (uint32_t)__popcll(__ballot(wi));
-    if (lane == 0) { s_n[wave][0] = n_cov; s_n[wave][1] = n_wi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t c0 = s_n[0][0] + s_n[1][0] + s_n[2][0] + s_n[3][0], c1 = s_n[0][1] + s_n[1][1] + s_n[2][1] + s_n[3][1];
-        if (c0) atomicAdd(a.counts + 2 * (size_t)n, c0);
-        if (c1) atomicAdd(a.counts + 2 * (size_t)n + 1, c1);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------- planar
@@ -142,7 +107,7 @@ void photo_nchw_kernel(const PArgs a)
         bool in[4];
         int  off[4];
         tap_frame(tp, H, W, in, off);
-        cov = photo_covered(a, field, pix, tp, in, off);
+        cov = photo_covered(a.fmask, a.near_mask, a.far_mask, field, pix, tp, in, off);
 
         const T *fp = static_cast<const T *>(a.far) + (size_t)n * C * hw;       // plane 0 of item n
         const T *np = static_cast<const T *>(a.near) + (size_t)n * C * hw + pix;
@@ -197,7 +162,7 @@ void photo_nchw_kernel(const PArgs a)
         }
         photo_finish(a, (size_t)n * hw + pix, S, cov, wi);
     }
-    if (a.counts) photo_count(a, n, cov, wi);
+    if (a.counts) photo_count(a.counts, n, (uint32_t)__popcll(__ballot(cov)), (uint32_t)__popcll(__ballot(wi)));
 }
 
 // ---------------------------------------------------------------------------------------------- channels-last
@@ -247,7 +212,7 @@ void photo_nhwc_kernel(const PArgs a, int lg)
         bool in[4];
         int  off[4];
         tap_frame(tp, H, W, in, off);
-        cov = photo_covered(a, field, pix, tp, in, off);
+        cov = photo_covered(a.fmask, a.near_mask, a.far_mask, field, pix, tp, in, off);
 
         const T *item = static_cast<const T *>(a.far) + (size_t)n * hw * C;
         const T *np = static_cast<const T *>(a.near) + ((size_t)n * hw + pix) * C;
@@ -272,7 +237,7 @@ void photo_nhwc_kernel(const PArgs a, int lg)
     const bool owner = act && j == 0;
     bool wi = false;
     if (owner) photo_finish(a, (size_t)n * hw + pix, p, cov, wi);
-    if (a.counts) photo_count(a, n, owner && cov, wi);
+    if (a.counts) photo_count(a.counts, n, (uint32_t)__popcll(__ballot(owner && cov)), (uint32_t)__popcll(__ballot(wi)));
 }
 
 int check_photometric_args(const char *who, const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,

@@ -33,7 +33,7 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rul
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
                    consistency_args, error_args, fill_args, median_args, upsample_args, upsample_weights_array, corr_args,
                    corr_host_array, optional_bool, mask_array_arg, match_args, match_host_array, splat_args, splat_host_array,
-                   splat_importance_array, photometric_args, photometric_host_array)
+                   splat_importance_array, photometric_args, photometric_host_array, census_args, census_channels)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
@@ -41,7 +41,7 @@ from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stat
                       tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
                       FlowErrorStats, fill_launch, fill_host, median_launch, median_host, upsample_launch,
                       upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host, match_launch, match_host, splat_launch, splat_host,
-                      photometric_launch, photometric_host)
+                      photometric_launch, photometric_host, census_launch, census_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -378,11 +378,10 @@ def splat_importance(buf, n_px):
     return buf
 
 
-def photometric_tensors(near, far, field_shape, batch=None):
+def photometric_tensors(near, far, field_shape, batch=None, prefix="Error computing photometric error: "):
     """The `near` and `far` of DeviceFlow.photometric (batch None) or DeviceFlowBatch.photometric (batch n) -> two
     DeviceTensors of one shape, layout and dtype with the height and width of the field.  A float32 DeviceImage [H][W][C] is
-    taken as the channels-last tensor it is, on the same buffer."""
-    prefix = "Error computing photometric error: "
+    taken as the channels-last tensor it is, on the same buffer.  `prefix` starts the messages (census passes its own)."""
     pair = []
     for name, t in (("near", near), ("far", far)):
         if isinstance(t, DeviceImage):
@@ -725,8 +724,8 @@ class DeviceFlow:
         -> (error, covered): a float32 and a uint8 DeviceBuffer [N][H][W]; `threshold` appends within = covered &
         (error <= threshold) as uint8, return_counts appends [(n_covered, n_within)] * N as Python ints -- the only option
         that synchronises.  `error` is what splat(mode='softmax', importance=error, alpha=-20.0) takes, without a copy.
-        Not built: window metrics (census, SSIM, gradient constancy), a mean or percentiles of the map, a backward pass,
-        mixed dtypes or layouts, integer tensors, padding offsets.  The inputs are not modified."""
+        Not built: the window metrics SSIM and gradient constancy (the census distance is `census`), a mean or percentiles
+        of the map, a backward pass, mixed dtypes or layouts, integer tensors, padding offsets.  The inputs are not modified."""
         prefix = "Error computing photometric error: "
         code, eps, threshold = photometric_args(metric, eps, threshold)
         near, far = photometric_tensors(near, far, self.shape)
@@ -735,6 +734,37 @@ class DeviceFlow:
         err, covered, within, counts = photometric_launch(
             near.buf, far.buf, near.dtype, near.layout, near.n, near.channels, self.shape, self.vecs, self.mask, True,
             1 if self.ref == 's' else -1, code, eps, threshold, near_mask, far_mask, want_counts=bool(return_counts), quant=quant)
+        res = (err, covered) + ((within,) if within is not None else ())
+        if return_counts:
+            res += ([(int(a), int(b)) for a, b in counts.to_host((near.n, 2), np.uint32)],)
+        return res
+
+    def census(self, near, far, window=7, mode='soft', delta=None, noise=None, knee=None, min_count=None, threshold=None,
+               near_mask=None, far_mask=None, return_counts=False, quant=nat.QUANT_OPENCV):
+        """The census distance of this field in ONE launch of K22 (include/ofl.h): where photometric compares the values of
+        `near` and of `far` sampled where this field points, census compares the ORDER of the intensities -- the channel
+        means A of `near` and B of the warped `far` -- in a window x window neighbourhood of the pixel, so a change of
+        exposure or gain that keeps the order costs nothing.  Per neighbour d: a = A(p + d) - A(p), b = B(p + d) - B(p) and
+            'hard'  1 where sign(a) != sign(b), each sign 0 inside the dead zone |v| <= delta (None: 0)
+            'soft'  q / (knee + q) of q = (rho(a) - rho(b))^2, rho(v) = v / sqrt(noise + v^2) -- the ternary census of
+                    unsupervised flow; noise None: 0.81, knee None: 0.1, both meant for intensities 0 ... 255
+        averaged over the neighbours that are inside the frame and covered as photometric defines it; a pixel is covered
+        when photometric covers it and at least min_count neighbours (None: all window^2 - 1, the usual border mask) are.
+        near, far, near_mask, far_mask, quant: as in photometric, with 1 to 4 channels.  Not a function of the reference and
+        without a zero-flow short cut; works for 's' and 't' fields alike.
+        -> (error, covered): a float32 and a uint8 DeviceBuffer [N][H][W]; `threshold` appends within = covered &
+        (error <= threshold) as uint8, return_counts appends [(n_covered, n_within)] * N as Python ints -- the only option
+        that synchronises.  Not built: more than 4 channels, a per-channel census, luma weights, SSIM, gradient constancy,
+        other windows, a mean of the map, a backward pass.  The inputs are not modified."""
+        prefix = "Error computing census distance: "
+        settings = census_args(window, mode, delta, noise, knee, min_count, threshold)
+        near, far = photometric_tensors(near, far, self.shape, prefix=prefix)
+        census_channels(near.channels)
+        near_mask = mask_buffer_arg(near_mask, self.n_px, prefix, "near_mask")
+        far_mask = mask_buffer_arg(far_mask, self.n_px, prefix, "far_mask")
+        err, covered, within, counts = census_launch(
+            near.buf, far.buf, near.dtype, near.layout, near.n, near.channels, self.shape, self.vecs, self.mask, True,
+            1 if self.ref == 's' else -1, *settings, near_mask=near_mask, far_mask=far_mask, want_counts=bool(return_counts), quant=quant)
         res = (err, covered) + ((within,) if within is not None else ())
         if return_counts:
             res += ([(int(a), int(b)) for a, b in counts.to_host((near.n, 2), np.uint32)],)

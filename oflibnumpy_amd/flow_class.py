@@ -459,6 +459,36 @@ class Flow(object):
                                    threshold, near_mask, far_mask, quant)
         return res if batched else tuple(r[0] for r in res)
 
+    def census(self, near: np.ndarray, far: np.ndarray, window: int = 7, mode: str = 'soft', delta: float = None,
+               noise: float = None, knee: float = None, min_count: int = None, threshold: float = None,
+               near_mask: np.ndarray = None, far_mask: np.ndarray = None, layout: str = 'hwc',
+               quant: int = 0) -> Tuple[np.ndarray, ...]:
+        """The census distance of this flow: the order of the intensities (channel means) in a window x window
+        neighbourhood of each pixel of `near`, the image of the flow's own frame, against the same in `far`, that of the
+        other frame, sampled where the flow points -- 'hard' (share of neighbours whose sign differs, dead zone `delta`) or
+        'soft' (the ternary census of unsupervised flow, `noise` None: 0.81, `knee` None: 0.1, for intensities 0 ... 255);
+        unlike photometric it ignores a change of exposure or gain.  near, far: arrays as in photometric with 1 to 4
+        channels, uint8 images included (converted to float32, exact).  min_count: the valid neighbours a pixel needs, None:
+        all window^2 - 1.  -> (error float32, covered bool), each (H, W) -- or (N, H, W) --, plus within = covered &
+        (error <= threshold) as bool with `threshold`.  Not a function of the reference; the definition is
+        DeviceFlow.census's.  One upload, one launch, one download."""
+        prefix = "Error computing census distance: "
+        settings = dev.census_args(window, mode, delta, noise, knee, min_count, threshold)
+        near, far = dev.photometric_host_array(near, layout, "near", prefix), dev.photometric_host_array(far, layout, "far", prefix)
+        if near.shape != far.shape:
+            raise ValueError("{}the arrays need the same shape, got {} and {}".format(prefix, near.shape, far.shape))
+        if near.dtype != far.dtype:
+            raise TypeError("{}the arrays need the same dtype, got {} and {}".format(prefix, near.dtype, far.dtype))
+        n, c, h, w, batched = dev.tensor_args(dev.tensor_logical_shape(near.shape, layout), layout, near.dtype.name)
+        dev.census_channels(c)
+        if (h, w) != tuple(self.shape):
+            raise ValueError("{}arrays and flow need the same height and width, got {} and {}".format(prefix, (h, w), tuple(self.shape)))
+        near_mask = None if near_mask is None else dev.mask_array_arg(near_mask, self.shape, prefix, "near_mask")
+        far_mask = None if far_mask is None else dev.mask_array_arg(far_mask, self.shape, prefix, "far_mask")
+        res = dev.census_host(near, far, layout, n, c, self._vecs, self._mask, 1 if self._ref == 's' else -1, *settings,
+                              near_mask=near_mask, far_mask=far_mask, quant=quant)
+        return res if batched else tuple(r[0] for r in res)
+
     def error(self, gt: FlowAlias, thresholds=None, outlier=None, speed_edges=None, use_est_mask: bool = None,
               return_map: bool = None):
         """How far this (estimated) flow is from the ground truth `gt`, a flow of the same shape and reference: the

@@ -11,7 +11,7 @@ from .flow_class import Flow
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
            'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow',
-           'upsample_flow_convex', 'correlation_lookup', 'global_match', 'splat_flow', 'photometric_error']
+           'upsample_flow_convex', 'correlation_lookup', 'global_match', 'splat_flow', 'photometric_error', 'census_error']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -168,3 +168,16 @@ def photometric_error(flow: nd, near: nd, far: nd, ref: str = None, mask: nd = N
     -- Flow.photometric: metric 'l1', 'l2' or 'charbonnier'; arrays (H, W), (H, W, C) or, with layout='chw', (C, H, W)."""
     return Flow(flow, ref, mask).photometric(near, far, metric=metric, eps=eps, threshold=threshold, near_mask=near_mask,
                                              far_mask=far_mask, layout=layout)
+
+
+def census_error(flow: nd, near: nd, far: nd, ref: str = None, mask: nd = None, window: int = 7, mode: str = 'soft',
+                 delta: float = None, noise: float = None, knee: float = None, min_count: int = None, threshold: float = None,
+                 near_mask: nd = None, far_mask: nd = None, layout: str = 'hwc') -> tuple:
+    """(error, covered) -- a float32 map and a bool array, plus the bool array `within` with `threshold` -- of the census
+    distance of the flow array `flow` (H, W, 2) with reference `ref` and mask `mask` (None: all valid): the order of the
+    intensities in a window around each pixel of `near`, the image of the flow's own frame, against that in `far`, sampled
+    where the flow points -- Flow.census: mode 'hard' or 'soft', window 3, 5 or 7; arrays (H, W), (H, W, C) or, with
+    layout='chw', (C, H, W), 1 to 4 channels."""
+    return Flow(flow, ref, mask).census(near, far, window=window, mode=mode, delta=delta, noise=noise, knee=knee,
+                                        min_count=min_count, threshold=threshold, near_mask=near_mask, far_mask=far_mask,
+                                        layout=layout)

@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching, K20 splatting and K21 photometric error.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching, K20 splatting, K21 photometric error and K22 census distance.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -618,5 +618,42 @@ def photometric_host(near, far, layout, n, c, vecs, mask, sign, metric, eps, thr
                                      n, c, h, w, vecs.ctypes.data, m.ctypes.data, 1, sign, _host_ptr(near_mask),
                                      _host_ptr(far_mask), metric, eps, np.float32(0) if threshold is None else threshold,
                                      err.ctypes.data, covered.ctypes.data, _host_ptr(within), None, quant))
+    res = (err, covered.view(np.bool_))
+    return res + (within.view(np.bool_),) if within is not None else res
+
+
+# ------------------------------------------------------------------------------ K22: census distance of a warp over a window
+def census_launch(near, far, dtype, layout, n, c, shape, flow, fmask, flow_shared, sign, window, mode, p0, p1, min_count,
+                  threshold=None, near_mask=None, far_mask=None, want_err=True, want_covered=True, want_counts=False,
+                  quant=nat.QUANT_OPENCV, stream=None):
+    """K22 (ofl_census_dev) on `n` items of `c` channels (1 to 4) in `layout` ('chw' / 'hwc') of `dtype`; buffers and the
+    shared or per-item field and masks as in photometric_launch; asynchronous, one launch.  window, mode, p0, p1, min_count,
+    threshold: from args.census_args (threshold None: no `within`).  -> (err or None, covered or None, within or None,
+    counts or None): float32, uint8 and uint8 [n][H][W] and the zeroed-then-added uint32 [n][2] = {covered, within} words,
+    all still in HBM."""
+    px = n * shape[0] * shape[1]
+    err = DeviceBuffer(px * 4) if want_err else None
+    covered = DeviceBuffer(px) if want_covered else None
+    within = DeviceBuffer(px) if threshold is not None else None
+    counts = DeviceBuffer.zeros(n * 8, stream) if want_counts else None
+    nat.check(_lib().ofl_census_dev(near.ptr, far.ptr, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, shape[0], shape[1],
+                                    flow.ptr, fmask.ptr, 1 if flow_shared else 0, sign, _ptr(near_mask), _ptr(far_mask),
+                                    window, mode, p0, p1, min_count, np.float32(0) if threshold is None else threshold,
+                                    _ptr(err), _ptr(covered), _ptr(within), _ptr(counts), quant, stream))
+    return err, covered, within, counts
+
+
+def census_host(near, far, layout, n, c, vecs, mask, sign, window, mode, p0, p1, min_count, threshold=None, near_mask=None,
+                far_mask=None, quant=nat.QUANT_OPENCV):
+    """K22 for host arrays through ofl_census (upload, one launch, download): arrays, field and masks as in
+    photometric_host -> (err float32, covered bool[, within bool]), each (n, H, W)."""
+    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(mask)
+    h, w = vecs.shape[:2]
+    err, covered = np.empty((n, h, w), np.float32), np.empty((n, h, w), np.uint8)
+    within = np.empty((n, h, w), np.uint8) if threshold is not None else None
+    nat.check(_lib().ofl_census(near.ctypes.data, far.ctypes.data, _TENSOR_EL[near.dtype.name], _TENSOR_LAYOUT[layout],
+                                n, c, h, w, vecs.ctypes.data, m.ctypes.data, 1, sign, _host_ptr(near_mask), _host_ptr(far_mask),
+                                window, mode, p0, p1, min_count, np.float32(0) if threshold is None else threshold,
+                                err.ctypes.data, covered.ctypes.data, _host_ptr(within), None, quant))
     res = (err, covered.view(np.bool_))
     return res + (within.view(np.bool_),) if within is not None else res
