@@ -1179,6 +1179,76 @@ int ofl_census(const void *near, const void *far, int elem, int layout, int N, i
                int window, int mode, float p0, float p1, int min_count, float tau,
                float *err, uint8_t *covered, uint8_t *within, uint32_t *counts_host, int quant);
 
+/* ------------------------------------------------------------------ K23: variational refinement of a field on two images
+ * K13, K21 and K22 score a field, K15 and K16 move existing vectors around; K23 moves a vector a fraction of a pixel towards
+ * where the images say it belongs: the variational refinement of Brox et al. (ECCV 2004) without the gradient-constancy
+ * term, the step EpicFlow, DeepFlow, RICFlow and DIS end with.  out = f + d, where d = (du, dv) approximately minimises
+ *     E(d) = sum_q data(q) (delta / n(q)) psi(r(q)^2 / n(q) ...) + alpha sum_q psi(|grad(u + du)|^2 + |grad(v + dv)|^2),
+ *     psi(s^2) = sqrt(s^2 + eps^2)
+ * by ONE linearisation (one warp), `fixed_point` lagged-weight updates and `sor` red-black SOR sweeps per update.  Calling
+ * it again re-warps; there is no loop over warps inside.  There is NO zero-flow short cut.
+ *     near, far, elem, layout, C, H, W, sign, near_mask, far_mask, quant: K22's (C in [1, 4]); N fields, fmasks and masks lie
+ *     back to back, one per item;  valid: uint8 [N][H][W] or NULL (all set), as in K15 / K16
+ * Every operation is float32 and rounded once (no FMA); sqrtf and every division are the correctly rounded ones; a sum
+ * written a + b + c is (a + b) + c.  (u, v) = flow[q], ex = (1, 0), ey = (0, 1), zeta2 = zeta * zeta, eps2 = eps * eps.
+ * Setup, per item and pixel q:
+ *     A(q), B(q), cov1(q)   K22's: the channel means of `near` and of the warped `far`, and K21's covered
+ *     dom(q)  = fmask(q) & valid(q) & isfinite(u) & isfinite(v)               a pixel outside the domain keeps its vector bit
+ *               for bit, has d = 0 and is nobody's neighbour
+ *     Bx = 0.5f * (B(q + ex) - B(q - ex)),  By = 0.5f * (B(q + ey) - B(q - ey));  a neighbour outside the frame is replaced
+ *               by q itself;   gx = sign > 0 ? Bx : -Bx,  gy likewise;   Iz = B(q) - A(q)
+ *     n       = gx * gx + gy * gy + zeta2
+ *     data(q) = dom(q) & cov1(q) & cov1 at every 4-neighbour inside the frame & isfinite(gx) & isfinite(gy) & isfinite(Iz)
+ *     d(q)    = (+0.0f, +0.0f)
+ * Each of the fixed_point iterations, from the current d:
+ *     r  = Iz + gx * du + gy * dv;    wD = data ? delta / (n * sqrtf((r * r) / n + eps2)) : +0.0f              (a select)
+ *     p  = wD * gx,  q = wD * gy;   A11 = p * gx,  A12 = p * gy,  A22 = q * gy,  b1 = -(p * Iz),  b2 = -(q * Iz)
+ *     U  = u + du,  V = v + dv;   Ux = 0.5f * (U(q + ex) - U(q - ex)),  Uy, Vx, Vy likewise; a neighbour outside the frame
+ *          OR the domain is replaced by q itself
+ *     s  = alpha / sqrtf(Ux * Ux + Uy * Uy + Vx * Vx + Vy * Vy + eps2)
+ *     w(q, q') = q' inside the frame and the domain ? 0.5f * (s(q) + s(q')) : +0.0f
+ *     sigma = +0.0f + w_up + w_left + w_right + w_down                        (q - ey, q - ex, q + ex, q + ey: the order of
+ *                                                                             every sum over the neighbours)
+ *   and each of the `sor` sweeps, colour 0 then colour 1 with colour = (x + y) & 1, for the domain pixels of that colour:
+ *     t_k  = neighbour k ? w_k * ((u' + du') - u) : +0.0f                      (a select; v likewise)
+ *     du*  = (b1 - A12 * dv + t_up + t_left + t_right + t_down) / (A11 + sigma);    du_new = du + omega * (du* - du)
+ *     ok_u = (A11 + sigma != 0) & isfinite(du_new)
+ *     dv*  = (b2 - A12 * (ok_u ? du* : du) + ...) / (A22 + sigma);    dv_new and ok_v likewise
+ *     du <- ok_u ? du_new : du;    dv <- ok_v ? dv_new : dv
+ *   A component whose denominator is 0 or whose new value is not finite stays as it is, so a NaN or Inf in an image or a
+ *   vector never spreads.  A pixel reads only its own values and the other colour's, so the result does not depend on how a
+ *   sweep is scheduled: the bits are reproducible.
+ * Finally out(q) = dom(q) ? (du != 0 ? u + du : u, dv != 0 ? v + dv : v) : flow(q): d = 0 keeps the bits of the input, the
+ * sign of a zero included.  The mask of the result is fmask.  tests/refine_ref.py restates all of this in NumPy.
+ *     alpha, delta finite and >= 0;  zeta, eps finite and > 0 with zeta2, eps2 finite and > 0;  fixed_point, sor in [1, 32];
+ *     omega in (0, 2).
+ *     Defaults of the Python layer: 20, 5, 0.1, 0.1, 5, 5, 1.6 -- eps is deliberately not Brox's 0.001, which makes a flat
+ *     field so stiff that 25 sweeps move it 1 % of the way.
+ *     out     float32 [N][H][W][2];   data  uint8 [N][H][W] or NULL: the data map
+ *     workspace  ofl_refine_workspace_bytes = 29 N H W (d, gx, gy, Iz, wD, s, flags), 8-byte aligned, caller-provided
+ * Launches: setup, then per iteration one for the weights and two per sweep, then one that writes out; no atomics, 64-bit
+ * offsets across items.  near / far aligned to their element, flow, out and workspace 8-byte, masks at any address.  out
+ * and the workspace must not overlap another argument.  A bad argument -- a NULL near / far / flow / fmask / out, another
+ * elem, layout or quant, C > 4, sizes out of range, sign not +-1, a parameter out of its range or not finite, an overlap, a
+ * misaligned pointer, a short workspace -- returns OFL_E_INVALID with a message before any launch.  The _dev entry is
+ * asynchronous; the host entry takes host pointers, uploads, launches, downloads and synchronises.
+ * Not built: the gradient-constancy term, per-channel data terms and C > 4, a loop over warps or a pyramid inside the call,
+ * image-driven (edge-aware) smoothness weights, a choice of omega, an energy read-back, a backward pass, mixed element types
+ * or layouts, several sweeps on one LDS tile.
+ */
+enum { OFL_REFINE_MAX_C = 4, OFL_REFINE_MAX_ITER = 32 };
+int ofl_refine_workspace_bytes(int N, int H, int W, size_t *bytes);
+int ofl_refine_dev(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                   const float *flow, const uint8_t *fmask, int sign,
+                   const uint8_t *near_mask, const uint8_t *far_mask, const uint8_t *valid,
+                   float alpha, float delta, float zeta, float eps, int fixed_point, int sor, float omega,
+                   void *workspace, size_t workspace_bytes, float *out, uint8_t *data, int quant, void *stream);
+int ofl_refine(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+               const float *flow, const uint8_t *fmask, int sign,
+               const uint8_t *near_mask, const uint8_t *far_mask, const uint8_t *valid,
+               float alpha, float delta, float zeta, float eps, int fixed_point, int sor, float omega,
+               float *out, uint8_t *data, int quant);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

@@ -31,6 +31,7 @@ SPLAT_SUM, SPLAT_AVERAGE, SPLAT_SOFTMAX = 0, 1, 2
 PHOTO_L1, PHOTO_L2, PHOTO_CHARBONNIER = 0, 1, 2
 CENSUS_HARD, CENSUS_SOFT = 0, 1
 CENSUS_MAX_C = 4
+REFINE_MAX_C, REFINE_MAX_ITER = 4, 32
 
 
 class MeshCert(ctypes.Structure):
@@ -175,6 +176,11 @@ SIGNATURES = {
                              _vp, _vp, _vp, _vp, _ci, _vp]),
     "ofl_census": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _ci, _cf, _cf, _ci, _cf,
                          _vp, _vp, _vp, _vp, _ci]),
+    "ofl_refine_workspace_bytes": (_ci, [_ci, _ci, _ci, ctypes.POINTER(_cs)]),
+    "ofl_refine_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _cf, _cf, _cf, _cf, _ci, _ci, _cf,
+                             _vp, _cs, _vp, _vp, _ci, _vp]),
+    "ofl_refine": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _cf, _cf, _cf, _cf, _ci, _ci, _cf,
+                         _vp, _vp, _ci]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

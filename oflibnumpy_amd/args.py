@@ -385,6 +385,54 @@ def census_channels(c):
     return c
 
 
+# -- variational refinement of a field on two images (K23)
+REFINE_DEFAULTS = dict(alpha=20.0, delta=5.0, zeta=0.1, eps=0.1, fixed_point=5, sor=5, omega=1.6)
+
+
+def refine_args(alpha=None, delta=None, zeta=None, eps=None, fixed_point=None, sor=None, omega=None):
+    """Validation of the settings of a variational refinement (K23) on the host before any device work -> (alpha, delta,
+    zeta, eps as float32, fixed_point, sor as int, omega as float32); None takes the default: 20, 5, 0.1, 0.1, 5, 5, 1.6.
+    alpha (smoothness weight), delta (data weight): finite and not negative; zeta (the normalisation of the data term), eps
+    (the Charbonnier constant): finite and positive, their float32 squares too; fixed_point, sor: integers 1 ... 32; omega
+    (the relaxation factor): in (0, 2).  A bool or a value of the wrong type is a TypeError, a value out of range or not
+    finite (as given, or once rounded to float32) a ValueError."""
+    prefix = "Error refining flow: "
+    given = dict(alpha=alpha, delta=delta, zeta=zeta, eps=eps, fixed_point=fixed_point, sor=sor, omega=omega)
+    out = {}
+    for name in ("alpha", "delta", "zeta", "eps", "omega"):
+        value = REFINE_DEFAULTS[name] if given[name] is None else given[name]
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise TypeError("{}{} must be a number or None, got {}".format(prefix, name, type(value).__name__))
+        with np.errstate(over='ignore', under='ignore'):
+            v32 = np.float32(float(value)) if abs(value) < 1e300 else np.float32(np.inf if value > 0 else -np.inf)
+            square = v32 * v32
+        if name == "omega":
+            if not 0 < v32 < 2:
+                raise ValueError("{}omega must lie in (0, 2), got {}".format(prefix, value))
+        elif name in ("zeta", "eps"):
+            if value != value or not np.isfinite(v32) or not v32 > 0 or not 0 < square < np.inf:
+                raise ValueError("{}{} must be finite and positive (its float32 square too), got {}".format(prefix, name, value))
+        elif value != value or value < 0 or not np.isfinite(v32):
+            raise ValueError("{}{} must be finite and not negative, got {}".format(prefix, name, value))
+        out[name] = v32
+    for name in ("fixed_point", "sor"):
+        value = REFINE_DEFAULTS[name] if given[name] is None else given[name]
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+            raise TypeError("{}{} must be an integer or None, got {}".format(prefix, name, type(value).__name__))
+        if not 1 <= value <= nat.REFINE_MAX_ITER:
+            raise ValueError("{}{} must be in [1, {}], got {}".format(prefix, name, nat.REFINE_MAX_ITER, value))
+        out[name] = int(value)
+    return out["alpha"], out["delta"], out["zeta"], out["eps"], out["fixed_point"], out["sor"], out["omega"]
+
+
+def refine_channels(c):
+    """The channel count of a variational refinement (K23): 1 ... 4, else a ValueError that names the limit."""
+    if not 1 <= c <= nat.REFINE_MAX_C:
+        raise ValueError("Error refining flow: the tensors need 1 to {} channels (grey, two-plane, RGB, RGBA), got {}"
+                         .format(nat.REFINE_MAX_C, c))
+    return c
+
+
 # -- an estimate against a ground truth (K14)
 ERROR_THRESHOLDS, ERROR_OUTLIER, ERROR_SPEED_EDGES = (1, 3, 5), (3, 0.05), (10, 40)     # px; KITTI's Fl rule; Sintel's speed bins
 

@@ -181,6 +181,27 @@ class DeviceFlowBatch:
         res = (err, covered) + ((within,) if within is not None else ())
         return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
 
+    def refine(self, near, far, alpha=None, delta=None, zeta=None, eps=None, fixed_point=None, sor=None, omega=None,
+               near_mask=None, far_mask=None, valid=None, return_data=False, quant=nat.QUANT_OPENCV):
+        """self[i].refine(item i of `near`, item i of `far`, ...) for every i in the SAME launches of K23
+        (DeviceFlow.refine): near, far DeviceTensors (n, C, H, W) of one layout and dtype with 1 to 4 channels, near_mask,
+        far_mask, valid uint8 DeviceBuffers [n][H][W] (per item) or None.  -> an unpacked DeviceFlowBatch of the same
+        length, shape, reference and masks; return_data appends the uint8 DeviceBuffer [n][H][W].  A packed batch is read
+        through its byte masks.  Nothing synchronises."""
+        prefix = "Error refining flow: "
+        settings = dev.refine_args(alpha, delta, zeta, eps, fixed_point, sor, omega)
+        near, far = dev.photometric_tensors(near, far, self.shape, batch=self.n, prefix=prefix)
+        dev.refine_channels(near.channels)
+        n_bytes = self.n * self.shape[0] * self.shape[1]
+        near_mask = dev.mask_buffer_arg(near_mask, n_bytes, prefix, "near_mask")
+        far_mask = dev.mask_buffer_arg(far_mask, n_bytes, prefix, "far_mask")
+        valid = dev.mask_buffer_arg(valid, n_bytes, prefix, "valid")
+        out, data = dev.refine_launch(near.buf, far.buf, near.dtype, near.layout, self.n, near.channels, self.shape, self.vecs,
+                                      self.mask, 1 if self.ref == 's' else -1, *settings, near_mask=near_mask, far_mask=far_mask,
+                                      valid=valid, want_data=bool(return_data), quant=quant)
+        b = DeviceFlowBatch.wrap(self.n, self.shape, self.ref, out, self.mask)
+        return (b, data) if return_data else b
+
     def error(self, gt, thresholds=None, outlier=None, speed_edges=None, use_est_mask=True, return_map=False, return_outliers=False):
         """self[i].error(gt[i], ...) for every i in ONE launch of K14 (DeviceFlow.error): `gt` a batch of the same length,
         shape and reference.  -> a DeviceFlowError whose read() gives a list of n FlowErrorStats (the one read-back, 96 bytes

@@ -17,12 +17,9 @@
 // There is no zero-flow short cut.  16-bit elements are widened exactly.
 //
 // One workgroup of 256 threads per tile of 64 x 16 pixels of one item (K16's shape), lanes along x.
-//   Staging  the (64 + 2r) x (16 + 2r) pixels of the tile and its halo are dealt to the threads, up to 7 each.  A thread first
-//            loads the flow vectors of all its pixels, then per pixel makes the tap and issues the C `near` and 4 C `far` loads
-//            and the mask loads together (unconditional, as in K21: a tap outside the frame reads element 0 and is replaced by
-//            0.0f) and stores A, B and member to LDS: two float planes and one byte plane, kept apart, so a wave reads 64
-//            consecutive words.  Both layouts go through ONE code path, as a pixel stride and a channel stride; the element
-//            type and `quant` are template arguments and end here.  The warped image is never written.
+//   Staging  stage_warped_tile (ofl_photo_dev.h, shared with K23): the (64 + 2r) x (16 + 2r) pixels of the tile and its halo are
+//            dealt to the threads, up to 7 each, and A, B and member go to LDS: two float planes and one byte plane, kept
+//            apart, so a wave reads 64 consecutive words.  The warped image is never written.
 //   Window   a thread owns 4 consecutive rows of one column.  It walks the K + 3 tile rows its four windows span once; of
 //            each it reads the K values of A, B and member into registers and adds that row's R_dy to every centre whose
 //            window holds the row -- ascending rows are ascending dy for each centre, so the stated order is kept -- which
@@ -85,63 +82,15 @@ template <int E, int QUANT, int K, int MODE>
 __global__ __launch_bounds__(256)
 void census_kernel(const CArgs a)
 {
-    typedef typename Elem<E>::T T;
-    constexpr int R = K / 2, TW = kTX + 2 * R, TH = kTY + 2 * R, NE = TW * TH, NIT = (NE + 255) / 256;
+    constexpr int R = K / 2, TW = kTX + 2 * R, TH = kTY + 2 * R, NE = TW * TH;
     __shared__ float   s_a[NE], s_b[NE];
     __shared__ uint8_t s_m[NE];
 
-    const int H = a.H, W = a.W, C = a.C;
+    const int H = a.H, W = a.W;
     const int n = blockIdx.z, x0 = blockIdx.x * kTX, y0 = blockIdx.y * kTY;
-    const size_t hw = (size_t)H * W, field = a.step * n;
+    const size_t hw = (size_t)H * W;
 
-    // ------------------------------------------------------------------------------------------ staging
-    {
-        const float *flow = a.flow + 2 * field;
-        float2 f[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {                  // entry i of the tile; the flow of pixel 0 where there is no pixel
-            const int i = threadIdx.x + 256 * it, ty = i / TW, tx = i - ty * TW, x = x0 - R + tx, y = y0 - R + ty;
-            const bool inside = i < NE && (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
-            f[it] = *reinterpret_cast<const float2 *>(flow + 2 * (inside ? (size_t)y * W + x : (size_t)0));
-        }
-        const T *fp = static_cast<const T *>(a.far) + (size_t)n * C * hw;        // element 0 of item n
-        const T *np = static_cast<const T *>(a.near) + (size_t)n * C * hw;
-        const size_t s_px = a.s_px, s_ch = a.s_ch;
-        const float inv_c = a.inv_c;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int i = threadIdx.x + 256 * it, ty = i / TW, tx = i - ty * TW, x = x0 - R + tx, y = y0 - R + ty;
-            if (i >= NE) break;
-            float A = 0.0f, B = 0.0f;
-            bool member = false;
-            if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) {
-                const size_t pix = (size_t)y * W + x;
-                const Tap tp = make_tap<QUANT>(map_coord(x, f[it].x, a.sign), map_coord(y, f[it].y, a.sign));
-                bool in[4];
-                int  off[4];
-                tap_frame(tp, H, W, in, off);
-                member = photo_covered(a.fmask, a.near_mask, a.far_mask, field, pix, tp, in, off);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (c >= C) break;                                      // uniform
-                    const T *s = fp + (size_t)c * s_ch;
-                    float v[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float t = Elem<E>::to_f32(s[(size_t)off[k] * s_px]);
-                        v[k] = in[k] ? t : 0.0f;
-                    }
-                    A = __fadd_rn(A, Elem<E>::to_f32(np[pix * s_px + (size_t)c * s_ch]));
-                    B = __fadd_rn(B, blend4(v[0], v[1], v[2], v[3], tp));
-                }
-                A = __fmul_rn(A, inv_c);
-                B = __fmul_rn(B, inv_c);
-            }
-            s_a[i] = A;
-            s_b[i] = B;
-            s_m[i] = member ? 1 : 0;
-        }
-    }
+    stage_warped_tile<E, QUANT, R, kTX, kTY>(a, n, x0, y0, s_a, s_b, s_m);           // ofl_photo_dev.h
     __syncthreads();
 
     // ------------------------------------------------------------------------------------------ window

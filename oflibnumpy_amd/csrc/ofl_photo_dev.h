@@ -1,7 +1,9 @@
-// ofl_photo_dev.h -- device helpers that K21 (ofl_photometric.hip) and K22 (ofl_census.hip) share: the frame test of a
-// tap, the `covered` rule of a pixel and the per-item counts of a workgroup.
+// ofl_photo_dev.h -- device helpers that K21 (ofl_photometric.hip), K22 (ofl_census.hip) and K23 (ofl_refine.hip) share: the
+// frame test of a tap, the `covered` rule of a pixel, the warp of a tile plus halo into LDS (K22, K23) and the per-item
+// counts of a workgroup.
 #pragma once
 #include "ofl_common.h"
+#include "ofl_elem.h"
 
 namespace ofl {
 
@@ -27,6 +29,68 @@ __device__ __forceinline__ bool photo_covered(const uint8_t *fmask, const uint8_
     bool cov = (blend4(m[0], m[1], m[2], m[3], tp) == 1.0f) & (fmask[field + pix] != 0);
     if (near_mask) cov &= near_mask[field + pix] != 0;
     return cov;
+}
+
+// K22's and K23's staging: one workgroup of 256 threads warps the TX x TY tile at (x0, y0) of item n and its halo of R pixels
+// into LDS -- entry i = ty * (TX + 2 R) + tx holds the pixel (x0 - R + tx, y0 - R + ty): A, the channel mean of `near`, B, that
+// of the warped `far` (sums from +0.0f in ascending c, times inv_c), and member = inside the frame & K21's covered; outside
+// the frame 0, 0 and 0.  The entries are dealt to the threads; a thread first loads the flow vectors of all its pixels, then
+// per pixel makes the tap and issues the C `near`, 4 C `far` and the mask loads together (unconditional, as in K21: a tap
+// outside the frame reads element 0 and is replaced by 0.0f).  Both layouts go through ONE code path, as a pixel stride and
+// a channel stride; the element type and `quant` are template arguments and end here.  The caller synchronises.
+// Args: near, far, flow, fmask, near_mask, far_mask, C (1 ... 4), H, W, sign, inv_c, step, s_px, s_ch (see K22's CArgs).
+template <int E, int QUANT, int R, int TX, int TY, class Args>
+__device__ __forceinline__ void stage_warped_tile(const Args &a, int n, int x0, int y0, float *s_a, float *s_b, uint8_t *s_m)
+{
+    typedef typename Elem<E>::T T;
+    constexpr int TW = TX + 2 * R, TH = TY + 2 * R, NE = TW * TH, NIT = (NE + 255) / 256;
+    const int H = a.H, W = a.W, C = a.C;
+    const size_t hw = (size_t)H * W, field = a.step * n;
+    const float *flow = a.flow + 2 * field;
+    float2 f[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {                  // entry i of the tile; the flow of pixel 0 where there is no pixel
+        const int i = threadIdx.x + 256 * it, ty = i / TW, tx = i - ty * TW, x = x0 - R + tx, y = y0 - R + ty;
+        const bool inside = i < NE && (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
+        f[it] = *reinterpret_cast<const float2 *>(flow + 2 * (inside ? (size_t)y * W + x : (size_t)0));
+    }
+    const T *fp = static_cast<const T *>(a.far) + (size_t)n * C * hw;        // element 0 of item n
+    const T *np = static_cast<const T *>(a.near) + (size_t)n * C * hw;
+    const size_t s_px = a.s_px, s_ch = a.s_ch;
+    const float inv_c = a.inv_c;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int i = threadIdx.x + 256 * it, ty = i / TW, tx = i - ty * TW, x = x0 - R + tx, y = y0 - R + ty;
+        if (i >= NE) break;
+        float A = 0.0f, B = 0.0f;
+        bool member = false;
+        if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) {
+            const size_t pix = (size_t)y * W + x;
+            const Tap tp = make_tap<QUANT>(map_coord(x, f[it].x, a.sign), map_coord(y, f[it].y, a.sign));
+            bool in[4];
+            int  off[4];
+            tap_frame(tp, H, W, in, off);
+            member = photo_covered(a.fmask, a.near_mask, a.far_mask, field, pix, tp, in, off);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (c >= C) break;                                      // uniform
+                const T *s = fp + (size_t)c * s_ch;
+                float v[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float t = Elem<E>::to_f32(s[(size_t)off[k] * s_px]);
+                    v[k] = in[k] ? t : 0.0f;
+                }
+                A = __fadd_rn(A, Elem<E>::to_f32(np[pix * s_px + (size_t)c * s_ch]));
+                B = __fadd_rn(B, blend4(v[0], v[1], v[2], v[3], tp));
+            }
+            A = __fmul_rn(A, inv_c);
+            B = __fmul_rn(B, inv_c);
+        }
+        s_a[i] = A;
+        s_b[i] = B;
+        s_m[i] = member ? 1 : 0;
+    }
 }
 
 // the covered and within pixels of this wave (n_cov, n_wi: wave-uniform) -> the block's two counts -> at most one atomicAdd

@@ -33,7 +33,8 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rul
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
                    consistency_args, error_args, fill_args, median_args, upsample_args, upsample_weights_array, corr_args,
                    corr_host_array, optional_bool, mask_array_arg, match_args, match_host_array, splat_args, splat_host_array,
-                   splat_importance_array, photometric_args, photometric_host_array, census_args, census_channels)
+                   splat_importance_array, photometric_args, photometric_host_array, census_args, census_channels,
+                   refine_args, refine_channels)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
@@ -41,7 +42,8 @@ from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stat
                       tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
                       FlowErrorStats, fill_launch, fill_host, median_launch, median_host, upsample_launch,
                       upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host, match_launch, match_host, splat_launch, splat_host,
-                      photometric_launch, photometric_host, census_launch, census_host)
+                      photometric_launch, photometric_host, census_launch, census_host,
+                      refine_launch, refine_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -769,6 +771,39 @@ class DeviceFlow:
         if return_counts:
             res += ([(int(a), int(b)) for a, b in counts.to_host((near.n, 2), np.uint32)],)
         return res
+
+    def refine(self, near, far, alpha=None, delta=None, zeta=None, eps=None, fixed_point=None, sor=None, omega=None,
+               near_mask=None, far_mask=None, valid=None, return_data=False, quant=nat.QUANT_OPENCV):
+        """This field moved a fraction of a pixel towards where the two images say it belongs: the variational refinement
+        of Brox et al. without the gradient-constancy term (K23, include/ofl.h), the step that classical pipelines put
+        after matching, `fill` and `median`.  `far` is warped once where this field points (photometric's taps, blend and
+        `covered`; channel means as in census) and the increment d of
+            sum data * (delta / n) * psi(r^2 / n) + alpha * sum psi(|grad(u + du)|^2 + |grad(v + dv)|^2),  psi(s^2) = sqrt(s^2 + eps^2)
+        with r = Iz + gx du + gy dv, n = gx^2 + gy^2 + zeta^2, is found by `fixed_point` lagged-weight updates of `sor`
+        red-black SOR sweeps with relaxation `omega`; None takes the defaults 20, 5, 0.1, 0.1, 5, 5, 1.6.  One linearisation:
+        call refine again to re-warp.  The domain is self.mask & valid (a uint8 DeviceBuffer [H][W] or None) & finite
+        vectors; a pixel outside it keeps its vector bit for bit and is nobody's neighbour; the data term acts where the
+        pixel and its 4-neighbours are covered.  near, far, near_mask, far_mask, quant: as in census, one item
+        ((C, H, W) or (1, C, H, W)), 1 to 4 channels.  Works for 's' and 't' fields; no zero-flow short cut; every operation
+        float32 in a stated order, so the bits are reproducible.
+        -> a DeviceFlow of the same shape, reference and mask; return_data appends the uint8 DeviceBuffer [H][W] of the
+        pixels with a data term.  Nothing synchronises.  Not built: gradient constancy, per-channel data terms, more than 4
+        channels, a loop over warps or a pyramid, edge-aware smoothness, a choice of omega, an energy read-back, a backward
+        pass, mixed dtypes or layouts.  The inputs are not modified."""
+        prefix = "Error refining flow: "
+        settings = refine_args(alpha, delta, zeta, eps, fixed_point, sor, omega)
+        near, far = photometric_tensors(near, far, self.shape, prefix=prefix)
+        refine_channels(near.channels)
+        if near.n != 1:
+            raise ValueError("{}one field takes tensors of shape (C, H, W) or (1, C, H, W), got {}".format(prefix, near.shape))
+        near_mask = mask_buffer_arg(near_mask, self.n_px, prefix, "near_mask")
+        far_mask = mask_buffer_arg(far_mask, self.n_px, prefix, "far_mask")
+        valid = mask_buffer_arg(valid, self.n_px, prefix, "valid")
+        out, data = refine_launch(near.buf, far.buf, near.dtype, near.layout, 1, near.channels, self.shape, self.vecs, self.mask,
+                                  1 if self.ref == 's' else -1, *settings, near_mask=near_mask, far_mask=far_mask, valid=valid,
+                                  want_data=bool(return_data), quant=quant)
+        res = DeviceFlow(out, self.mask, self.shape, self.ref)          # buffers are immutable: the mask is shared
+        return (res, data) if return_data else res
 
     def error(self, gt, thresholds=None, outlier=None, speed_edges=None, use_est_mask=True, return_map=False, return_outliers=False):
         """How far this (estimated) field is from the ground truth `gt`, a DeviceFlow of the same shape and reference, in one

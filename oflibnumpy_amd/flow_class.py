@@ -489,6 +489,40 @@ class Flow(object):
                               near_mask=near_mask, far_mask=far_mask, quant=quant)
         return res if batched else tuple(r[0] for r in res)
 
+    def refine(self, near: np.ndarray, far: np.ndarray, alpha: float = None, delta: float = None, zeta: float = None,
+               eps: float = None, fixed_point: int = None, sor: int = None, omega: float = None,
+               near_mask: np.ndarray = None, far_mask: np.ndarray = None, valid: np.ndarray = None, return_data: bool = False,
+               layout: str = 'hwc', quant: int = 0):
+        """This flow moved a fraction of a pixel towards where the two images say it belongs: the variational refinement of
+        Brox et al. without the gradient-constancy term, the last step of EpicFlow, DeepFlow, RICFlow and DIS -- one warp
+        of `far`, `fixed_point` lagged-weight updates of `sor` red-black SOR sweeps with relaxation `omega`, smoothness
+        weight `alpha`, data weight `delta`, normalisation `zeta`, Charbonnier constant `eps` (None: 20, 5, 0.1, 0.1, 5, 5,
+        1.6).  Call it again to re-warp.  near, far: arrays as in census (one item, 1 to 4 channels, uint8 images
+        included); near_mask, far_mask, valid: bool or uint8 (H, W) arrays or None; vectors where the mask or `valid` is
+        unset, or that are not finite, come back unchanged.  -> a Flow of the same reference and mask, plus the bool (H, W)
+        array of the pixels with a data term with `return_data`.  The definition is DeviceFlow.refine's.  One upload, the
+        launches, one download."""
+        prefix = "Error refining flow: "
+        settings = dev.refine_args(alpha, delta, zeta, eps, fixed_point, sor, omega)
+        near, far = dev.photometric_host_array(near, layout, "near", prefix), dev.photometric_host_array(far, layout, "far", prefix)
+        if near.shape != far.shape:
+            raise ValueError("{}the arrays need the same shape, got {} and {}".format(prefix, near.shape, far.shape))
+        if near.dtype != far.dtype:
+            raise TypeError("{}the arrays need the same dtype, got {} and {}".format(prefix, near.dtype, far.dtype))
+        n, c, h, w, batched = dev.tensor_args(dev.tensor_logical_shape(near.shape, layout), layout, near.dtype.name)
+        dev.refine_channels(c)
+        if n != 1:
+            raise ValueError("{}one flow takes one item, got {}".format(prefix, n))
+        if (h, w) != tuple(self.shape):
+            raise ValueError("{}arrays and flow need the same height and width, got {} and {}".format(prefix, (h, w), tuple(self.shape)))
+        near_mask = None if near_mask is None else dev.mask_array_arg(near_mask, self.shape, prefix, "near_mask")
+        far_mask = None if far_mask is None else dev.mask_array_arg(far_mask, self.shape, prefix, "far_mask")
+        valid = None if valid is None else dev.mask_array_arg(valid, self.shape, prefix, "valid")
+        vecs, data = dev.refine_host(near, far, layout, 1, c, self._vecs, self._mask, 1 if self._ref == 's' else -1, *settings,
+                                     near_mask=near_mask, far_mask=far_mask, valid=valid, want_data=bool(return_data), quant=quant)
+        out = Flow(vecs[0], self._ref, self._mask.copy())
+        return (out, data[0]) if return_data else out
+
     def error(self, gt: FlowAlias, thresholds=None, outlier=None, speed_edges=None, use_est_mask: bool = None,
               return_map: bool = None):
         """How far this (estimated) flow is from the ground truth `gt`, a flow of the same shape and reference: the

@@ -11,7 +11,8 @@ from .flow_class import Flow
 nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
            'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow',
-           'upsample_flow_convex', 'correlation_lookup', 'global_match', 'splat_flow', 'photometric_error', 'census_error']
+           'upsample_flow_convex', 'correlation_lookup', 'global_match', 'splat_flow', 'photometric_error', 'census_error',
+           'refine_flow']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -181,3 +182,15 @@ def census_error(flow: nd, near: nd, far: nd, ref: str = None, mask: nd = None, 
     return Flow(flow, ref, mask).census(near, far, window=window, mode=mode, delta=delta, noise=noise, knee=knee,
                                         min_count=min_count, threshold=threshold, near_mask=near_mask, far_mask=far_mask,
                                         layout=layout)
+
+
+def refine_flow(flow: nd, near: nd, far: nd, ref: str = None, mask: nd = None, alpha: float = None, delta: float = None,
+                zeta: float = None, eps: float = None, fixed_point: int = None, sor: int = None, omega: float = None,
+                near_mask: nd = None, far_mask: nd = None, valid: nd = None, layout: str = 'hwc', quant: int = 0) -> nd:
+    """The flow array `flow` (H, W, 2) with reference `ref` and mask `mask` (None: all valid) after one variational
+    refinement on `near`, the image of the flow's own frame, and `far`, that of the other frame -- Flow.refine: one warp,
+    `fixed_point` updates of `sor` red-black SOR sweeps; arrays (H, W), (H, W, C) or, with layout='chw', (C, H, W).
+    -> the refined float32 (H, W, 2) array."""
+    return Flow(flow, ref, mask).refine(near, far, alpha=alpha, delta=delta, zeta=zeta, eps=eps, fixed_point=fixed_point, sor=sor,
+                                        omega=omega, near_mask=near_mask, far_mask=far_mask, valid=valid, layout=layout,
+                                        quant=quant).vecs

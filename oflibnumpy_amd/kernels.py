@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching, K20 splatting, K21 photometric error and K22 census distance.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching, K20 splatting, K21 photometric error, K22 census distance and K23 variational refinement.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -657,3 +657,37 @@ def census_host(near, far, layout, n, c, vecs, mask, sign, window, mode, p0, p1,
                                 err.ctypes.data, covered.ctypes.data, _host_ptr(within), None, quant))
     res = (err, covered.view(np.bool_))
     return res + (within.view(np.bool_),) if within is not None else res
+
+
+# ------------------------------------------------------------------------------ K23: variational refinement of a field
+def refine_launch(near, far, dtype, layout, n, c, shape, flow, fmask, sign, alpha, delta, zeta, eps, fixed_point, sor, omega,
+                  near_mask=None, far_mask=None, valid=None, want_data=False, quant=nat.QUANT_OPENCV, stream=None):
+    """K23 (ofl_refine_dev) on `n` items of `c` channels (1 to 4) in `layout` ('chw' / 'hwc') of `dtype`, item i with field i:
+    flow, fmask, near_mask, far_mask, valid lie back to back, [n][H][W]; asynchronous: setup, fixed_point * (1 + 2 * sor)
+    solver launches, finish.  alpha ... omega: from args.refine_args.  The workspace comes from the buffer pool and goes back
+    to it on return (one stream).  -> (vecs float32 [n][H][W][2], data uint8 [n][H][W] or None), still in HBM."""
+    lib, (h, w) = _lib(), shape
+    nbytes = _size_query(lib.ofl_refine_workspace_bytes, n, h, w)
+    work = DeviceBuffer(nbytes)
+    out = DeviceBuffer(n * h * w * 8)
+    data = DeviceBuffer(n * h * w) if want_data else None
+    nat.check(lib.ofl_refine_dev(near.ptr, far.ptr, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, h, w, flow.ptr, fmask.ptr, sign,
+                                 _ptr(near_mask), _ptr(far_mask), _ptr(valid), alpha, delta, zeta, eps, fixed_point, sor, omega,
+                                 work.ptr, nbytes, out.ptr, _ptr(data), quant, stream))
+    return out, data
+
+
+def refine_host(near, far, layout, n, c, vecs, mask, sign, alpha, delta, zeta, eps, fixed_point, sor, omega, near_mask=None,
+                far_mask=None, valid=None, want_data=False, quant=nat.QUANT_OPENCV):
+    """K23 for host arrays through ofl_refine (upload, launches, download): near, far as in photometric_host, vecs
+    (n, H, W, 2) or (H, W, 2) with n = 1, and the masks uint8 of n * H * W bytes or None -> (vecs float32 (n, H, W, 2),
+    data bool (n, H, W) or None)."""
+    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(mask)
+    h, w = vecs.shape[-3:-1]
+    out = np.empty((n, h, w, 2), np.float32)
+    data = np.empty((n, h, w), np.uint8) if want_data else None
+    nat.check(_lib().ofl_refine(near.ctypes.data, far.ctypes.data, _TENSOR_EL[near.dtype.name], _TENSOR_LAYOUT[layout],
+                                n, c, h, w, vecs.ctypes.data, m.ctypes.data, sign, _host_ptr(near_mask), _host_ptr(far_mask),
+                                _host_ptr(valid), alpha, delta, zeta, eps, fixed_point, sor, omega,
+                                out.ctypes.data, _host_ptr(data), quant))
+    return out, None if data is None else data.view(np.bool_)
