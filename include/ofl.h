@@ -677,6 +677,11 @@ int ofl_permute_image_dev(const void *src, void *dst, int elem_bytes, int C, int
  *   ofl_tensor_import_dev   a strided view -- element strides (item, channel, row, column) >= 0, elements of 2 or 4 bytes
  *                           that move unchanged -- into a contiguous dst of `layout`.
  *   ofl_tensor_permute_dev  contiguous (N, C, H, W) -> (N, H, W, C) with to_nhwc != 0, else the way back; any C.
+ *   ofl_tensor_halve_dev    the 2 x 2 mean of a tensor of either layout and of OFL_EL_F32 / F16 / BF16 -> dst of the same
+ *                           layout and element with H >> 1 rows and W >> 1 columns: ((tl + tr) + (bl + br)) * 0.25f in
+ *                           float32, rounded once to the element (K18's ofl_avgpool2_dev arithmetic); an odd last row or
+ *                           column is dropped; H or W < 2 is refused; dst must not overlap src.  One level of the image
+ *                           pyramid of estimate_flow (K24).
  */
 enum { OFL_TENSOR_NCHW = 0, OFL_TENSOR_NHWC = 1 };
 int ofl_gather_tensor_dev(const void *src, int elem, int layout, int N, int C, int H, int W,
@@ -686,6 +691,7 @@ int ofl_gather_tensor_dev(const void *src, int elem, int layout, int N, int C, i
 int ofl_tensor_import_dev(const void *src, int elem_bytes, int64_t s_item, int64_t s_chan, int64_t s_row, int64_t s_col,
                           int layout, int N, int C, int H, int W, void *dst, void *stream);
 int ofl_tensor_permute_dev(const void *src, void *dst, int elem_bytes, int N, int C, int H, int W, int to_nhwc, void *stream);
+int ofl_tensor_halve_dev(const void *src, int elem, int layout, int N, int C, int H, int W, void *dst, void *stream);
 
 /* ------------------------------------------------------------------ K13: forward-backward consistency of two fields
  * The check between "two fields come out of a network" and "warp with them": sample the backward field b where the
@@ -1248,6 +1254,73 @@ int ofl_refine(const void *near, const void *far, int elem, int layout, int N, i
                const uint8_t *near_mask, const uint8_t *far_mask, const uint8_t *valid,
                float alpha, float delta, float zeta, float eps, int fixed_point, int sor, float omega,
                float *out, uint8_t *data, int quant);
+
+/* ------------------------------------------------------------------ K24: dense inverse search of a field on two images
+ * K23 moves a vector a fraction of a pixel; K24 finds it: the patch inverse search and the densification of Dense Inverse
+ * Search (Kroeger et al., ECCV 2016; OpenCV's DISOpticalFlow).  Every patch of P x P pixels on a grid of stride S takes
+ * `iterations` inverse-compositional Lucas-Kanade translation steps from the vector of `flow` at its centre, then every
+ * pixel takes the weighted average of the patches that cover it.  There is NO zero-flow short cut.
+ *     near, far, elem, layout, C in [1, 4], H, W, sign, quant: K22's;  N items, fields and fmasks lie back to back
+ *     flow  float32 [N][H][W][2] or NULL: the zero field (fmask is then not read);  fmask uint8 [N][H][W] or NULL: all set
+ * Every operation is float32 and rounded once (no FMA); every division is the correctly rounded one; a sum written
+ * a + b + c is (a + b) + c.  ex = (1, 0), ey = (0, 1), PP = P * P.
+ * Setup, per item and pixel q:
+ *     A(q), Bm(q)  K22's channel means of `near` and of the UNWARPED `far` (ascending c from +0.0f, times (float)(1.0 / C)),
+ *                  two float32 planes in the workspace: the mean first, the blend later, so a tap costs the same for any C
+ *     Ax = 0.5f * (A(q + ex) - A(q - ex)),  Ay = 0.5f * (A(q + ey) - A(q - ey));  a neighbour outside the frame is replaced
+ *                  by q itself (K23's rule);   gx = sign > 0 ? Ax : -Ax,  gy likewise
+ * Patch grid: along an axis of length n the origins are 0, S, 2 S, ... <= n - P, and one more at n - P where the last of
+ *     them is not n - P, so every pixel lies in a patch;  origin(i) = min(i S, n - P);  ny x nx patches in row-major order.
+ * Sample: S(q, u) = the bilinear blend of Bm at the position (K12's map_coord of q and u under `sign`) clamped
+ *     componentwise to [0, W - 1] x [0, H - 1]; taps and weights are K21's for that position under `quant`, the blend is
+ *     K12's v00 w0 + v01 w1 + v10 w2 + v11 w3.  After the clamp only a tap at column W or row H can lie outside the frame:
+ *     it counts as +0.0f, K21's rule, and its weight is 0.
+ * Tree sum over a patch: the PP values in row-major patch order, added pairwise x[2i] + x[2i + 1], level by level,
+ *     log2(PP) levels.  Float addition is commutative, so an xor butterfly across lanes gives these bits in every lane.
+ * Per patch with origin (ox, oy), pixels q of the patch:
+ *     u0   = the vector of `flow` at (ox + P / 2, oy + P / 2) if fmask is set there and both components are finite, else
+ *            (+0.0f, +0.0f)
+ *     T    = normalise ? A - (sum A) * (1 / PP) : A
+ *     H11  = sum gx * gx,  H12 = sum gx * gy,  H22 = sum gy * gy,  det = H11 * H22 - H12 * H12
+ *     r(u) = (normalise ? S(q, u) - (sum S) * (1 / PP) : S(q, u)) - T,   ssd(u) = sum r * r
+ *     best = ssd(u0), +Inf if that is not finite;  ubest = u = u0
+ *     if det is finite and > 0, `iterations` times:
+ *         b1 = sum r * gx,  b2 = sum r * gy;   du = (H22 * b1 - H12 * b2) / det,  dv = (H11 * b2 - H12 * b1) / det
+ *         u' = (u.x - du, u.y - dv);  e = u' - u0
+ *         stop if a component of u' is not finite or e.x * e.x + e.y * e.y > PP
+ *         u <- u';  r and ssd at u;  if ssd < best (a NaN never wins): best <- ssd, ubest <- u
+ *     patch_vecs = ubest,  patch_ssd = best
+ *   A flat or NaN-ridden patch therefore returns u0 bit for bit, and ubest never lies farther than P from u0.
+ * Densify, per pixel q, the patches p that contain q in row-major grid order, u_p = patch_vecs(p):
+ *     d   = |S(q, u_p) - A(q)|   (raw intensities, as OpenCV takes them);   w_p = 1 / (d < floor ? floor : d): a NaN
+ *           difference is a NaN weight
+ *     out = ((+0 + w_1 u_1.x + ...) / (+0 + w_1 + ...),  likewise y);  out_mask = both components finite; else the vector
+ *           is (+0.0f, +0.0f) and the mask 0.  A NaN poisons only the pixels of the patches it touches.
+ *     patch P in {4, 8};  stride S in [1, P];  iterations in [1, 32];  floor finite and > 0 (the Python layer's default 1.0
+ *     is meant for intensities 0 ... 255);  H >= P and W >= P
+ *     out float32 [N][H][W][2], out_mask uint8 [N][H][W];  patch_vecs float32 [N][ny][nx][2], patch_ssd float32 [N][ny][nx],
+ *     each or NULL;  workspace: 8 N H W bytes, plus 12 bytes per patch unless both patch buffers are given;
+ *     ofl_inverse_search_workspace_bytes returns the larger figure.  8-byte aligned, caller-provided.
+ * Three launches: setup (one thread per pixel), search (one wave per 8 x 8 patch, four 4 x 4 patches a wave; the sums cross
+ * lanes, no LDS, 12 bytes written per patch), densify (one thread per pixel); no atomics, 64-bit offsets across items.
+ * near / far aligned to their element, flow, out, patch_vecs and the workspace 8-byte, patch_ssd 4-byte.  The outputs and
+ * the workspace must not overlap each other or an input.  A bad argument -- a NULL near / far / out / out_mask, another
+ * elem, layout or quant, C > 4, sizes out of range, sign not +-1, a parameter out of its range or not finite, an overlap,
+ * a misaligned pointer, a short workspace -- returns OFL_E_INVALID with a message before any launch.  The _dev entry is
+ * asynchronous; the host entry takes host pointers, uploads, launches, downloads and synchronises.
+ * Not built: OpenCV's spatial propagation between neighbouring patches and its early exits, patches of 12 / 16 px,
+ * per-channel residuals and C > 4, near_mask / far_mask, affine patch models, a pyramid or a fused multi-level launch (the
+ * Python layer's estimate_flow loops over halved levels), a backward pass.
+ */
+enum { OFL_ISEARCH_MAX_C = 4, OFL_ISEARCH_MAX_ITER = 32 };
+int ofl_inverse_search_workspace_bytes(int N, int H, int W, int patch, int stride, size_t *bytes);
+int ofl_inverse_search_dev(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                           const float *flow, const uint8_t *fmask, int sign, int patch, int stride, int iterations,
+                           int normalise, float floor, void *workspace, size_t workspace_bytes,
+                           float *out, uint8_t *out_mask, float *patch_vecs, float *patch_ssd, int quant, void *stream);
+int ofl_inverse_search(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                       const float *flow, const uint8_t *fmask, int sign, int patch, int stride, int iterations,
+                       int normalise, float floor, float *out, uint8_t *out_mask, float *patch_vecs, float *patch_ssd, int quant);
 
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`

@@ -32,6 +32,7 @@ PHOTO_L1, PHOTO_L2, PHOTO_CHARBONNIER = 0, 1, 2
 CENSUS_HARD, CENSUS_SOFT = 0, 1
 CENSUS_MAX_C = 4
 REFINE_MAX_C, REFINE_MAX_ITER = 4, 32
+ISEARCH_MAX_C, ISEARCH_MAX_ITER = 4, 32
 
 
 class MeshCert(ctypes.Structure):
@@ -146,6 +147,7 @@ SIGNATURES = {
     "ofl_gather_tensor_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _ci, _vp]),
     "ofl_tensor_import_dev": (_ci, [_vp, _ci, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
     "ofl_tensor_permute_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "ofl_tensor_halve_dev": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp]),
     "ofl_consistency_dev": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp, _ci, _vp]),
     "ofl_consistency": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp, _ci]),
     "ofl_flow_error_workspace_bytes": (_ci, [_ci, _ci, _ci, ctypes.POINTER(_cs)]),
@@ -181,6 +183,11 @@ SIGNATURES = {
                              _vp, _cs, _vp, _vp, _ci, _vp]),
     "ofl_refine": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _cf, _cf, _cf, _cf, _ci, _ci, _cf,
                          _vp, _vp, _ci]),
+    "ofl_inverse_search_workspace_bytes": (_ci, [_ci, _ci, _ci, _ci, _ci, ctypes.POINTER(_cs)]),
+    "ofl_inverse_search_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cf, _vp, _cs,
+                                     _vp, _vp, _vp, _vp, _ci, _vp]),
+    "ofl_inverse_search": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cf,
+                                 _vp, _vp, _vp, _vp, _ci]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

@@ -433,6 +433,85 @@ def refine_channels(c):
     return c
 
 
+# -- dense inverse search of a field on two images (K24) and the coarse-to-fine estimator on top of it
+ISEARCH_PATCHES = (4, 8)
+ESTIMATE_MAX_LEVELS = 6
+
+
+def inverse_search_args(patch=8, stride=4, iterations=12, normalise=True, floor=1.0):
+    """Validation of the settings of a dense inverse search (K24) on the host before any device work -> (patch, stride,
+    iterations as int, normalise as bool, floor as float32).  patch: 4 or 8; stride: an integer 1 ... patch; iterations: an
+    integer 1 ... 32; normalise: a bool (subtract the patch means); floor: the smallest intensity difference a weight of the
+    densification divides by, finite and positive (1.0 is meant for intensities 0 ... 255).  A value of the wrong type is a
+    TypeError, a value out of range or not finite (as given, or once rounded to float32) a ValueError."""
+    prefix = "Error searching flow: "
+    for name, value in (("patch", patch), ("stride", stride), ("iterations", iterations)):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+            raise TypeError("{}{} must be an integer, got {}".format(prefix, name, type(value).__name__))
+    if patch not in ISEARCH_PATCHES:
+        raise ValueError("{}patch must be 4 or 8, got {}".format(prefix, patch))
+    if not 1 <= stride <= patch:
+        raise ValueError("{}stride must be in [1, patch = {}], got {}".format(prefix, patch, stride))
+    if not 1 <= iterations <= nat.ISEARCH_MAX_ITER:
+        raise ValueError("{}iterations must be in [1, {}], got {}".format(prefix, nat.ISEARCH_MAX_ITER, iterations))
+    if not isinstance(normalise, (bool, np.bool_)):
+        raise TypeError("{}normalise must be a bool, got {}".format(prefix, type(normalise).__name__))
+    if isinstance(floor, (bool, np.bool_)) or not isinstance(floor, (int, float, np.integer, np.floating)):
+        raise TypeError("{}floor must be a number, got {}".format(prefix, type(floor).__name__))
+    with np.errstate(over='ignore', under='ignore'):
+        f32 = np.float32(float(floor)) if abs(floor) < 1e300 else np.float32(np.inf if floor > 0 else -np.inf)
+    if floor != floor or not np.isfinite(f32) or not f32 > 0:
+        raise ValueError("{}floor must be finite and positive (as float32 too), got {}".format(prefix, floor))
+    return int(patch), int(stride), int(iterations), bool(normalise), f32
+
+
+def inverse_search_channels(c):
+    """The channel count of a dense inverse search (K24): 1 ... 4, else a ValueError that names the limit."""
+    if not 1 <= c <= nat.ISEARCH_MAX_C:
+        raise ValueError("Error searching flow: the tensors need 1 to {} channels (grey, two-plane, RGB, RGBA), got {}"
+                         .format(nat.ISEARCH_MAX_C, c))
+    return c
+
+
+def patch_origins(n, patch, stride):
+    """The origins of K24's patch grid along an axis of length n >= patch: 0, stride, 2 stride, ... <= n - patch, and n - patch
+    itself where the last of them is not, so every pixel lies in a patch."""
+    if n < patch:
+        raise ValueError("Error searching flow: an axis of {} pixels holds no patch of {}".format(n, patch))
+    origins = list(range(0, n - patch + 1, stride))
+    if origins[-1] != n - patch:
+        origins.append(n - patch)
+    return origins
+
+
+def estimate_levels(shape, levels=None, patch=8):
+    """The number of pyramid levels of estimate_flow for images of `shape` (H, W): with `levels` given, an integer 1 ... 6,
+    H and W must be divisible by 2^(levels - 1) and the coarsest level must measure at least 2 patch in both axes, else a
+    ValueError that names `pad`; None is the largest count <= 6 that meets both conditions (at least one level must)."""
+    prefix = "Error estimating flow: "
+    h, w = int(shape[0]), int(shape[1])
+
+    def fits(k):
+        f = 1 << (k - 1)
+        return h % f == 0 and w % f == 0 and h // f >= 2 * patch and w // f >= 2 * patch
+
+    if levels is None:
+        good = [k for k in range(1, ESTIMATE_MAX_LEVELS + 1) if fits(k)]
+        if not good:
+            raise ValueError("{}images of {} x {} are smaller than two patches of {}; pad them first (Flow.pad / np.pad)"
+                             .format(prefix, h, w, patch))
+        return good[-1]
+    if isinstance(levels, (bool, np.bool_)) or not isinstance(levels, (int, np.integer)):
+        raise TypeError("{}levels must be an integer or None, got {}".format(prefix, type(levels).__name__))
+    if not 1 <= levels <= ESTIMATE_MAX_LEVELS:
+        raise ValueError("{}levels must be in [1, {}], got {}".format(prefix, ESTIMATE_MAX_LEVELS, levels))
+    if not fits(int(levels)):
+        raise ValueError("{}{} levels need a height and width divisible by {} and a coarsest level of at least {} x {} pixels, "
+                         "got {} x {}; pad the images first (Flow.pad / np.pad) or take fewer levels"
+                         .format(prefix, levels, 1 << (levels - 1), 2 * patch, 2 * patch, h, w))
+    return int(levels)
+
+
 # -- an estimate against a ground truth (K14)
 ERROR_THRESHOLDS, ERROR_OUTLIER, ERROR_SPEED_EDGES = (1, 3, 5), (3, 0.05), (10, 40)     # px; KITTI's Fl rule; Sintel's speed bins
 

@@ -202,6 +202,25 @@ class DeviceFlowBatch:
         b = DeviceFlowBatch.wrap(self.n, self.shape, self.ref, out, self.mask)
         return (b, data) if return_data else b
 
+    def inverse_search(self, near, far, patch=8, stride=4, iterations=12, normalise=True, floor=1.0, return_patches=False,
+                       quant=nat.QUANT_EXACT):
+        """self[i].inverse_search(item i of `near`, item i of `far`, ...) for every i in the SAME launches of K24
+        (DeviceFlow.inverse_search): near, far DeviceTensors (n, C, H, W) of one layout and dtype with 1 to 4 channels.
+        -> an unpacked DeviceFlowBatch of the same length, shape and reference whose masks are K24's out_mask;
+        return_patches appends (patch_vecs float32 DeviceBuffer [n][ny][nx][2], patch_ssd float32 DeviceBuffer [n][ny][nx],
+        (ny, nx)).  A packed batch is read through its byte masks.  Nothing synchronises."""
+        prefix = "Error searching flow: "
+        settings = dev.inverse_search_args(patch, stride, iterations, normalise, floor)
+        near, far = dev.photometric_tensors(near, far, self.shape, batch=self.n, prefix=prefix)
+        dev.inverse_search_channels(near.channels)
+        if min(self.shape) < settings[0]:
+            raise ValueError("{}a {} x {} field holds no patch of {}".format(prefix, self.shape[0], self.shape[1], settings[0]))
+        out, mask, pv, ps, grid = dev.inverse_search_launch(near.buf, far.buf, near.dtype, near.layout, self.n, near.channels,
+                                                            self.shape, self.vecs, self.mask, 1 if self.ref == 's' else -1,
+                                                            *settings, want_patches=bool(return_patches), quant=quant)
+        b = DeviceFlowBatch.wrap(self.n, self.shape, self.ref, out, mask)
+        return (b, pv, ps, grid) if return_patches else b
+
     def error(self, gt, thresholds=None, outlier=None, speed_edges=None, use_est_mask=True, return_map=False, return_outliers=False):
         """self[i].error(gt[i], ...) for every i in ONE launch of K14 (DeviceFlow.error): `gt` a batch of the same length,
         shape and reference.  -> a DeviceFlowError whose read() gives a list of n FlowErrorStats (the one read-back, 96 bytes

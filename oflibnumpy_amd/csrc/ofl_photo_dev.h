@@ -1,6 +1,6 @@
-// ofl_photo_dev.h -- device helpers that K21 (ofl_photometric.hip), K22 (ofl_census.hip) and K23 (ofl_refine.hip) share: the
-// frame test of a tap, the `covered` rule of a pixel, the warp of a tile plus halo into LDS (K22, K23) and the per-item
-// counts of a workgroup.
+// ofl_photo_dev.h -- device helpers that K21 (ofl_photometric.hip), K22 (ofl_census.hip), K23 (ofl_refine.hip) and K24
+// (ofl_inverse_search.hip) share: the frame test of a tap, the `covered` rule of a pixel, the channel mean of a pixel (K24),
+// the warp of a tile plus halo into LDS (K22, K23) and the per-item counts of a workgroup.
 #pragma once
 #include "ofl_common.h"
 #include "ofl_elem.h"
@@ -29,6 +29,22 @@ __device__ __forceinline__ bool photo_covered(const uint8_t *fmask, const uint8_
     bool cov = (blend4(m[0], m[1], m[2], m[3], tp) == 1.0f) & (fmask[field + pix] != 0);
     if (near_mask) cov &= near_mask[field + pix] != 0;
     return cov;
+}
+
+// K22's channel mean of ONE unwarped pixel, for K24's planes: the C values (1 ... 4) of pixel `pix` of the item whose element 0
+// is `base`, added in ascending c from +0.0f, times inv_c -- the A of stage_warped_tile below
+template <int E>
+__device__ __forceinline__ float channel_mean(const void *tensor, size_t base, size_t pix, size_t s_px, size_t s_ch, int C, float inv_c)
+{
+    typedef typename Elem<E>::T T;
+    const T *p = static_cast<const T *>(tensor) + base + pix * s_px;
+    float m = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (c >= C) break;                                              // uniform
+        m = __fadd_rn(m, Elem<E>::to_f32(p[(size_t)c * s_ch]));
+    }
+    return __fmul_rn(m, inv_c);
 }
 
 // K22's and K23's staging: one workgroup of 256 threads warps the TX x TY tile at (x0, y0) of item n and its halo of R pixels

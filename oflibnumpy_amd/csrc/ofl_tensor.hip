@@ -227,6 +227,26 @@ void tensor_transpose_kernel(const T *__restrict__ src, T *__restrict__ dst, uin
     }
 }
 
+// the 2 x 2 mean ((tl + tr) + (bl + br)) * 0.25f of a tensor seen as [M][H][W][K] -- planar: M = N C, K = 1; channels last:
+// M = N, K = C -- in float32, rounded once to the element type; one output element per thread and round, in memory order.
+// An odd last row or column is never read.
+template <int E>
+__global__ __launch_bounds__(256)
+void tensor_halve_kernel(const typename Elem<E>::T *__restrict__ src, typename Elem<E>::T *__restrict__ dst,
+                         uint32_t K, uint32_t H, uint32_t W, uint32_t Ho, uint32_t Wo, uint64_t total)
+{
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    const size_t right = K, down = (size_t)W * K;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const uint64_t p = div_u64(i, K), q = div_u64(p, Wo), m = div_u64(q, Ho);
+        const uint64_t k = i - p * K, xo = p - q * Wo, yo = q - m * Ho;
+        const typename Elem<E>::T *s = src + ((m * H + 2 * yo) * W + 2 * xo) * K + k;
+        const float tl = Elem<E>::to_f32(s[0]), tr = Elem<E>::to_f32(s[right]);
+        const float bl = Elem<E>::to_f32(s[down]), br = Elem<E>::to_f32(s[down + right]);
+        dst[i] = Elem<E>::from_f32(__fmul_rn(__fadd_rn(__fadd_rn(tl, tr), __fadd_rn(bl, br)), 0.25f));
+    }
+}
+
 int check_tensor_dims(const char *who, int N, int C, int H, int W)
 {
     if (N < 1 || N > 65535) return fail(OFL_E_INVALID, "%s: N must be in [1, 65535], got %d", who, N);
@@ -332,6 +352,33 @@ int ofl_tensor_permute_dev(const void *src, void *dst, int elem_bytes, int N, in
         hipLaunchKernelGGL((tensor_transpose_kernel<uint16_t>), grid, block, 0, s, static_cast<const uint16_t *>(src), static_cast<uint16_t *>(dst), R, K, (uint32_t)tiles_k);
     else
         hipLaunchKernelGGL((tensor_transpose_kernel<uint32_t>), grid, block, 0, s, static_cast<const uint32_t *>(src), static_cast<uint32_t *>(dst), R, K, (uint32_t)tiles_k);
+    OFL_HIP(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_tensor_halve_dev(const void *src, int elem, int layout, int N, int C, int H, int W, void *dst, void *stream)
+{
+    OFL_TRY(need_device());
+    if (!src || !dst) return fail(OFL_E_INVALID, "ofl_tensor_halve: NULL pointer");
+    if (elem != OFL_EL_F16 && elem != OFL_EL_BF16 && elem != OFL_EL_F32)
+        return fail(OFL_E_INVALID, "ofl_tensor_halve: elem must be OFL_EL_F16, OFL_EL_BF16 or OFL_EL_F32, got %d", elem);
+    if (layout != OFL_TENSOR_NCHW && layout != OFL_TENSOR_NHWC) return fail(OFL_E_INVALID, "ofl_tensor_halve: bad layout %d", layout);
+    OFL_TRY(check_tensor_dims("ofl_tensor_halve", N, C, H, W));
+    if (H < 2 || W < 2) return fail(OFL_E_INVALID, "ofl_tensor_halve: a %d x %d tensor has no 2 x 2 mean", H, W);
+    const unsigned eb = elem == OFL_EL_F32 ? 4 : 2;
+    if (!host_aligned(src, eb) || !host_aligned(dst, eb)) return fail(OFL_E_INVALID, "ofl_tensor_halve: src and dst must be aligned to the element size");
+    const uint32_t Ho = (uint32_t)H >> 1, Wo = (uint32_t)W >> 1, K = layout == OFL_TENSOR_NCHW ? 1u : (uint32_t)C;
+    const uint64_t total = (uint64_t)N * C * Ho * Wo;
+    if (overlap(dst, total * eb, src, (size_t)N * C * H * W * eb)) return fail(OFL_E_INVALID, "ofl_tensor_halve: dst must not overlap src");
+    const uint64_t nb = (total + 255) / 256;
+    const dim3 grid((unsigned)(nb < 0x7fffffffull ? nb : 0x7fffffffull)), block(256);
+    hipStream_t s = stream_of(stream);
+    if (elem == OFL_EL_F16)
+        hipLaunchKernelGGL((tensor_halve_kernel<OFL_EL_F16>), grid, block, 0, s, static_cast<const uint16_t *>(src), static_cast<uint16_t *>(dst), K, (uint32_t)H, (uint32_t)W, Ho, Wo, total);
+    else if (elem == OFL_EL_BF16)
+        hipLaunchKernelGGL((tensor_halve_kernel<OFL_EL_BF16>), grid, block, 0, s, static_cast<const uint16_t *>(src), static_cast<uint16_t *>(dst), K, (uint32_t)H, (uint32_t)W, Ho, Wo, total);
+    else
+        hipLaunchKernelGGL((tensor_halve_kernel<OFL_EL_F32>), grid, block, 0, s, static_cast<const float *>(src), static_cast<float *>(dst), K, (uint32_t)H, (uint32_t)W, Ho, Wo, total);
     OFL_HIP(hipGetLastError());
     return OFL_OK;
 }

@@ -34,7 +34,7 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rul
                    consistency_args, error_args, fill_args, median_args, upsample_args, upsample_weights_array, corr_args,
                    corr_host_array, optional_bool, mask_array_arg, match_args, match_host_array, splat_args, splat_host_array,
                    splat_importance_array, photometric_args, photometric_host_array, census_args, census_channels,
-                   refine_args, refine_channels)
+                   refine_args, refine_channels, inverse_search_args, inverse_search_channels, estimate_levels)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
@@ -43,7 +43,7 @@ from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stat
                       FlowErrorStats, fill_launch, fill_host, median_launch, median_host, upsample_launch,
                       upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host, match_launch, match_host, splat_launch, splat_host,
                       photometric_launch, photometric_host, census_launch, census_host,
-                      refine_launch, refine_host)
+                      refine_launch, refine_host, tensor_halve_launch, inverse_search_launch, inverse_search_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)
@@ -271,6 +271,16 @@ class DeviceTensor:
                              .format(self.layout, layout))
         buf = tensor_permute_launch(self.buf, self.dtype, self.n, self.channels, self.h, self.w, layout == 'hwc')
         return DeviceArray(buf, out_shape, _TENSOR_TYPESTR[self.dtype])
+
+    def halve(self):
+        """The next level of an image pyramid: the 2 x 2 mean ((tl + tr) + (bl + br)) * 0.25 of every channel, in float32,
+        rounded once to the dtype (ofl_tensor_halve_dev; K18's avgpool arithmetic) -> a DeviceTensor of shape
+        (..., H // 2, W // 2) in the same layout and dtype.  An odd last row or column is dropped; H or W below 2 is a
+        ValueError.  Asynchronous."""
+        if self.h < 2 or self.w < 2:
+            raise ValueError("Error halving tensor: a {} x {} tensor has no 2 x 2 mean".format(self.h, self.w))
+        buf = tensor_halve_launch(self.buf, self.dtype, self.layout, self.n, self.channels, self.h, self.w)
+        return DeviceTensor(buf, self.shape[:-2] + (self.h >> 1, self.w >> 1), self.dtype, self.layout)
 
     def correlation(self, other, flow=None, radius=4, levels=1, scale=None, order='xy', quant=nat.QUANT_EXACT):
         """The correlation of this tensor's features with those of `other` around every pixel, in one call:
@@ -805,6 +815,38 @@ class DeviceFlow:
         res = DeviceFlow(out, self.mask, self.shape, self.ref)          # buffers are immutable: the mask is shared
         return (res, data) if return_data else res
 
+    def inverse_search(self, near, far, patch=8, stride=4, iterations=12, normalise=True, floor=1.0, return_patches=False,
+                       quant=nat.QUANT_EXACT):
+        """The field the two images ask for near this one: the patch inverse search and the densification of Dense Inverse
+        Search (Kroeger et al., ECCV 2016; OpenCV's DISOpticalFlow; K24, include/ofl.h).  Every `patch` x `patch` window
+        (4 or 8) on a grid of `stride` (1 ... patch) starts from this field's vector at its centre (+0 where the mask is unset
+        or the vector not finite) and takes up to `iterations` (1 ... 32) inverse-compositional Lucas-Kanade translation
+        steps on the channel means of `near` and `far`, with the patch means subtracted if `normalise`; it keeps the best
+        step and never moves farther than `patch` pixels.  Every pixel then takes the average of the patches covering it,
+        weighted by 1 / max(floor, |far there - near|) (raw intensities: floor = 1.0 is meant for 0 ... 255).  near, far: as
+        in refine, one item ((C, H, W) or (1, C, H, W)), 1 to 4 channels, H and W at least `patch`.  Works for 's' and 't'
+        fields; no zero-flow short cut; every operation float32 in a stated order, every sum of a patch a fixed tree across
+        the lanes of a wave, so the bits are reproducible.  `quant` defaults to exact taps, as in correlation: the 1 / 32 px
+        tap grid of QUANT_OPENCV is a floor an iterative search cannot get below.
+        -> a DeviceFlow of the same shape and reference whose mask is set where the average is finite; return_patches appends
+        (patch_vecs float32 DeviceBuffer [ny][nx][2], patch_ssd float32 DeviceBuffer [ny][nx], (ny, nx)).  Nothing
+        synchronises.  Not built: OpenCV's propagation between neighbouring patches and its early exits, patches of 12 / 16
+        px, per-channel residuals and more than 4 channels, near_mask / far_mask, affine patches, a backward pass; the pyramid
+        is estimate_flow.  The inputs are not modified."""
+        prefix = "Error searching flow: "
+        settings = inverse_search_args(patch, stride, iterations, normalise, floor)
+        near, far = photometric_tensors(near, far, self.shape, prefix=prefix)
+        inverse_search_channels(near.channels)
+        if near.n != 1:
+            raise ValueError("{}one field takes tensors of shape (C, H, W) or (1, C, H, W), got {}".format(prefix, near.shape))
+        if min(self.shape) < settings[0]:
+            raise ValueError("{}a {} x {} field holds no patch of {}".format(prefix, self.shape[0], self.shape[1], settings[0]))
+        out, mask, pv, ps, grid = inverse_search_launch(near.buf, far.buf, near.dtype, near.layout, 1, near.channels, self.shape,
+                                                        self.vecs, self.mask, 1 if self.ref == 's' else -1, *settings,
+                                                        want_patches=bool(return_patches), quant=quant)
+        res = DeviceFlow(out, mask, self.shape, self.ref)
+        return (res, pv, ps, grid) if return_patches else res
+
     def error(self, gt, thresholds=None, outlier=None, speed_edges=None, use_est_mask=True, return_map=False, return_outliers=False):
         """How far this (estimated) field is from the ground truth `gt`, a DeviceFlow of the same shape and reference, in one
         launch of K14 (include/ofl.h) and without leaving HBM: per pixel epe = |self - gt| in float32 with one rounding per
@@ -1332,3 +1374,52 @@ class DeviceFlow:
         scatter_linear(self.vecs, sign, pm, None, 0, self.mask, h, w, None, None, valid, 0,
                        cert=self.mesh_cert(sign) if pm is None else None, drops_points=pm is not None)
         return valid
+
+
+# ------------------------------------------------------------------------------ a field out of two images
+def estimate_flow(near, far, ref='s', levels=None, patch=8, stride=4, iterations=12, refine=True, refine_args=None, init=None):
+    """The flow between two images, estimated on the device without a network: Dense Inverse Search (Kroeger et al., ECCV
+    2016; OpenCV's DISOpticalFlow) -- coarse to fine over a pyramid of 2 x 2 means (DeviceTensor.halve), at every level
+    DeviceFlow.inverse_search (K24) from the level above and, with `refine`, DeviceFlow.refine (K23; `refine_args`: a dict of
+    its settings or None), then resize(2) to the next level.  near: the image of the field's own frame, far: that of the
+    other frame -- DeviceTensors of one item ((C, H, W) or (1, C, H, W)) with 1 to 4 channels, one layout and dtype, or
+    float32 DeviceImages; intensities 0 ... 255 are what the defaults are meant for.  ref: 's' or 't'.  levels: 1 ... 6 or None,
+    the largest count <= 6 such that H and W are divisible by 2^(levels - 1) and the coarsest level measures at least 2 patch
+    in both axes; a count that does not meet both is a ValueError (pad the images first).  init: a DeviceFlow of the images'
+    shape and of `ref` to start from (resized to the coarsest level) or None, the zero field.
+    -> a DeviceFlow of the images' shape.  A plain loop over existing methods: no kernel of its own, nothing synchronises.
+    Not built: sizes that are not divisible (pad first), a fused multi-level launch, OpenCV's patch propagation, parity with
+    cv2.DISOpticalFlow itself."""
+    from .utils import get_valid_ref
+    prefix = "Error estimating flow: "
+    ref = get_valid_ref(ref)
+    for name, t in (("near", near), ("far", far)):
+        if not isinstance(t, (DeviceTensor, DeviceImage)):
+            raise TypeError("{}{} needs to be a DeviceTensor or a float32 DeviceImage, got {}".format(prefix, name, type(t).__name__))
+    shape = (near.h, near.w) if isinstance(near, DeviceTensor) else tuple(near.shape[:2])
+    near, far = photometric_tensors(near, far, shape, prefix=prefix)
+    inverse_search_channels(near.channels)
+    if near.n != 1:
+        raise ValueError("{}two images make one field: tensors of shape (C, H, W) or (1, C, H, W), got {}".format(prefix, near.shape))
+    settings = inverse_search_args(patch, stride, iterations)
+    levels = estimate_levels(shape, levels, settings[0])
+    if refine_args is not None and not isinstance(refine_args, dict):
+        raise TypeError("{}refine_args needs to be a dict or None, got {}".format(prefix, type(refine_args).__name__))
+    if init is not None and (not isinstance(init, DeviceFlow) or init.shape != shape or init.ref != ref):
+        raise ValueError("{}init needs to be a DeviceFlow of shape {} and reference '{}'".format(prefix, shape, ref))
+    pyramid = [(near, far)]
+    for _ in range(levels - 1):
+        pyramid.append((pyramid[-1][0].halve(), pyramid[-1][1].halve()))
+    coarse = (shape[0] >> (levels - 1), shape[1] >> (levels - 1))
+    if init is None:
+        flow = DeviceFlow.zero(coarse, ref)
+    else:
+        flow = init if levels == 1 else init.resize(1.0 / (1 << (levels - 1)))
+    for level in range(levels - 1, -1, -1):
+        a, b = pyramid[level]
+        flow = flow.inverse_search(a, b, patch=patch, stride=stride, iterations=iterations)
+        if refine:
+            flow = flow.refine(a, b, **(refine_args or {}))
+        if level:
+            flow = flow.resize(2)
+    return flow

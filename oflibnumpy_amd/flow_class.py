@@ -523,6 +523,39 @@ class Flow(object):
         out = Flow(vecs[0], self._ref, self._mask.copy())
         return (out, data[0]) if return_data else out
 
+    def inverse_search(self, near: np.ndarray, far: np.ndarray, patch: int = 8, stride: int = 4, iterations: int = 12,
+                       normalise: bool = True, floor: float = 1.0, return_patches: bool = False, layout: str = 'hwc',
+                       quant: int = 1):
+        """The flow the two images ask for near this one: the patch inverse search and the densification of Dense Inverse
+        Search (Kroeger et al., ECCV 2016; OpenCV's DISOpticalFlow).  Every `patch` x `patch` window (4 or 8) on a grid of
+        `stride` starts from this flow's vector at its centre (zero where the mask is unset or the vector not finite), takes
+        up to `iterations` Lucas-Kanade translation steps on the channel means of the images and keeps the best, at most
+        `patch` pixels away; every pixel then takes the average of the patches covering it, weighted by
+        1 / max(floor, intensity difference).  near, far: arrays as in refine (one item, 1 to 4 channels, uint8 images
+        included), at least `patch` high and wide.  -> a Flow of the same reference whose mask is set where the average is
+        finite, plus (patch_vecs (ny, nx, 2), patch_ssd (ny, nx), (ny, nx)) with `return_patches`.  The definition is
+        DeviceFlow.inverse_search's; the pyramid is estimate_flow.  One upload, three launches, one download."""
+        prefix = "Error searching flow: "
+        settings = dev.inverse_search_args(patch, stride, iterations, normalise, floor)
+        near, far = dev.photometric_host_array(near, layout, "near", prefix), dev.photometric_host_array(far, layout, "far", prefix)
+        if near.shape != far.shape:
+            raise ValueError("{}the arrays need the same shape, got {} and {}".format(prefix, near.shape, far.shape))
+        if near.dtype != far.dtype:
+            raise TypeError("{}the arrays need the same dtype, got {} and {}".format(prefix, near.dtype, far.dtype))
+        n, c, h, w, batched = dev.tensor_args(dev.tensor_logical_shape(near.shape, layout), layout, near.dtype.name)
+        dev.inverse_search_channels(c)
+        if n != 1:
+            raise ValueError("{}one flow takes one item, got {}".format(prefix, n))
+        if (h, w) != tuple(self.shape):
+            raise ValueError("{}arrays and flow need the same height and width, got {} and {}".format(prefix, (h, w), tuple(self.shape)))
+        if min(h, w) < settings[0]:
+            raise ValueError("{}a {} x {} flow holds no patch of {}".format(prefix, h, w, settings[0]))
+        vecs, mask, pv, ps, grid = dev.inverse_search_host(near, far, layout, 1, c, self._vecs, self._mask,
+                                                           1 if self._ref == 's' else -1, *settings,
+                                                           want_patches=bool(return_patches), quant=quant)
+        out = Flow(vecs[0], self._ref, mask[0])
+        return (out, pv[0], ps[0], grid) if return_patches else out
+
     def error(self, gt: FlowAlias, thresholds=None, outlier=None, speed_edges=None, use_est_mask: bool = None,
               return_map: bool = None):
         """How far this (estimated) flow is from the ground truth `gt`, a flow of the same shape and reference: the

@@ -12,7 +12,7 @@ nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
            'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow',
            'upsample_flow_convex', 'correlation_lookup', 'global_match', 'splat_flow', 'photometric_error', 'census_error',
-           'refine_flow']
+           'refine_flow', 'inverse_search_flow', 'estimate_flow', 'halve_tensor']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -194,3 +194,58 @@ def refine_flow(flow: nd, near: nd, far: nd, ref: str = None, mask: nd = None, a
     return Flow(flow, ref, mask).refine(near, far, alpha=alpha, delta=delta, zeta=zeta, eps=eps, fixed_point=fixed_point, sor=sor,
                                         omega=omega, near_mask=near_mask, far_mask=far_mask, valid=valid, layout=layout,
                                         quant=quant).vecs
+
+
+def inverse_search_flow(flow: nd, near: nd, far: nd, ref: str = None, mask: nd = None, patch: int = 8, stride: int = 4,
+                        iterations: int = 12, normalise: bool = True, floor: float = 1.0, layout: str = 'hwc',
+                        quant: int = 1) -> nd:
+    """The flow array `flow` (H, W, 2) with reference `ref` and mask `mask` (None: all valid) after one dense inverse search
+    on `near`, the image of the flow's own frame, and `far`, that of the other frame -- Flow.inverse_search: patches of
+    `patch` on a grid of `stride`, `iterations` Lucas-Kanade steps each, then the weighted average per pixel; arrays (H, W),
+    (H, W, C) or, with layout='chw', (C, H, W).  -> the float32 (H, W, 2) array; where the average is not finite it is 0."""
+    return Flow(flow, ref, mask).inverse_search(near, far, patch=patch, stride=stride, iterations=iterations, normalise=normalise,
+                                                floor=floor, layout=layout, quant=quant).vecs
+
+
+def estimate_flow(img1: nd, img2: nd, ref: str = 't', levels: int = None, patch: int = 8, stride: int = 4,
+                  iterations: int = 12, refine: bool = True, refine_args: dict = None, init: Union[Flow, nd] = None,
+                  layout: str = 'hwc') -> Flow:
+    """The flow from `img1` to `img2`, estimated without a network: Dense Inverse Search, coarse to fine over a pyramid of
+    2 x 2 means, with a variational refinement at every level (device.estimate_flow: K24 and K23 on the device, one upload
+    and one download).  img1, img2: arrays (H, W), (H, W, C) or, with layout='chw', (C, H, W) of uint8, float32 or float16
+    with 1 to 4 channels; intensities 0 ... 255 are what the defaults are meant for.  ref: 't' (vectors sit on the pixels of
+    img2) or 's' (on those of img1).  levels: 1 ... 6 or None for the largest count the size allows; H and W must be divisible
+    by 2^(levels - 1) and the coarsest level at least 2 patch wide and high, else a ValueError (pad first).  init: a Flow or
+    an (H, W, 2) array to start from, or None.  -> a Flow of reference `ref`."""
+    from . import device as dev
+    from .utils import get_valid_ref
+    prefix = "Error estimating flow: "
+    ref = get_valid_ref(ref)
+    a, b = dev.photometric_host_array(img1, layout, "img1", prefix), dev.photometric_host_array(img2, layout, "img2", prefix)
+    if a.shape != b.shape:
+        raise ValueError("{}the images need the same shape, got {} and {}".format(prefix, a.shape, b.shape))
+    if a.dtype != b.dtype:
+        raise TypeError("{}the images need the same dtype, got {} and {}".format(prefix, a.dtype, b.dtype))
+    n, c, h, w, batched = dev.tensor_args(dev.tensor_logical_shape(a.shape, layout), layout, a.dtype.name)
+    dev.inverse_search_channels(c)
+    if n != 1:
+        raise ValueError("{}two images make one flow, got {} items".format(prefix, n))
+    dev.estimate_levels((h, w), levels, dev.inverse_search_args(patch, stride, iterations)[0])
+    if init is not None:
+        init = init if isinstance(init, Flow) else Flow(init, ref)
+        if init.ref != ref or tuple(init.shape) != (h, w):
+            raise ValueError("{}init needs the shape {} and the reference '{}'".format(prefix, (h, w), ref))
+        init = dev.DeviceFlow.from_host(init.vecs, ref, init.mask)
+    near, far = (a, b) if ref == 's' else (b, a)
+    out = dev.estimate_flow(dev.DeviceTensor.from_host(near, layout), dev.DeviceTensor.from_host(far, layout), ref, levels,
+                            patch, stride, iterations, refine, refine_args, init)
+    vecs, mask = out.to_host()
+    return Flow(vecs, ref, mask)
+
+
+def halve_tensor(arr: nd, layout: str = 'chw') -> nd:
+    """The 2 x 2 mean of a float32 or float16 array in the memory order of `layout` -- (C, H, W) / (N, C, H, W) for 'chw',
+    (H, W, C) / (N, H, W, C) for 'hwc' --: ((tl + tr) + (bl + br)) * 0.25 in float32, rounded once to the dtype; an odd last
+    row or column is dropped (DeviceTensor.halve: one upload, one launch, one download)."""
+    from . import device as dev
+    return dev.DeviceTensor.from_host(arr, layout).halve().to_host()

@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching, K20 splatting, K21 photometric error, K22 census distance and K23 variational refinement.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching, K20 splatting, K21 photometric error, K22 census distance, K23 variational refinement and K24 dense inverse search.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -9,7 +9,7 @@ import numpy as np
 from . import _native as nat
 from .memory import DeviceBuffer, _BufferView, _lib, _ptr, _size_query
 from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _TENSOR_EL, _TENSOR_LAYOUT, percentile_ranks, resize_scales,
-                   resized_shape, mask_bytes, valid_mask_array)
+                   resized_shape, mask_bytes, valid_mask_array, patch_origins)
 
 
 def _host_ptr(a):
@@ -484,6 +484,14 @@ def tensor_permute_launch(src, dtype, n, c, h, w, to_hwc, stream=None):
     return dst
 
 
+def tensor_halve_launch(src, dtype, layout, n, c, h, w, stream=None):
+    """ofl_tensor_halve_dev: the 2 x 2 mean of a tensor of either layout -> a fresh buffer of the same layout and dtype with
+    h >> 1 rows and w >> 1 columns."""
+    dst = DeviceBuffer(n * c * (h >> 1) * (w >> 1) * _tensor_bytes(dtype))
+    nat.check(_lib().ofl_tensor_halve_dev(src.ptr, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, h, w, dst.ptr, stream))
+    return dst
+
+
 # ------------------------------------------------------------------------------ K18: on-demand correlation lookup
 def avgpool2_launch(src, dtype, n, c, h, w, stream=None):
     """ofl_avgpool2_dev: the 2 x 2 mean of a channels-last tensor [n][h][w][c] of `dtype` -> float32 [n][h >> 1][w >> 1][c]."""
@@ -691,3 +699,41 @@ def refine_host(near, far, layout, n, c, vecs, mask, sign, alpha, delta, zeta, e
                                 _host_ptr(valid), alpha, delta, zeta, eps, fixed_point, sor, omega,
                                 out.ctypes.data, _host_ptr(data), quant))
     return out, None if data is None else data.view(np.bool_)
+
+
+# ------------------------------------------------------------------------------ K24: dense inverse search of a field
+def inverse_search_launch(near, far, dtype, layout, n, c, shape, flow, fmask, sign, patch, stride, iterations, normalise, floor,
+                          want_patches=False, quant=nat.QUANT_EXACT, stream=None):
+    """K24 (ofl_inverse_search_dev) on `n` items of `c` channels (1 to 4) in `layout` ('chw' / 'hwc') of `dtype`, item i with
+    field i: flow and fmask lie back to back, [n][H][W], or are None (the zero field); asynchronous: setup, search, densify.
+    patch ... floor: from args.inverse_search_args.  The workspace comes from the buffer pool and goes back to it on return
+    (one stream).  -> (vecs float32 [n][H][W][2], mask uint8 [n][H][W], patch_vecs float32 [n][ny][nx][2] or None, patch_ssd
+    float32 [n][ny][nx] or None, (ny, nx)), still in HBM."""
+    lib, (h, w) = _lib(), shape
+    ny, nx = len(patch_origins(h, patch, stride)), len(patch_origins(w, patch, stride))
+    nbytes = _size_query(lib.ofl_inverse_search_workspace_bytes, n, h, w, patch, stride)
+    work = DeviceBuffer(nbytes)
+    out, mask = DeviceBuffer(n * h * w * 8), DeviceBuffer(n * h * w)
+    pv = DeviceBuffer(n * ny * nx * 8) if want_patches else None
+    ps = DeviceBuffer(n * ny * nx * 4) if want_patches else None
+    nat.check(lib.ofl_inverse_search_dev(near.ptr, far.ptr, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, h, w, _ptr(flow),
+                                         _ptr(fmask), sign, patch, stride, iterations, 1 if normalise else 0, floor,
+                                         work.ptr, nbytes, out.ptr, mask.ptr, _ptr(pv), _ptr(ps), quant, stream))
+    return out, mask, pv, ps, (ny, nx)
+
+
+def inverse_search_host(near, far, layout, n, c, vecs, mask, sign, patch, stride, iterations, normalise, floor,
+                        want_patches=False, quant=nat.QUANT_EXACT):
+    """K24 for host arrays through ofl_inverse_search (upload, launches, download): near, far as in photometric_host, vecs
+    (n, H, W, 2) or (H, W, 2) with n = 1 -> (vecs float32 (n, H, W, 2), mask bool (n, H, W), patch_vecs float32
+    (n, ny, nx, 2) or None, patch_ssd float32 (n, ny, nx) or None, (ny, nx))."""
+    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(mask)
+    h, w = vecs.shape[-3:-1]
+    ny, nx = len(patch_origins(h, patch, stride)), len(patch_origins(w, patch, stride))
+    out, om = np.empty((n, h, w, 2), np.float32), np.empty((n, h, w), np.uint8)
+    pv = np.empty((n, ny, nx, 2), np.float32) if want_patches else None
+    ps = np.empty((n, ny, nx), np.float32) if want_patches else None
+    nat.check(_lib().ofl_inverse_search(near.ctypes.data, far.ctypes.data, _TENSOR_EL[near.dtype.name], _TENSOR_LAYOUT[layout],
+                                        n, c, h, w, vecs.ctypes.data, m.ctypes.data, sign, patch, stride, iterations,
+                                        1 if normalise else 0, floor, out.ctypes.data, om.ctypes.data, _host_ptr(pv), _host_ptr(ps), quant))
+    return out, om.view(np.bool_), pv, ps, (ny, nx)
