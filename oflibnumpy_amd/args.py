@@ -271,6 +271,61 @@ def consistency_args(alpha=None, beta=None):
     return out[0], out[1]
 
 
+# -- what the image-pair families K21 ... K24 share: their number settings, the channel limit and the two host arrays
+def _float32_rounded(value, name, prefix, none_ok=True):
+    """a number -> float32, +-inf where float32 cannot hold it; a bool or a non-number is a TypeError (none_ok: the caller
+    takes None for a default, and the message says so)"""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise TypeError("{}{} must be a number{}, got {}".format(prefix, name, " or None" if none_ok else "", type(value).__name__))
+    with np.errstate(over='ignore', under='ignore'):
+        return np.float32(float(value)) if abs(value) < 1e300 else np.float32(np.inf if value > 0 else -np.inf)
+
+
+def _float32_setting(value, name, prefix, positive=False, none_ok=True, note=""):
+    """_float32_rounded, and a ValueError for NaN, a negative value, one that is not finite once rounded to float32 and --
+    `positive` -- one that is not above 0 then; `note` follows the rule in that message"""
+    v32 = _float32_rounded(value, name, prefix, none_ok)
+    if value != value or value < 0 or not np.isfinite(v32) or (positive and not v32 > 0):
+        raise ValueError("{}{} must be finite and {}{}, got {}".format(prefix, name, "positive" if positive else "not negative", note, value))
+    return v32
+
+
+def _integer_setting(value, name, prefix, lo=None, hi=None, none_ok=False):
+    """an integer -> int; a bool or a non-integer is a TypeError (none_ok as above), a value outside [lo, hi] a ValueError
+    (lo None: the caller checks the value, in its own words)"""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise TypeError("{}{} must be an integer{}, got {}".format(prefix, name, " or None" if none_ok else "", type(value).__name__))
+    if lo is not None and not lo <= value <= hi:
+        raise ValueError("{}{} must be in [{}, {}], got {}".format(prefix, name, lo, hi, value))
+    return int(value)
+
+
+def pair_channels(c, limit, prefix):
+    """The channel count of a family that forms channel means (K22, K23, K24): 1 ... limit, else a ValueError that names it."""
+    if not 1 <= c <= limit:
+        raise ValueError("{}the tensors need 1 to {} channels (grey, two-plane, RGB, RGBA), got {}".format(prefix, limit, c))
+    return c
+
+
+def pair_host_arrays(near, far, layout, field_shape, prefix, max_c=None, one_item=False):
+    """The `near` and `far` of Flow.photometric / census / refine / inverse_search -> (near, far, n, c, batched): two
+    contiguous arrays (photometric_host_array) of one shape and dtype with the height and width of the flow, at most max_c
+    channels (None: any count) and -- one_item -- a single item.  `prefix` starts the messages."""
+    near, far = photometric_host_array(near, layout, "near", prefix), photometric_host_array(far, layout, "far", prefix)
+    if near.shape != far.shape:
+        raise ValueError("{}the arrays need the same shape, got {} and {}".format(prefix, near.shape, far.shape))
+    if near.dtype != far.dtype:
+        raise TypeError("{}the arrays need the same dtype, got {} and {}".format(prefix, near.dtype, far.dtype))
+    n, c, h, w, batched = tensor_args(tensor_logical_shape(near.shape, layout), layout, near.dtype.name)
+    if max_c is not None:
+        pair_channels(c, max_c, prefix)
+    if one_item and n != 1:
+        raise ValueError("{}one flow takes one item, got {}".format(prefix, n))
+    if (h, w) != tuple(field_shape):
+        raise ValueError("{}arrays and flow need the same height and width, got {} and {}".format(prefix, (h, w), tuple(field_shape)))
+    return near, far, n, c, batched
+
+
 # -- photometric error of a warp (K21)
 PHOTO_METRICS = {'l1': nat.PHOTO_L1, 'l2': nat.PHOTO_L2, 'charbonnier': nat.PHOTO_CHARBONNIER}
 PHOTO_EPS = 1e-3                  # the Charbonnier constant when none is given
@@ -287,19 +342,9 @@ def photometric_args(metric='l1', eps=None, threshold=None):
         raise TypeError("{}metric must be a string, got {}".format(prefix, type(metric).__name__))
     if metric not in PHOTO_METRICS:
         raise ValueError("{}metric must be 'l1', 'l2' or 'charbonnier', got {!r}".format(prefix, metric))
-    out = []
-    for name, value in (("eps", PHOTO_EPS if eps is None else eps), ("threshold", threshold)):
-        if value is None:
-            out.append(None)
-            continue
-        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
-            raise TypeError("{}{} must be a number or None, got {}".format(prefix, name, type(value).__name__))
-        with np.errstate(over='ignore'):
-            v32 = np.float32(float(value)) if abs(value) < 1e300 else np.float32(np.inf if value > 0 else -np.inf)
-        if value != value or value < 0 or not np.isfinite(v32):
-            raise ValueError("{}{} must be finite and not negative, got {}".format(prefix, name, value))
-        out.append(v32)
-    return PHOTO_METRICS[metric], out[0], out[1]
+    eps = _float32_setting(PHOTO_EPS if eps is None else eps, "eps", prefix)
+    threshold = None if threshold is None else _float32_setting(threshold, "threshold", prefix)
+    return PHOTO_METRICS[metric], eps, threshold
 
 
 def photometric_host_array(a, layout, name, prefix="Error computing photometric error: "):
@@ -338,8 +383,7 @@ def census_args(window=7, mode='soft', delta=None, noise=None, knee=None, min_co
     output, else the bound err <= threshold.  A bool or a value of the wrong type is a TypeError, a value out of range or
     not finite (as given, or once rounded to float32) a ValueError."""
     prefix = "Error computing census distance: "
-    if isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, np.integer)):
-        raise TypeError("{}window must be an integer, got {}".format(prefix, type(window).__name__))
+    _integer_setting(window, "window", prefix)
     if window not in CENSUS_WINDOWS:
         raise ValueError("{}window must be 3, 5 or 7, got {}".format(prefix, window))
     if not isinstance(mode, str):
@@ -354,23 +398,11 @@ def census_args(window=7, mode='soft', delta=None, noise=None, knee=None, min_co
     else:
         values = (("noise", CENSUS_NOISE if noise is None else noise, True), ("knee", CENSUS_KNEE if knee is None else knee, True),
                   ("threshold", threshold, False))
-    out = {}
-    for name, value, positive in values:
-        if value is None:
-            out[name] = None
-            continue
-        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
-            raise TypeError("{}{} must be a number or None, got {}".format(prefix, name, type(value).__name__))
-        with np.errstate(over='ignore'):
-            v32 = np.float32(float(value)) if abs(value) < 1e300 else np.float32(np.inf if value > 0 else -np.inf)
-        if value != value or value < 0 or not np.isfinite(v32) or (positive and not v32 > 0):
-            raise ValueError("{}{} must be finite and {}, got {}".format(prefix, name, "positive" if positive else "not negative", value))
-        out[name] = v32
+    out = {name: None if value is None else _float32_setting(value, name, prefix, positive) for name, value, positive in values}
     full = int(window) * int(window) - 1
     if min_count is None:
         min_count = full
-    if isinstance(min_count, (bool, np.bool_)) or not isinstance(min_count, (int, np.integer)):
-        raise TypeError("{}min_count must be an integer or None, got {}".format(prefix, type(min_count).__name__))
+    _integer_setting(min_count, "min_count", prefix, none_ok=True)
     if not 1 <= min_count <= full:
         raise ValueError("{}min_count must be in [1, {}] for window {}, got {}".format(prefix, full, window, min_count))
     p0, p1 = (out["delta"], np.float32(0)) if mode == 'hard' else (out["noise"], out["knee"])
@@ -379,10 +411,7 @@ def census_args(window=7, mode='soft', delta=None, noise=None, knee=None, min_co
 
 def census_channels(c):
     """The channel count of a census distance (K22): 1 ... 4, else a ValueError that names the limit."""
-    if not 1 <= c <= nat.CENSUS_MAX_C:
-        raise ValueError("Error computing census distance: the tensors need 1 to {} channels (grey, two-plane, RGB, RGBA), got {}"
-                         .format(nat.CENSUS_MAX_C, c))
-    return c
+    return pair_channels(c, nat.CENSUS_MAX_C, "Error computing census distance: ")
 
 
 # -- variational refinement of a field on two images (K23)
@@ -398,39 +427,26 @@ def refine_args(alpha=None, delta=None, zeta=None, eps=None, fixed_point=None, s
     finite (as given, or once rounded to float32) a ValueError."""
     prefix = "Error refining flow: "
     given = dict(alpha=alpha, delta=delta, zeta=zeta, eps=eps, fixed_point=fixed_point, sor=sor, omega=omega)
-    out = {}
-    for name in ("alpha", "delta", "zeta", "eps", "omega"):
-        value = REFINE_DEFAULTS[name] if given[name] is None else given[name]
-        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
-            raise TypeError("{}{} must be a number or None, got {}".format(prefix, name, type(value).__name__))
+    given = {name: REFINE_DEFAULTS[name] if value is None else value for name, value in given.items()}
+    out = {name: _float32_setting(given[name], name, prefix) for name in ("alpha", "delta")}
+    square_too = " (its float32 square too)"
+    for name in ("zeta", "eps"):
+        out[name] = _float32_setting(given[name], name, prefix, positive=True, note=square_too)
         with np.errstate(over='ignore', under='ignore'):
-            v32 = np.float32(float(value)) if abs(value) < 1e300 else np.float32(np.inf if value > 0 else -np.inf)
-            square = v32 * v32
-        if name == "omega":
-            if not 0 < v32 < 2:
-                raise ValueError("{}omega must lie in (0, 2), got {}".format(prefix, value))
-        elif name in ("zeta", "eps"):
-            if value != value or not np.isfinite(v32) or not v32 > 0 or not 0 < square < np.inf:
-                raise ValueError("{}{} must be finite and positive (its float32 square too), got {}".format(prefix, name, value))
-        elif value != value or value < 0 or not np.isfinite(v32):
-            raise ValueError("{}{} must be finite and not negative, got {}".format(prefix, name, value))
-        out[name] = v32
+            square = out[name] * out[name]
+        if not 0 < square < np.inf:
+            raise ValueError("{}{} must be finite and positive{}, got {}".format(prefix, name, square_too, given[name]))
+    omega = _float32_rounded(given["omega"], "omega", prefix)
+    if not 0 < omega < 2:
+        raise ValueError("{}omega must lie in (0, 2), got {}".format(prefix, given["omega"]))
     for name in ("fixed_point", "sor"):
-        value = REFINE_DEFAULTS[name] if given[name] is None else given[name]
-        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
-            raise TypeError("{}{} must be an integer or None, got {}".format(prefix, name, type(value).__name__))
-        if not 1 <= value <= nat.REFINE_MAX_ITER:
-            raise ValueError("{}{} must be in [1, {}], got {}".format(prefix, name, nat.REFINE_MAX_ITER, value))
-        out[name] = int(value)
-    return out["alpha"], out["delta"], out["zeta"], out["eps"], out["fixed_point"], out["sor"], out["omega"]
+        out[name] = _integer_setting(given[name], name, prefix, 1, nat.REFINE_MAX_ITER, none_ok=True)
+    return out["alpha"], out["delta"], out["zeta"], out["eps"], out["fixed_point"], out["sor"], omega
 
 
 def refine_channels(c):
     """The channel count of a variational refinement (K23): 1 ... 4, else a ValueError that names the limit."""
-    if not 1 <= c <= nat.REFINE_MAX_C:
-        raise ValueError("Error refining flow: the tensors need 1 to {} channels (grey, two-plane, RGB, RGBA), got {}"
-                         .format(nat.REFINE_MAX_C, c))
-    return c
+    return pair_channels(c, nat.REFINE_MAX_C, "Error refining flow: ")
 
 
 # -- dense inverse search of a field on two images (K24) and the coarse-to-fine estimator on top of it
@@ -446,31 +462,21 @@ def inverse_search_args(patch=8, stride=4, iterations=12, normalise=True, floor=
     TypeError, a value out of range or not finite (as given, or once rounded to float32) a ValueError."""
     prefix = "Error searching flow: "
     for name, value in (("patch", patch), ("stride", stride), ("iterations", iterations)):
-        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
-            raise TypeError("{}{} must be an integer, got {}".format(prefix, name, type(value).__name__))
+        _integer_setting(value, name, prefix)
     if patch not in ISEARCH_PATCHES:
         raise ValueError("{}patch must be 4 or 8, got {}".format(prefix, patch))
     if not 1 <= stride <= patch:
         raise ValueError("{}stride must be in [1, patch = {}], got {}".format(prefix, patch, stride))
-    if not 1 <= iterations <= nat.ISEARCH_MAX_ITER:
-        raise ValueError("{}iterations must be in [1, {}], got {}".format(prefix, nat.ISEARCH_MAX_ITER, iterations))
+    iterations = _integer_setting(iterations, "iterations", prefix, 1, nat.ISEARCH_MAX_ITER)
     if not isinstance(normalise, (bool, np.bool_)):
         raise TypeError("{}normalise must be a bool, got {}".format(prefix, type(normalise).__name__))
-    if isinstance(floor, (bool, np.bool_)) or not isinstance(floor, (int, float, np.integer, np.floating)):
-        raise TypeError("{}floor must be a number, got {}".format(prefix, type(floor).__name__))
-    with np.errstate(over='ignore', under='ignore'):
-        f32 = np.float32(float(floor)) if abs(floor) < 1e300 else np.float32(np.inf if floor > 0 else -np.inf)
-    if floor != floor or not np.isfinite(f32) or not f32 > 0:
-        raise ValueError("{}floor must be finite and positive (as float32 too), got {}".format(prefix, floor))
-    return int(patch), int(stride), int(iterations), bool(normalise), f32
+    floor = _float32_setting(floor, "floor", prefix, positive=True, none_ok=False, note=" (as float32 too)")
+    return int(patch), int(stride), iterations, bool(normalise), floor
 
 
 def inverse_search_channels(c):
     """The channel count of a dense inverse search (K24): 1 ... 4, else a ValueError that names the limit."""
-    if not 1 <= c <= nat.ISEARCH_MAX_C:
-        raise ValueError("Error searching flow: the tensors need 1 to {} channels (grey, two-plane, RGB, RGBA), got {}"
-                         .format(nat.ISEARCH_MAX_C, c))
-    return c
+    return pair_channels(c, nat.ISEARCH_MAX_C, "Error searching flow: ")
 
 
 def patch_origins(n, patch, stride):
@@ -703,10 +709,7 @@ MATCH_MAX_CHANNELS = 512
 
 def _float32_arg(value, name, prefix):
     """a finite number -> float32 (TypeError for a bool or a non-number, ValueError where float32 cannot hold it)"""
-    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
-        raise TypeError("{}{} must be a number or None, got {}".format(prefix, name, type(value).__name__))
-    with np.errstate(over='ignore'):
-        value = np.float32(float(value)) if abs(value) < 1e300 else np.float32(np.inf)
+    value = _float32_rounded(value, name, prefix)
     if not np.isfinite(value):
         raise ValueError("{}{} must be finite as float32".format(prefix, name))
     return value

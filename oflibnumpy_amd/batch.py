@@ -149,16 +149,9 @@ class DeviceFlowBatch:
         DeviceBuffers [n][H][W] (per item) or None.  -> (error float32, covered uint8) as DeviceBuffers [n][H][W];
         `threshold` appends within (uint8), return_counts an (n, 2) uint32 array of (covered, within) pixels per item -- the
         only option that synchronises.  A packed batch is read through its byte masks."""
-        prefix = "Error computing photometric error: "
-        code, eps, threshold = dev.photometric_args(metric, eps, threshold)
-        near, far = dev.photometric_tensors(near, far, self.shape, batch=self.n)
-        n_bytes = self.n * self.shape[0] * self.shape[1]
-        near_mask = dev.mask_buffer_arg(near_mask, n_bytes, prefix, "near_mask")
-        far_mask = dev.mask_buffer_arg(far_mask, n_bytes, prefix, "far_mask")
-        err, covered, within, counts = dev.photometric_launch(
-            near.buf, far.buf, near.dtype, near.layout, self.n, near.channels, self.shape, self.vecs, self.mask, False,
-            1 if self.ref == 's' else -1, code, eps, threshold, near_mask, far_mask, want_counts=bool(return_counts), quant=quant)
-        res = (err, covered) + ((within,) if within is not None else ())
+        res, counts, _ = dev.error_map_op(dev.photometric_launch, dev.photometric_args(metric, eps, threshold), None,
+                                          "Error computing photometric error: ", self.vecs, self.mask, self.shape, self.ref,
+                                          near, far, near_mask, far_mask, return_counts, quant, batch=self.n)
         return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
 
     def census(self, near, far, window=7, mode='soft', delta=None, noise=None, knee=None, min_count=None, threshold=None,
@@ -168,17 +161,9 @@ class DeviceFlowBatch:
         DeviceBuffers [n][H][W] (per item) or None.  -> (error float32, covered uint8) as DeviceBuffers [n][H][W];
         `threshold` appends within (uint8), return_counts an (n, 2) uint32 array of (covered, within) pixels per item -- the
         only option that synchronises.  A packed batch is read through its byte masks."""
-        prefix = "Error computing census distance: "
-        settings = dev.census_args(window, mode, delta, noise, knee, min_count, threshold)
-        near, far = dev.photometric_tensors(near, far, self.shape, batch=self.n, prefix=prefix)
-        dev.census_channels(near.channels)
-        n_bytes = self.n * self.shape[0] * self.shape[1]
-        near_mask = dev.mask_buffer_arg(near_mask, n_bytes, prefix, "near_mask")
-        far_mask = dev.mask_buffer_arg(far_mask, n_bytes, prefix, "far_mask")
-        err, covered, within, counts = dev.census_launch(
-            near.buf, far.buf, near.dtype, near.layout, self.n, near.channels, self.shape, self.vecs, self.mask, False,
-            1 if self.ref == 's' else -1, *settings, near_mask=near_mask, far_mask=far_mask, want_counts=bool(return_counts), quant=quant)
-        res = (err, covered) + ((within,) if within is not None else ())
+        res, counts, _ = dev.error_map_op(dev.census_launch, dev.census_args(window, mode, delta, noise, knee, min_count, threshold),
+                                          nat.CENSUS_MAX_C, "Error computing census distance: ", self.vecs, self.mask, self.shape,
+                                          self.ref, near, far, near_mask, far_mask, return_counts, quant, batch=self.n)
         return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
 
     def refine(self, near, far, alpha=None, delta=None, zeta=None, eps=None, fixed_point=None, sor=None, omega=None,
@@ -188,17 +173,8 @@ class DeviceFlowBatch:
         far_mask, valid uint8 DeviceBuffers [n][H][W] (per item) or None.  -> an unpacked DeviceFlowBatch of the same
         length, shape, reference and masks; return_data appends the uint8 DeviceBuffer [n][H][W].  A packed batch is read
         through its byte masks.  Nothing synchronises."""
-        prefix = "Error refining flow: "
-        settings = dev.refine_args(alpha, delta, zeta, eps, fixed_point, sor, omega)
-        near, far = dev.photometric_tensors(near, far, self.shape, batch=self.n, prefix=prefix)
-        dev.refine_channels(near.channels)
-        n_bytes = self.n * self.shape[0] * self.shape[1]
-        near_mask = dev.mask_buffer_arg(near_mask, n_bytes, prefix, "near_mask")
-        far_mask = dev.mask_buffer_arg(far_mask, n_bytes, prefix, "far_mask")
-        valid = dev.mask_buffer_arg(valid, n_bytes, prefix, "valid")
-        out, data = dev.refine_launch(near.buf, far.buf, near.dtype, near.layout, self.n, near.channels, self.shape, self.vecs,
-                                      self.mask, 1 if self.ref == 's' else -1, *settings, near_mask=near_mask, far_mask=far_mask,
-                                      valid=valid, want_data=bool(return_data), quant=quant)
+        out, data = dev.refine_op(dev.refine_args(alpha, delta, zeta, eps, fixed_point, sor, omega), self.vecs, self.mask,
+                                  self.shape, self.ref, near, far, near_mask, far_mask, valid, return_data, quant, batch=self.n)
         b = DeviceFlowBatch.wrap(self.n, self.shape, self.ref, out, self.mask)
         return (b, data) if return_data else b
 
@@ -209,15 +185,9 @@ class DeviceFlowBatch:
         -> an unpacked DeviceFlowBatch of the same length, shape and reference whose masks are K24's out_mask;
         return_patches appends (patch_vecs float32 DeviceBuffer [n][ny][nx][2], patch_ssd float32 DeviceBuffer [n][ny][nx],
         (ny, nx)).  A packed batch is read through its byte masks.  Nothing synchronises."""
-        prefix = "Error searching flow: "
-        settings = dev.inverse_search_args(patch, stride, iterations, normalise, floor)
-        near, far = dev.photometric_tensors(near, far, self.shape, batch=self.n, prefix=prefix)
-        dev.inverse_search_channels(near.channels)
-        if min(self.shape) < settings[0]:
-            raise ValueError("{}a {} x {} field holds no patch of {}".format(prefix, self.shape[0], self.shape[1], settings[0]))
-        out, mask, pv, ps, grid = dev.inverse_search_launch(near.buf, far.buf, near.dtype, near.layout, self.n, near.channels,
-                                                            self.shape, self.vecs, self.mask, 1 if self.ref == 's' else -1,
-                                                            *settings, want_patches=bool(return_patches), quant=quant)
+        out, mask, pv, ps, grid = dev.inverse_search_op(dev.inverse_search_args(patch, stride, iterations, normalise, floor),
+                                                        self.vecs, self.mask, self.shape, self.ref, near, far, return_patches,
+                                                        quant, batch=self.n)
         b = DeviceFlowBatch.wrap(self.n, self.shape, self.ref, out, mask)
         return (b, pv, ps, grid) if return_patches else b
 

@@ -46,10 +46,7 @@ using namespace ofl;
 
 namespace {
 
-constexpr int kTX = 64, kTY = 16;       // the tile
-constexpr int kRows = 4;                // rows of a column one thread owns: 4 waves x 4 rows
-
-struct CArgs {
+struct CArgs {                              // PairArgs' members by name, in the order the kernel was measured with (ofl_photo_dev.h)
     const void    *near, *far;
     const float   *flow;
     const uint8_t *fmask, *near_mask, *far_mask;
@@ -58,8 +55,8 @@ struct CArgs {
     uint32_t      *counts;
     int            N, C, H, W, sign, min_count;
     float          p0, p1, tau, inv_c;      // hard: p0 = delta; soft: p0 = noise, p1 = knee
-    size_t         step;                    // pixels from one item's field and masks to the next (0: shared)
-    size_t         s_px, s_ch;              // elements from a pixel to the next and from a channel to the next
+    size_t         step;
+    size_t         s_px, s_ch;
 };
 
 // hard mode: s(a) != s(b).  delta >= 0, so v > delta and v < -delta exclude each other and the two signs are equal exactly when
@@ -167,13 +164,7 @@ int check_census_args(const char *who, const void *near, const void *far, int el
                       float tau, const void *err, const void *within, int quant)
 {
     if (!near || !far || !flow || !fmask) return fail(OFL_E_INVALID, "%s: NULL pointer (near, far, flow and fmask are required)", who);
-    if (elem != OFL_EL_F16 && elem != OFL_EL_BF16 && elem != OFL_EL_F32)
-        return fail(OFL_E_INVALID, "%s: elem must be OFL_EL_F16, OFL_EL_BF16 or OFL_EL_F32, got %d", who, elem);
-    if (layout != OFL_TENSOR_NCHW && layout != OFL_TENSOR_NHWC) return fail(OFL_E_INVALID, "%s: bad layout %d", who, layout);
-    if (N < 1 || N > 65535) return fail(OFL_E_INVALID, "%s: N must be in [1, 65535], got %d", who, N);
-    if (C < 1 || C > OFL_CENSUS_MAX_C) return fail(OFL_E_INVALID, "%s: C must be in [1, %d], got %d", who, OFL_CENSUS_MAX_C, C);
-    OFL_TRY(check_field_dims(who, H, W));
-    if (sign != 1 && sign != -1) return fail(OFL_E_INVALID, "%s: sign must be +1 or -1", who);
+    OFL_TRY(check_pair_args(who, elem, layout, N, C, OFL_CENSUS_MAX_C, H, W, sign, quant));
     if (window != 3 && window != 5 && window != 7) return fail(OFL_E_INVALID, "%s: window must be 3, 5 or 7, got %d", who, window);
     if (mode == OFL_CENSUS_HARD) {
         if (!(p0 >= 0.0f) || !__builtin_isfinite(p0)) return fail(OFL_E_INVALID, "%s: delta must be finite and not negative (got %g)", who, (double)p0);
@@ -188,7 +179,6 @@ int check_census_args(const char *who, const void *near, const void *far, int el
     if (!err && !within) return fail(OFL_E_INVALID, "%s: one of err and within is required", who);
     if (within && (!(tau >= 0.0f) || !__builtin_isfinite(tau)))
         return fail(OFL_E_INVALID, "%s: tau must be finite and not negative (got %g)", who, (double)tau);
-    if (quant != OFL_QUANT_OPENCV && quant != OFL_QUANT_EXACT) return fail(OFL_E_INVALID, "%s: bad quant", who);
     return OFL_OK;
 }
 
@@ -198,23 +188,6 @@ void launch_census(const CArgs &a, int mode, hipStream_t s)
     const dim3 grid((unsigned)((a.W + kTX - 1) / kTX), (unsigned)((a.H + kTY - 1) / kTY), (unsigned)a.N);
     if (mode == OFL_CENSUS_HARD) hipLaunchKernelGGL((census_kernel<E, QUANT, K, OFL_CENSUS_HARD>), grid, dim3(256), 0, s, a);
     else                         hipLaunchKernelGGL((census_kernel<E, QUANT, K, OFL_CENSUS_SOFT>), grid, dim3(256), 0, s, a);
-}
-
-template <int E, int QUANT>
-void launch_census(const CArgs &a, int window, int mode, hipStream_t s)
-{
-    switch (window) {
-    case 3:  launch_census<E, QUANT, 3>(a, mode, s); break;
-    case 5:  launch_census<E, QUANT, 5>(a, mode, s); break;
-    default: launch_census<E, QUANT, 7>(a, mode, s); break;
-    }
-}
-
-template <int E>
-void launch_census(const CArgs &a, int window, int mode, int quant, hipStream_t s)
-{
-    if (quant == OFL_QUANT_OPENCV) launch_census<E, OFL_QUANT_OPENCV>(a, window, mode, s);
-    else                           launch_census<E, OFL_QUANT_EXACT>(a, window, mode, s);
 }
 
 }  // namespace
@@ -230,25 +203,22 @@ int ofl_census_dev(const void *near, const void *far, int elem, int layout, int 
     OFL_TRY(need_device());
     OFL_TRY(check_census_args("ofl_census", near, far, elem, layout, N, C, H, W, flow, fmask, sign, window, mode, p0, p1, min_count, tau,
                               err, within, quant));
-    const unsigned eb = elem == OFL_EL_F32 ? 4 : 2;
-    if (!host_aligned(near, eb) || !host_aligned(far, eb)) return fail(OFL_E_INVALID, "ofl_census: near and far must be aligned to the element size");
+    OFL_TRY(check_pair_alignment("ofl_census", near, far, elem));
     if (!host_aligned(flow, 8)) return fail(OFL_E_INVALID, "ofl_census: flow must be 8-byte aligned");
     if (!host_aligned(err, 4) || !host_aligned(counts, 4)) return fail(OFL_E_INVALID, "ofl_census: err and counts must be 4-byte aligned");
     CArgs a;
-    a.near = near; a.far = far; a.flow = flow; a.fmask = fmask; a.near_mask = near_mask; a.far_mask = far_mask;
+    pair_fill(a, near, far, layout, N, C, H, W, flow, fmask, flow_shared != 0, sign, near_mask, far_mask);
     a.err = err; a.covered = covered; a.within = within; a.counts = counts;
-    a.N = N; a.C = C; a.H = H; a.W = W; a.sign = sign; a.min_count = min_count;
+    a.min_count = min_count;
     a.p0 = p0; a.p1 = p1; a.tau = tau;
-    a.inv_c = (float)(1.0 / (double)C);
-    a.step = flow_shared ? 0 : (size_t)H * W;
-    a.s_px = layout == OFL_TENSOR_NCHW ? 1 : (size_t)C;
-    a.s_ch = layout == OFL_TENSOR_NCHW ? (size_t)H * W : 1;
     hipStream_t s = stream_of(stream);
-    switch (elem) {
-    case OFL_EL_F16:  launch_census<OFL_EL_F16>(a, window, mode, quant, s); break;
-    case OFL_EL_BF16: launch_census<OFL_EL_BF16>(a, window, mode, quant, s); break;
-    default:          launch_census<OFL_EL_F32>(a, window, mode, quant, s); break;
-    }
+    with_elem(elem, [&](auto E) { with_quant(quant, [&](auto Q) {
+        switch (window) {
+        case 3:  launch_census<E.value, Q.value, 3>(a, mode, s); break;
+        case 5:  launch_census<E.value, Q.value, 5>(a, mode, s); break;
+        default: launch_census<E.value, Q.value, 7>(a, mode, s); break;
+        }
+    }); });
     OFL_HIP(hipGetLastError());
     return OFL_OK;
 }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 #include "../../include/ofl.h"
 
 // ----------------------------------------------------------------------------- host side state
@@ -32,6 +33,15 @@ inline bool overlap(const void *p, size_t n, const void *q, size_t m)
 {
     const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
     return p && q && a < b + m && b < a + n;
+}
+
+// f(std::integral_constant<int, quant>) for a checked quant: f is a generic lambda whose argument Q gives the template
+// argument Q.value (with_elem of ofl_elem.h does the same for the element type)
+template <class F>
+inline void with_quant(int quant, F &&f)
+{
+    if (quant == OFL_QUANT_OPENCV) f(std::integral_constant<int, OFL_QUANT_OPENCV>());
+    else                           f(std::integral_constant<int, OFL_QUANT_EXACT>());
 }
 
 }  // namespace ofl

@@ -1,4 +1,5 @@
-// ofl_elem.h -- the element types fields and tensors are stored in (OFL_EL_*), shared by ofl_interop.hip and ofl_tensor.hip.
+// ofl_elem.h -- the element types fields and tensors are stored in (OFL_EL_*), shared by every file whose kernels are templates
+// of the element type, and with_elem, which turns a checked run-time OFL_EL_* into that template argument.
 #pragma once
 #include "ofl_common.h"
 
@@ -33,5 +34,17 @@ template <> struct Elem<OFL_EL_F64> {
     typedef double T;
     static __device__ __forceinline__ float to_f32(T v) { return (float)v; }                                              // nearest even
 };
+
+// f(std::integral_constant<int, elem>) for a checked elem of the three tensor types: f is a generic lambda whose argument E
+// gives the template argument E.value
+template <class F>
+inline void with_elem(int elem, F &&f)
+{
+    switch (elem) {
+    case OFL_EL_F16:  f(std::integral_constant<int, OFL_EL_F16>()); break;
+    case OFL_EL_BF16: f(std::integral_constant<int, OFL_EL_BF16>()); break;
+    default:          f(std::integral_constant<int, OFL_EL_F32>()); break;
+    }
+}
 
 }  // namespace ofl

@@ -37,13 +37,7 @@ using namespace ofl;
 
 namespace {
 
-struct IArgs {
-    const void    *near, *far;
-    const float   *flow;                    // NULL: the zero field
-    const uint8_t *fmask;                   // NULL: all set
-    int            N, C, H, W, sign;
-    float          inv_c;
-    size_t         s_px, s_ch;
+struct IArgs : PairArgs {                   // flow NULL: the zero field; fmask NULL: all set; near_mask, far_mask: NULL
     float         *pa, *pb;                 // the planes A and Bm, [N][H][W]
     float2        *pv;                      // patch vectors [N][ny][nx]
     float         *pssd;                    // patch ssd [N][ny][nx] or NULL
@@ -52,8 +46,6 @@ struct IArgs {
     float         *out;
     uint8_t       *out_mask;
 };
-
-__device__ __forceinline__ bool finite32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // origin i of the patch grid along an axis of length n: 0, S, 2 S, ... and n - P for the last
 __device__ __forceinline__ int origin_of(int i, int stride, int last) { return min(i * stride, last); }
@@ -215,16 +207,11 @@ int check_isearch_args(const char *who, const void *near, const void *far, int e
                        int sign, int patch, int stride, int iterations, float floor, const void *out, const void *out_mask, int quant)
 {
     if (!near || !far || !out || !out_mask) return fail(OFL_E_INVALID, "%s: NULL pointer (near, far, out and out_mask are required)", who);
-    if (elem != OFL_EL_F16 && elem != OFL_EL_BF16 && elem != OFL_EL_F32)
-        return fail(OFL_E_INVALID, "%s: elem must be OFL_EL_F16, OFL_EL_BF16 or OFL_EL_F32, got %d", who, elem);
-    if (layout != OFL_TENSOR_NCHW && layout != OFL_TENSOR_NHWC) return fail(OFL_E_INVALID, "%s: bad layout %d", who, layout);
-    if (C < 1 || C > OFL_ISEARCH_MAX_C) return fail(OFL_E_INVALID, "%s: C must be in [1, %d], got %d", who, OFL_ISEARCH_MAX_C, C);
+    OFL_TRY(check_pair_args(who, elem, layout, N, C, OFL_ISEARCH_MAX_C, H, W, sign, quant));
     OFL_TRY(check_isearch_dims(who, N, H, W, patch, stride));
-    if (sign != 1 && sign != -1) return fail(OFL_E_INVALID, "%s: sign must be +1 or -1", who);
     if (iterations < 1 || iterations > OFL_ISEARCH_MAX_ITER)
         return fail(OFL_E_INVALID, "%s: iterations must be in [1, %d], got %d", who, OFL_ISEARCH_MAX_ITER, iterations);
     if (!(__builtin_isfinite(floor) && floor > 0.0f)) return fail(OFL_E_INVALID, "%s: floor must be finite and positive (got %g)", who, (double)floor);
-    if (quant != OFL_QUANT_OPENCV && quant != OFL_QUANT_EXACT) return fail(OFL_E_INVALID, "%s: bad quant", who);
     return OFL_OK;
 }
 
@@ -256,11 +243,10 @@ int ofl_inverse_search_dev(const void *near, const void *far, int elem, int layo
     const size_t need = px * 8 + (own ? np * 12 : 0);
     if (!workspace || workspace_bytes < need)
         return fail(OFL_E_INVALID, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace ? workspace_bytes : (size_t)0);
-    const unsigned eb = elem == OFL_EL_F32 ? 4 : 2;
-    if (!host_aligned(near, eb) || !host_aligned(far, eb)) return fail(OFL_E_INVALID, "%s: near and far must be aligned to the element size", who);
+    OFL_TRY(check_pair_alignment(who, near, far, elem));
     if (!host_aligned(flow, 8) || !host_aligned(out, 8) || !host_aligned(workspace, 8) || !host_aligned(patch_vecs, 8) || !host_aligned(patch_ssd, 4))
         return fail(OFL_E_INVALID, "%s: flow, out, patch_vecs and the workspace must be 8-byte, patch_ssd 4-byte aligned", who);
-    const size_t tb = px * C * eb;
+    const size_t tb = px * C * (elem == OFL_EL_F32 ? 4 : 2);
     const void *ins[4] = { near, far, flow, fmask };
     const size_t in_bytes[4] = { tb, tb, px * 8, px };
     void *outs[5] = { workspace, out, out_mask, patch_vecs, patch_ssd };
@@ -272,11 +258,7 @@ int ofl_inverse_search_dev(const void *near, const void *far, int elem, int layo
             if (overlap(outs[i], out_bytes[i], outs[j], out_bytes[j])) return fail(OFL_E_INVALID, "%s: the outputs and the workspace overlap", who);
     }
     IArgs a;
-    a.near = near; a.far = far; a.flow = flow; a.fmask = fmask;
-    a.N = N; a.C = C; a.H = H; a.W = W; a.sign = sign;
-    a.inv_c = (float)(1.0 / (double)C);
-    a.s_px = layout == OFL_TENSOR_NCHW ? 1 : (size_t)C;
-    a.s_ch = layout == OFL_TENSOR_NCHW ? (size_t)H * W : 1;
+    pair_fill(a, near, far, layout, N, C, H, W, flow, fmask, false, sign, nullptr, nullptr);
     a.pa = static_cast<float *>(workspace);
     a.pb = a.pa + px;
     a.pv = patch_vecs ? reinterpret_cast<float2 *>(patch_vecs) : reinterpret_cast<float2 *>(a.pb + px);
@@ -287,23 +269,14 @@ int ofl_inverse_search_dev(const void *near, const void *far, int elem, int layo
 
     hipStream_t s = stream_of(stream);
     const dim3 block(256), full((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4), (unsigned)N);
-    switch (elem) {
-    case OFL_EL_F16:  hipLaunchKernelGGL((isearch_setup_kernel<OFL_EL_F16>), full, block, 0, s, a); break;
-    case OFL_EL_BF16: hipLaunchKernelGGL((isearch_setup_kernel<OFL_EL_BF16>), full, block, 0, s, a); break;
-    default:          hipLaunchKernelGGL((isearch_setup_kernel<OFL_EL_F32>), full, block, 0, s, a); break;
-    }
+    with_elem(elem, [&](auto E) { hipLaunchKernelGGL((isearch_setup_kernel<E.value>), full, block, 0, s, a); });
     const int per_block = patch == 8 ? 4 : 16;
     const dim3 sgrid((unsigned)((ny * nx + per_block - 1) / per_block), (unsigned)N);
-    const bool cv = quant == OFL_QUANT_OPENCV;
-    if (patch == 8) {
-        if (cv) hipLaunchKernelGGL((isearch_search_kernel<8, OFL_QUANT_OPENCV>), sgrid, block, 0, s, a);
-        else    hipLaunchKernelGGL((isearch_search_kernel<8, OFL_QUANT_EXACT>), sgrid, block, 0, s, a);
-    } else {
-        if (cv) hipLaunchKernelGGL((isearch_search_kernel<4, OFL_QUANT_OPENCV>), sgrid, block, 0, s, a);
-        else    hipLaunchKernelGGL((isearch_search_kernel<4, OFL_QUANT_EXACT>), sgrid, block, 0, s, a);
-    }
-    if (cv) hipLaunchKernelGGL((isearch_densify_kernel<OFL_QUANT_OPENCV>), full, block, 0, s, a, patch);
-    else    hipLaunchKernelGGL((isearch_densify_kernel<OFL_QUANT_EXACT>), full, block, 0, s, a, patch);
+    with_quant(quant, [&](auto Q) {
+        if (patch == 8) hipLaunchKernelGGL((isearch_search_kernel<8, Q.value>), sgrid, block, 0, s, a);
+        else            hipLaunchKernelGGL((isearch_search_kernel<4, Q.value>), sgrid, block, 0, s, a);
+        hipLaunchKernelGGL((isearch_densify_kernel<Q.value>), full, block, 0, s, a, patch);
+    });
     OFL_HIP(hipGetLastError());
     return OFL_OK;
 }

@@ -1,11 +1,69 @@
-// ofl_photo_dev.h -- device helpers that K21 (ofl_photometric.hip), K22 (ofl_census.hip), K23 (ofl_refine.hip) and K24
-// (ofl_inverse_search.hip) share: the frame test of a tap, the `covered` rule of a pixel, the channel mean of a pixel (K24),
-// the warp of a tile plus halo into LDS (K22, K23) and the per-item counts of a workgroup.
+// ofl_photo_dev.h -- what the image-pair families K21 (ofl_photometric.hip), K22 (ofl_census.hip), K23 (ofl_refine.hip) and K24
+// (ofl_inverse_search.hip) share.  Host: PairArgs, the kernel arguments that describe the two tensors and the field, with the
+// checks of the arguments behind them (check_pair_args, check_pair_alignment) and pair_fill, which sets them.  Device: the
+// frame test of a tap, the `covered` rule of a pixel, finite32, the channel mean of a pixel (K24), the warp of a tile plus halo
+// into LDS (K22, K23) with the tile it is instantiated on, and the per-item counts of a workgroup.  A family keeps its own
+// NULL-pointer line, the checks of its settings, outputs and workspace, and the launches (DESIGN "Image-pair families").
 #pragma once
 #include "ofl_common.h"
 #include "ofl_elem.h"
 
 namespace ofl {
+
+// ----------------------------------------------------------------------------- host side
+// the arguments every kernel of the four families takes: the Args of stage_warped_tile.  K23's and K24's structs derive from
+// it.  K21's and K22's declare the same members by name in an order of their own, their outputs between the pointers and the
+// sizes: where a member lies in the kernel-argument segment changes the code of their kernels -- derived, with the outputs
+// behind, census_kernel<..., 7, hard> ran 7 - 10 % and photo_nchw_kernel<..., 0> at C = 128 42 % longer (profiles/r24_pair_fold_ab.txt).
+struct PairArgs {
+    const void    *near, *far;
+    const float   *flow;
+    const uint8_t *fmask, *near_mask, *far_mask;
+    int            N, C, H, W, sign;
+    float          inv_c;
+    size_t         step;            // pixels from one item's field and masks to the next (0: shared)
+    size_t         s_px, s_ch;      // elements from a pixel to the next and from a channel to the next
+};
+
+// the checks of the arguments the four families share, C against the family's limit `max_c`
+inline int check_pair_args(const char *who, int elem, int layout, int N, int C, int max_c, int H, int W, int sign, int quant)
+{
+    if (elem != OFL_EL_F16 && elem != OFL_EL_BF16 && elem != OFL_EL_F32)
+        return fail(OFL_E_INVALID, "%s: elem must be OFL_EL_F16, OFL_EL_BF16 or OFL_EL_F32, got %d", who, elem);
+    if (layout != OFL_TENSOR_NCHW && layout != OFL_TENSOR_NHWC) return fail(OFL_E_INVALID, "%s: bad layout %d", who, layout);
+    if (N < 1 || N > 65535) return fail(OFL_E_INVALID, "%s: N must be in [1, 65535], got %d", who, N);
+    if (C < 1 || C > max_c) return fail(OFL_E_INVALID, "%s: C must be in [1, %d], got %d", who, max_c, C);
+    OFL_TRY(check_field_dims(who, H, W));
+    if (sign != 1 && sign != -1) return fail(OFL_E_INVALID, "%s: sign must be +1 or -1", who);
+    if (quant != OFL_QUANT_OPENCV && quant != OFL_QUANT_EXACT) return fail(OFL_E_INVALID, "%s: bad quant", who);
+    return OFL_OK;
+}
+
+// the device pointers `near` and `far` on a boundary of their element
+inline int check_pair_alignment(const char *who, const void *near, const void *far, int elem)
+{
+    const unsigned eb = elem == OFL_EL_F32 ? 4 : 2;
+    if (!host_aligned(near, eb) || !host_aligned(far, eb)) return fail(OFL_E_INVALID, "%s: near and far must be aligned to the element size", who);
+    return OFL_OK;
+}
+
+// checked arguments -> the members of PairArgs (Args: PairArgs, a struct derived from it or one with the same members); both
+// layouts become a pixel stride and a channel stride
+template <class Args>
+inline void pair_fill(Args &a, const void *near, const void *far, int layout, int N, int C, int H, int W,
+                      const float *flow, const uint8_t *fmask, bool flow_shared, int sign,
+                      const uint8_t *near_mask, const uint8_t *far_mask)
+{
+    a.near = near; a.far = far; a.flow = flow; a.fmask = fmask; a.near_mask = near_mask; a.far_mask = far_mask;
+    a.N = N; a.C = C; a.H = H; a.W = W; a.sign = sign;
+    a.inv_c = (float)(1.0 / (double)C);
+    a.step = flow_shared ? 0 : (size_t)H * W;
+    a.s_px = layout == OFL_TENSOR_NCHW ? 1 : (size_t)C;
+    a.s_ch = layout == OFL_TENSOR_NCHW ? (size_t)H * W : 1;
+}
+
+// ----------------------------------------------------------------------------- device side
+__device__ __forceinline__ bool finite32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // the four in-frame flags and in-plane offsets of a tap (inside one plane: H * W < 2^31)
 __device__ __forceinline__ void tap_frame(const Tap &tp, int H, int W, bool (&in)[4], int (&off)[4])
@@ -54,7 +112,10 @@ __device__ __forceinline__ float channel_mean(const void *tensor, size_t base, s
 // per pixel makes the tap and issues the C `near`, 4 C `far` and the mask loads together (unconditional, as in K21: a tap
 // outside the frame reads element 0 and is replaced by 0.0f).  Both layouts go through ONE code path, as a pixel stride and
 // a channel stride; the element type and `quant` are template arguments and end here.  The caller synchronises.
-// Args: near, far, flow, fmask, near_mask, far_mask, C (1 ... 4), H, W, sign, inv_c, step, s_px, s_ch (see K22's CArgs).
+// Args: PairArgs, a struct derived from it or one with the same members, with C in 1 ... 4.  K22 and K23 instantiate it on the tile below.
+constexpr int kTX = 64, kTY = 16;       // the tile
+constexpr int kRows = 4;                // rows of a column one thread owns after the staging: 4 waves x 4 rows
+
 template <int E, int QUANT, int R, int TX, int TY, class Args>
 __device__ __forceinline__ void stage_warped_tile(const Args &a, int n, int x0, int y0, float *s_a, float *s_b, uint8_t *s_m)
 {

@@ -36,7 +36,7 @@
 // atomicAdd per counter (integer adds: their order cannot change the result); these are the only atomics.  Every element
 // offset is 64-bit.  No workspace.  A variant with two pixels per lane was not built: no figure, no variant.
 //
-// tap_frame, photo_covered and photo_count are shared with K22 (ofl_photo_dev.h).
+// PairArgs with its checks, tap_frame, photo_covered and photo_count are shared with K22 ... K24 (ofl_photo_dev.h).
 //
 // OUT OF SCOPE: window metrics (SSIM, gradient constancy; the census distance is K22, ofl_census.hip), a reduction of the
 // map, a backward pass, mixed element types or layouts, integer tensors, padding offsets.
@@ -54,7 +54,7 @@ namespace {
 constexpr int kV = 4;       // consecutive channels per group
 constexpr int kL = 16;      // partial sums
 
-struct PArgs {
+struct PArgs {                      // PairArgs' members by name, in the order the kernels were measured with (ofl_photo_dev.h)
     const void    *near, *far;
     const float   *flow;
     const uint8_t *fmask, *near_mask, *far_mask;
@@ -63,7 +63,8 @@ struct PArgs {
     uint32_t      *counts;
     int            N, C, H, W, sign, metric;
     float          eps2, tau, inv_c;
-    size_t         step;            // pixels from one item's field and masks to the next (0: shared)
+    size_t         step;
+    size_t         s_px, s_ch;      // pair_fill's; K21's two mappings index their layout themselves
 };
 
 // one channel's term from the difference d
@@ -245,19 +246,12 @@ int check_photometric_args(const char *who, const void *near, const void *far, i
                            const void *err, const void *within, int quant)
 {
     if (!near || !far || !flow || !fmask) return fail(OFL_E_INVALID, "%s: NULL pointer (near, far, flow and fmask are required)", who);
-    if (elem != OFL_EL_F16 && elem != OFL_EL_BF16 && elem != OFL_EL_F32)
-        return fail(OFL_E_INVALID, "%s: elem must be OFL_EL_F16, OFL_EL_BF16 or OFL_EL_F32, got %d", who, elem);
-    if (layout != OFL_TENSOR_NCHW && layout != OFL_TENSOR_NHWC) return fail(OFL_E_INVALID, "%s: bad layout %d", who, layout);
-    if (N < 1 || N > 65535) return fail(OFL_E_INVALID, "%s: N must be in [1, 65535], got %d", who, N);
-    if (C < 1 || C > 65535) return fail(OFL_E_INVALID, "%s: C must be in [1, 65535], got %d", who, C);
-    OFL_TRY(check_field_dims(who, H, W));
-    if (sign != 1 && sign != -1) return fail(OFL_E_INVALID, "%s: sign must be +1 or -1", who);
+    OFL_TRY(check_pair_args(who, elem, layout, N, C, 65535, H, W, sign, quant));
     if (metric != OFL_PHOTO_L1 && metric != OFL_PHOTO_L2 && metric != OFL_PHOTO_CHARBONNIER) return fail(OFL_E_INVALID, "%s: bad metric %d", who, metric);
     if (!(eps >= 0.0f) || !__builtin_isfinite(eps)) return fail(OFL_E_INVALID, "%s: eps must be finite and not negative (got %g)", who, (double)eps);
     if (!err && !within) return fail(OFL_E_INVALID, "%s: one of err and within is required", who);
     if (within && (!(tau >= 0.0f) || !__builtin_isfinite(tau)))
         return fail(OFL_E_INVALID, "%s: tau must be finite and not negative (got %g)", who, (double)tau);
-    if (quant != OFL_QUANT_OPENCV && quant != OFL_QUANT_EXACT) return fail(OFL_E_INVALID, "%s: bad quant", who);
     return OFL_OK;
 }
 
@@ -287,13 +281,6 @@ void launch_photometric(const PArgs &a, int layout, hipStream_t s)
         hipLaunchKernelGGL((photo_nhwc_kernel<E, QUANT, false>), grid, dim3(256), 0, s, a, lg);
 }
 
-template <int E>
-void launch_photometric(const PArgs &a, int layout, int quant, hipStream_t s)
-{
-    if (quant == OFL_QUANT_OPENCV) launch_photometric<E, OFL_QUANT_OPENCV>(a, layout, s);
-    else                           launch_photometric<E, OFL_QUANT_EXACT>(a, layout, s);
-}
-
 }  // namespace
 
 extern "C" {
@@ -306,24 +293,17 @@ int ofl_photometric_dev(const void *near, const void *far, int elem, int layout,
 {
     OFL_TRY(need_device());
     OFL_TRY(check_photometric_args("ofl_photometric", near, far, elem, layout, N, C, H, W, flow, fmask, sign, metric, eps, tau, err, within, quant));
-    const unsigned eb = elem == OFL_EL_F32 ? 4 : 2;
-    if (!host_aligned(near, eb) || !host_aligned(far, eb)) return fail(OFL_E_INVALID, "ofl_photometric: near and far must be aligned to the element size");
+    OFL_TRY(check_pair_alignment("ofl_photometric", near, far, elem));
     if (!host_aligned(flow, 8)) return fail(OFL_E_INVALID, "ofl_photometric: flow must be 8-byte aligned");
     if (!host_aligned(err, 4) || !host_aligned(counts, 4)) return fail(OFL_E_INVALID, "ofl_photometric: err and counts must be 4-byte aligned");
     PArgs a;
-    a.near = near; a.far = far; a.flow = flow; a.fmask = fmask; a.near_mask = near_mask; a.far_mask = far_mask;
+    pair_fill(a, near, far, layout, N, C, H, W, flow, fmask, flow_shared != 0, sign, near_mask, far_mask);
     a.err = err; a.covered = covered; a.within = within; a.counts = counts;
-    a.N = N; a.C = C; a.H = H; a.W = W; a.sign = sign; a.metric = metric;
+    a.metric = metric;
     a.eps2 = eps * eps;                                  // float32, rounded once (-ffp-contract=off)
     a.tau = tau;
-    a.inv_c = (float)(1.0 / (double)C);
-    a.step = flow_shared ? 0 : (size_t)H * W;
     hipStream_t s = stream_of(stream);
-    switch (elem) {
-    case OFL_EL_F16:  launch_photometric<OFL_EL_F16>(a, layout, quant, s); break;
-    case OFL_EL_BF16: launch_photometric<OFL_EL_BF16>(a, layout, quant, s); break;
-    default:          launch_photometric<OFL_EL_F32>(a, layout, quant, s); break;
-    }
+    with_elem(elem, [&](auto E) { with_quant(quant, [&](auto Q) { launch_photometric<E.value, Q.value>(a, layout, s); }); });
     OFL_HIP(hipGetLastError());
     return OFL_OK;
 }

@@ -35,28 +35,17 @@ using namespace ofl;
 
 namespace {
 
-constexpr int kTX = 64, kTY = 16;       // the setup tile (K22's)
-constexpr int kRows = 4;                // rows of a column one setup thread owns: 4 waves x 4 rows
 constexpr int kBY = 4;                  // rows of a weights / sweep / finish block of 64 x 4 threads
 constexpr uint8_t kDom = 1, kData = 2;  // the flag bits
 
-struct RArgs {
-    const void    *near, *far;                                  // stage_warped_tile's
-    const float   *flow;
-    const uint8_t *fmask, *near_mask, *far_mask;
-    int            N, C, H, W, sign;
-    float          inv_c;
-    size_t         step;                                        // pixels from one item's field and masks to the next
-    size_t         s_px, s_ch;
-    const uint8_t *valid;                                       // K23's
+struct RArgs : PairArgs {               // the setup tile kTX x kTY and a setup thread's kRows are stage_warped_tile's
+    const uint8_t *valid;
     float2        *d;
     float         *gx, *gy, *iz, *wd, *s;
     uint8_t       *flags, *data;
     float         *out;
     float          alpha, delta, zeta2, eps2, omega;
 };
-
-__device__ __forceinline__ bool finite32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // the four neighbours in the order of the definition: up, left, right, down
 __device__ __forceinline__ int nb_dx(int k) { return k == 1 ? -1 : (k == 2 ? 1 : 0); }
@@ -220,13 +209,7 @@ int check_refine_args(const char *who, const void *near, const void *far, int el
                       int fixed_point, int sor, float omega, const void *out, int quant)
 {
     if (!near || !far || !flow || !fmask || !out) return fail(OFL_E_INVALID, "%s: NULL pointer (near, far, flow, fmask and out are required)", who);
-    if (elem != OFL_EL_F16 && elem != OFL_EL_BF16 && elem != OFL_EL_F32)
-        return fail(OFL_E_INVALID, "%s: elem must be OFL_EL_F16, OFL_EL_BF16 or OFL_EL_F32, got %d", who, elem);
-    if (layout != OFL_TENSOR_NCHW && layout != OFL_TENSOR_NHWC) return fail(OFL_E_INVALID, "%s: bad layout %d", who, layout);
-    if (N < 1 || N > 65535) return fail(OFL_E_INVALID, "%s: N must be in [1, 65535], got %d", who, N);
-    if (C < 1 || C > OFL_REFINE_MAX_C) return fail(OFL_E_INVALID, "%s: C must be in [1, %d], got %d", who, OFL_REFINE_MAX_C, C);
-    OFL_TRY(check_field_dims(who, H, W));
-    if (sign != 1 && sign != -1) return fail(OFL_E_INVALID, "%s: sign must be +1 or -1", who);
+    OFL_TRY(check_pair_args(who, elem, layout, N, C, OFL_REFINE_MAX_C, H, W, sign, quant));
     if (!finite_in(alpha, 0.0f, false)) return fail(OFL_E_INVALID, "%s: alpha must be finite and not negative (got %g)", who, (double)alpha);
     if (!finite_in(delta, 0.0f, false)) return fail(OFL_E_INVALID, "%s: delta must be finite and not negative (got %g)", who, (double)delta);
     if (!finite_in(zeta, 0.0f, true)) return fail(OFL_E_INVALID, "%s: zeta must be finite and positive (got %g)", who, (double)zeta);
@@ -236,16 +219,7 @@ int check_refine_args(const char *who, const void *near, const void *far, int el
     if (fixed_point < 1 || fixed_point > OFL_REFINE_MAX_ITER) return fail(OFL_E_INVALID, "%s: fixed_point must be in [1, %d], got %d", who, OFL_REFINE_MAX_ITER, fixed_point);
     if (sor < 1 || sor > OFL_REFINE_MAX_ITER) return fail(OFL_E_INVALID, "%s: sor must be in [1, %d], got %d", who, OFL_REFINE_MAX_ITER, sor);
     if (!(omega > 0.0f && omega < 2.0f)) return fail(OFL_E_INVALID, "%s: omega must lie in (0, 2) (got %g)", who, (double)omega);
-    if (quant != OFL_QUANT_OPENCV && quant != OFL_QUANT_EXACT) return fail(OFL_E_INVALID, "%s: bad quant", who);
     return OFL_OK;
-}
-
-template <int E>
-void launch_setup(const RArgs &a, int quant, hipStream_t s)
-{
-    const dim3 grid((unsigned)((a.W + kTX - 1) / kTX), (unsigned)((a.H + kTY - 1) / kTY), (unsigned)a.N);
-    if (quant == OFL_QUANT_OPENCV) hipLaunchKernelGGL((refine_setup_kernel<E, OFL_QUANT_OPENCV>), grid, dim3(256), 0, s, a);
-    else                           hipLaunchKernelGGL((refine_setup_kernel<E, OFL_QUANT_EXACT>), grid, dim3(256), 0, s, a);
 }
 
 }  // namespace
@@ -274,11 +248,10 @@ int ofl_refine_dev(const void *near, const void *far, int elem, int layout, int 
     OFL_TRY(ofl_refine_workspace_bytes(N, H, W, &need));
     if (!workspace || workspace_bytes < need)
         return fail(OFL_E_INVALID, "ofl_refine: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
-    const unsigned eb = elem == OFL_EL_F32 ? 4 : 2;
-    if (!host_aligned(near, eb) || !host_aligned(far, eb)) return fail(OFL_E_INVALID, "ofl_refine: near and far must be aligned to the element size");
+    OFL_TRY(check_pair_alignment("ofl_refine", near, far, elem));
     if (!host_aligned(flow, 8) || !host_aligned(out, 8) || !host_aligned(workspace, 8))
         return fail(OFL_E_INVALID, "ofl_refine: flow, out and the workspace must be 8-byte aligned");
-    const size_t px = (size_t)N * H * W, tb = px * C * eb;
+    const size_t px = (size_t)N * H * W, tb = px * C * (elem == OFL_EL_F32 ? 4 : 2);
     if (overlap(out, px * 8, flow, px * 8) || overlap(out, px * 8, near, tb) || overlap(out, px * 8, far, tb) ||
         overlap(out, px * 8, fmask, px) || overlap(out, px * 8, near_mask, px) || overlap(out, px * 8, far_mask, px) ||
         overlap(out, px * 8, valid, px) || overlap(out, px * 8, data, px))
@@ -288,12 +261,7 @@ int ofl_refine_dev(const void *near, const void *far, int elem, int layout, int 
         overlap(workspace, need, far_mask, px) || overlap(workspace, need, valid, px) || overlap(workspace, need, data, px))
         return fail(OFL_E_INVALID, "ofl_refine: the workspace overlaps an argument");
     RArgs a;
-    a.near = near; a.far = far; a.flow = flow; a.fmask = fmask; a.near_mask = near_mask; a.far_mask = far_mask;
-    a.N = N; a.C = C; a.H = H; a.W = W; a.sign = sign;
-    a.inv_c = (float)(1.0 / (double)C);
-    a.step = (size_t)H * W;
-    a.s_px = layout == OFL_TENSOR_NCHW ? 1 : (size_t)C;
-    a.s_ch = layout == OFL_TENSOR_NCHW ? (size_t)H * W : 1;
+    pair_fill(a, near, far, layout, N, C, H, W, flow, fmask, false, sign, near_mask, far_mask);
     a.valid = valid;
     a.d = static_cast<float2 *>(workspace);
     a.gx = reinterpret_cast<float *>(a.d + px);
@@ -303,11 +271,10 @@ int ofl_refine_dev(const void *near, const void *far, int elem, int layout, int 
     a.alpha = alpha; a.delta = delta; a.zeta2 = zeta * zeta; a.eps2 = eps * eps; a.omega = omega;
 
     hipStream_t s = stream_of(stream);
-    switch (elem) {
-    case OFL_EL_F16:  launch_setup<OFL_EL_F16>(a, quant, s); break;
-    case OFL_EL_BF16: launch_setup<OFL_EL_BF16>(a, quant, s); break;
-    default:          launch_setup<OFL_EL_F32>(a, quant, s); break;
-    }
+    const dim3 tiles((unsigned)((W + kTX - 1) / kTX), (unsigned)((H + kTY - 1) / kTY), (unsigned)N);
+    with_elem(elem, [&](auto E) { with_quant(quant, [&](auto Q) {
+        hipLaunchKernelGGL((refine_setup_kernel<E.value, Q.value>), tiles, dim3(256), 0, s, a);
+    }); });
     const dim3 block(64, kBY);
     const dim3 full((unsigned)((W + 63) / 64), (unsigned)((H + kBY - 1) / kBY), (unsigned)N);
     const dim3 half((unsigned)((W + 127) / 128), (unsigned)((H + kBY - 1) / kBY), (unsigned)N);

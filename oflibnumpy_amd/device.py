@@ -33,8 +33,8 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rul
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
                    consistency_args, error_args, fill_args, median_args, upsample_args, upsample_weights_array, corr_args,
                    corr_host_array, optional_bool, mask_array_arg, match_args, match_host_array, splat_args, splat_host_array,
-                   splat_importance_array, photometric_args, photometric_host_array, census_args, census_channels,
-                   refine_args, refine_channels, inverse_search_args, inverse_search_channels, estimate_levels)
+                   splat_importance_array, photometric_args, photometric_host_array, census_args, refine_args,
+                   inverse_search_args, inverse_search_channels, estimate_levels, pair_channels, pair_host_arrays)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
@@ -390,10 +390,11 @@ def splat_importance(buf, n_px):
     return buf
 
 
-def photometric_tensors(near, far, field_shape, batch=None, prefix="Error computing photometric error: "):
+def photometric_tensors(near, far, field_shape, batch=None, prefix="Error computing photometric error: ", max_c=None, one_item=False):
     """The `near` and `far` of DeviceFlow.photometric (batch None) or DeviceFlowBatch.photometric (batch n) -> two
-    DeviceTensors of one shape, layout and dtype with the height and width of the field.  A float32 DeviceImage [H][W][C] is
-    taken as the channels-last tensor it is, on the same buffer.  `prefix` starts the messages (census passes its own)."""
+    DeviceTensors of one shape, layout and dtype with the height and width of the field, at most max_c channels (None: any
+    count) and -- one_item -- a single item.  A float32 DeviceImage [H][W][C] is taken as the channels-last tensor it is, on
+    the same buffer.  `prefix` starts the messages (census, refine and inverse_search pass their own)."""
     pair = []
     for name, t in (("near", near), ("far", far)):
         if isinstance(t, DeviceImage):
@@ -415,7 +416,52 @@ def photometric_tensors(near, far, field_shape, batch=None, prefix="Error comput
                          .format(prefix, (near.h, near.w), tuple(field_shape)))
     if batch is not None and (not near.batched or near.n != batch):
         raise ValueError("{}a batch of {} fields takes tensors of shape ({}, C, H, W), got {}".format(prefix, batch, batch, near.shape))
+    if max_c is not None:
+        pair_channels(near.channels, max_c, prefix)
+    if one_item and near.n != 1:
+        raise ValueError("{}one field takes tensors of shape (C, H, W) or (1, C, H, W), got {}".format(prefix, near.shape))
     return near, far
+
+
+# One body per operation of the image-pair families K21 ... K24 for DeviceFlow (batch None: ONE field and one of each mask
+# serve every item of the tensors, or -- refine, inverse_search -- the tensors hold one item) and DeviceFlowBatch (batch n: item
+# i with field i and masks i).  vecs, mask: the buffers of the field(s) of `shape` and reference `ref`; settings: what the
+# family's args.*_args returned.  They return the buffers of the launch wrapper; the two classes shape their own results.
+def error_map_op(launch, settings, max_c, prefix, vecs, mask, shape, ref, near, far, near_mask, far_mask, return_counts, quant,
+                 batch=None):
+    """photometric (launch photometric_launch, max_c None) and census (census_launch, 4) -> ((err, covered[, within]), the
+    counts buffer or None, the number of items)"""
+    near, far = photometric_tensors(near, far, shape, batch, prefix, max_c)
+    n_bytes = (batch or 1) * shape[0] * shape[1]
+    near_mask = mask_buffer_arg(near_mask, n_bytes, prefix, "near_mask")
+    far_mask = mask_buffer_arg(far_mask, n_bytes, prefix, "far_mask")
+    err, covered, within, counts = launch(
+        near.buf, far.buf, near.dtype, near.layout, near.n, near.channels, shape, vecs, mask, batch is None,
+        1 if ref == 's' else -1, *settings, near_mask=near_mask, far_mask=far_mask, want_counts=bool(return_counts), quant=quant)
+    return (err, covered) + ((within,) if within is not None else ()), counts, near.n
+
+
+def refine_op(settings, vecs, mask, shape, ref, near, far, near_mask, far_mask, valid, return_data, quant, batch=None):
+    """refine -> (vecs, data or None)"""
+    prefix = "Error refining flow: "
+    near, far = photometric_tensors(near, far, shape, batch, prefix, nat.REFINE_MAX_C, one_item=batch is None)
+    n_bytes = (batch or 1) * shape[0] * shape[1]
+    near_mask = mask_buffer_arg(near_mask, n_bytes, prefix, "near_mask")
+    far_mask = mask_buffer_arg(far_mask, n_bytes, prefix, "far_mask")
+    valid = mask_buffer_arg(valid, n_bytes, prefix, "valid")
+    return refine_launch(near.buf, far.buf, near.dtype, near.layout, near.n, near.channels, shape, vecs, mask,
+                         1 if ref == 's' else -1, *settings, near_mask=near_mask, far_mask=far_mask, valid=valid,
+                         want_data=bool(return_data), quant=quant)
+
+
+def inverse_search_op(settings, vecs, mask, shape, ref, near, far, return_patches, quant, batch=None):
+    """inverse_search -> (vecs, mask, patch_vecs or None, patch_ssd or None, (ny, nx))"""
+    prefix = "Error searching flow: "
+    near, far = photometric_tensors(near, far, shape, batch, prefix, nat.ISEARCH_MAX_C, one_item=batch is None)
+    if min(shape) < settings[0]:
+        raise ValueError("{}a {} x {} field holds no patch of {}".format(prefix, shape[0], shape[1], settings[0]))
+    return inverse_search_launch(near.buf, far.buf, near.dtype, near.layout, near.n, near.channels, shape, vecs, mask,
+                                 1 if ref == 's' else -1, *settings, want_patches=bool(return_patches), quant=quant)
 
 
 def upsample_weights(weights, factor, shape, batch=None):
@@ -738,18 +784,10 @@ class DeviceFlow:
         that synchronises.  `error` is what splat(mode='softmax', importance=error, alpha=-20.0) takes, without a copy.
         Not built: the window metrics SSIM and gradient constancy (the census distance is `census`), a mean or percentiles
         of the map, a backward pass, mixed dtypes or layouts, integer tensors, padding offsets.  The inputs are not modified."""
-        prefix = "Error computing photometric error: "
-        code, eps, threshold = photometric_args(metric, eps, threshold)
-        near, far = photometric_tensors(near, far, self.shape)
-        near_mask = mask_buffer_arg(near_mask, self.n_px, prefix, "near_mask")
-        far_mask = mask_buffer_arg(far_mask, self.n_px, prefix, "far_mask")
-        err, covered, within, counts = photometric_launch(
-            near.buf, far.buf, near.dtype, near.layout, near.n, near.channels, self.shape, self.vecs, self.mask, True,
-            1 if self.ref == 's' else -1, code, eps, threshold, near_mask, far_mask, want_counts=bool(return_counts), quant=quant)
-        res = (err, covered) + ((within,) if within is not None else ())
-        if return_counts:
-            res += ([(int(a), int(b)) for a, b in counts.to_host((near.n, 2), np.uint32)],)
-        return res
+        res, counts, n = error_map_op(photometric_launch, photometric_args(metric, eps, threshold), None,
+                                      "Error computing photometric error: ", self.vecs, self.mask, self.shape, self.ref,
+                                      near, far, near_mask, far_mask, return_counts, quant)
+        return res + ([(int(a), int(b)) for a, b in counts.to_host((n, 2), np.uint32)],) if return_counts else res
 
     def census(self, near, far, window=7, mode='soft', delta=None, noise=None, knee=None, min_count=None, threshold=None,
                near_mask=None, far_mask=None, return_counts=False, quant=nat.QUANT_OPENCV):
@@ -768,19 +806,10 @@ class DeviceFlow:
         (error <= threshold) as uint8, return_counts appends [(n_covered, n_within)] * N as Python ints -- the only option
         that synchronises.  Not built: more than 4 channels, a per-channel census, luma weights, SSIM, gradient constancy,
         other windows, a mean of the map, a backward pass.  The inputs are not modified."""
-        prefix = "Error computing census distance: "
-        settings = census_args(window, mode, delta, noise, knee, min_count, threshold)
-        near, far = photometric_tensors(near, far, self.shape, prefix=prefix)
-        census_channels(near.channels)
-        near_mask = mask_buffer_arg(near_mask, self.n_px, prefix, "near_mask")
-        far_mask = mask_buffer_arg(far_mask, self.n_px, prefix, "far_mask")
-        err, covered, within, counts = census_launch(
-            near.buf, far.buf, near.dtype, near.layout, near.n, near.channels, self.shape, self.vecs, self.mask, True,
-            1 if self.ref == 's' else -1, *settings, near_mask=near_mask, far_mask=far_mask, want_counts=bool(return_counts), quant=quant)
-        res = (err, covered) + ((within,) if within is not None else ())
-        if return_counts:
-            res += ([(int(a), int(b)) for a, b in counts.to_host((near.n, 2), np.uint32)],)
-        return res
+        res, counts, n = error_map_op(census_launch, census_args(window, mode, delta, noise, knee, min_count, threshold),
+                                      nat.CENSUS_MAX_C, "Error computing census distance: ", self.vecs, self.mask, self.shape,
+                                      self.ref, near, far, near_mask, far_mask, return_counts, quant)
+        return res + ([(int(a), int(b)) for a, b in counts.to_host((n, 2), np.uint32)],) if return_counts else res
 
     def refine(self, near, far, alpha=None, delta=None, zeta=None, eps=None, fixed_point=None, sor=None, omega=None,
                near_mask=None, far_mask=None, valid=None, return_data=False, quant=nat.QUANT_OPENCV):
@@ -800,18 +829,8 @@ class DeviceFlow:
         pixels with a data term.  Nothing synchronises.  Not built: gradient constancy, per-channel data terms, more than 4
         channels, a loop over warps or a pyramid, edge-aware smoothness, a choice of omega, an energy read-back, a backward
         pass, mixed dtypes or layouts.  The inputs are not modified."""
-        prefix = "Error refining flow: "
-        settings = refine_args(alpha, delta, zeta, eps, fixed_point, sor, omega)
-        near, far = photometric_tensors(near, far, self.shape, prefix=prefix)
-        refine_channels(near.channels)
-        if near.n != 1:
-            raise ValueError("{}one field takes tensors of shape (C, H, W) or (1, C, H, W), got {}".format(prefix, near.shape))
-        near_mask = mask_buffer_arg(near_mask, self.n_px, prefix, "near_mask")
-        far_mask = mask_buffer_arg(far_mask, self.n_px, prefix, "far_mask")
-        valid = mask_buffer_arg(valid, self.n_px, prefix, "valid")
-        out, data = refine_launch(near.buf, far.buf, near.dtype, near.layout, 1, near.channels, self.shape, self.vecs, self.mask,
-                                  1 if self.ref == 's' else -1, *settings, near_mask=near_mask, far_mask=far_mask, valid=valid,
-                                  want_data=bool(return_data), quant=quant)
+        out, data = refine_op(refine_args(alpha, delta, zeta, eps, fixed_point, sor, omega), self.vecs, self.mask, self.shape,
+                              self.ref, near, far, near_mask, far_mask, valid, return_data, quant)
         res = DeviceFlow(out, self.mask, self.shape, self.ref)          # buffers are immutable: the mask is shared
         return (res, data) if return_data else res
 
@@ -833,17 +852,8 @@ class DeviceFlow:
         synchronises.  Not built: OpenCV's propagation between neighbouring patches and its early exits, patches of 12 / 16
         px, per-channel residuals and more than 4 channels, near_mask / far_mask, affine patches, a backward pass; the pyramid
         is estimate_flow.  The inputs are not modified."""
-        prefix = "Error searching flow: "
-        settings = inverse_search_args(patch, stride, iterations, normalise, floor)
-        near, far = photometric_tensors(near, far, self.shape, prefix=prefix)
-        inverse_search_channels(near.channels)
-        if near.n != 1:
-            raise ValueError("{}one field takes tensors of shape (C, H, W) or (1, C, H, W), got {}".format(prefix, near.shape))
-        if min(self.shape) < settings[0]:
-            raise ValueError("{}a {} x {} field holds no patch of {}".format(prefix, self.shape[0], self.shape[1], settings[0]))
-        out, mask, pv, ps, grid = inverse_search_launch(near.buf, far.buf, near.dtype, near.layout, 1, near.channels, self.shape,
-                                                        self.vecs, self.mask, 1 if self.ref == 's' else -1, *settings,
-                                                        want_patches=bool(return_patches), quant=quant)
+        out, mask, pv, ps, grid = inverse_search_op(inverse_search_args(patch, stride, iterations, normalise, floor), self.vecs,
+                                                    self.mask, self.shape, self.ref, near, far, return_patches, quant)
         res = DeviceFlow(out, mask, self.shape, self.ref)
         return (res, pv, ps, grid) if return_patches else res
 

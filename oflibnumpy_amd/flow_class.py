@@ -445,14 +445,7 @@ class Flow(object):
         download."""
         prefix = "Error computing photometric error: "
         code, eps, threshold = dev.photometric_args(metric, eps, threshold)
-        near, far = dev.photometric_host_array(near, layout, "near"), dev.photometric_host_array(far, layout, "far")
-        if near.shape != far.shape:
-            raise ValueError("{}the arrays need the same shape, got {} and {}".format(prefix, near.shape, far.shape))
-        if near.dtype != far.dtype:
-            raise TypeError("{}the arrays need the same dtype, got {} and {}".format(prefix, near.dtype, far.dtype))
-        n, c, h, w, batched = dev.tensor_args(dev.tensor_logical_shape(near.shape, layout), layout, near.dtype.name)
-        if (h, w) != tuple(self.shape):
-            raise ValueError("{}arrays and flow need the same height and width, got {} and {}".format(prefix, (h, w), tuple(self.shape)))
+        near, far, n, c, batched = dev.pair_host_arrays(near, far, layout, self.shape, prefix)
         near_mask = None if near_mask is None else dev.mask_array_arg(near_mask, self.shape, prefix, "near_mask")
         far_mask = None if far_mask is None else dev.mask_array_arg(far_mask, self.shape, prefix, "far_mask")
         res = dev.photometric_host(near, far, layout, n, c, self._vecs, self._mask, 1 if self._ref == 's' else -1, code, eps,
@@ -474,15 +467,7 @@ class Flow(object):
         DeviceFlow.census's.  One upload, one launch, one download."""
         prefix = "Error computing census distance: "
         settings = dev.census_args(window, mode, delta, noise, knee, min_count, threshold)
-        near, far = dev.photometric_host_array(near, layout, "near", prefix), dev.photometric_host_array(far, layout, "far", prefix)
-        if near.shape != far.shape:
-            raise ValueError("{}the arrays need the same shape, got {} and {}".format(prefix, near.shape, far.shape))
-        if near.dtype != far.dtype:
-            raise TypeError("{}the arrays need the same dtype, got {} and {}".format(prefix, near.dtype, far.dtype))
-        n, c, h, w, batched = dev.tensor_args(dev.tensor_logical_shape(near.shape, layout), layout, near.dtype.name)
-        dev.census_channels(c)
-        if (h, w) != tuple(self.shape):
-            raise ValueError("{}arrays and flow need the same height and width, got {} and {}".format(prefix, (h, w), tuple(self.shape)))
+        near, far, n, c, batched = dev.pair_host_arrays(near, far, layout, self.shape, prefix, nat.CENSUS_MAX_C)
         near_mask = None if near_mask is None else dev.mask_array_arg(near_mask, self.shape, prefix, "near_mask")
         far_mask = None if far_mask is None else dev.mask_array_arg(far_mask, self.shape, prefix, "far_mask")
         res = dev.census_host(near, far, layout, n, c, self._vecs, self._mask, 1 if self._ref == 's' else -1, *settings,
@@ -504,17 +489,7 @@ class Flow(object):
         launches, one download."""
         prefix = "Error refining flow: "
         settings = dev.refine_args(alpha, delta, zeta, eps, fixed_point, sor, omega)
-        near, far = dev.photometric_host_array(near, layout, "near", prefix), dev.photometric_host_array(far, layout, "far", prefix)
-        if near.shape != far.shape:
-            raise ValueError("{}the arrays need the same shape, got {} and {}".format(prefix, near.shape, far.shape))
-        if near.dtype != far.dtype:
-            raise TypeError("{}the arrays need the same dtype, got {} and {}".format(prefix, near.dtype, far.dtype))
-        n, c, h, w, batched = dev.tensor_args(dev.tensor_logical_shape(near.shape, layout), layout, near.dtype.name)
-        dev.refine_channels(c)
-        if n != 1:
-            raise ValueError("{}one flow takes one item, got {}".format(prefix, n))
-        if (h, w) != tuple(self.shape):
-            raise ValueError("{}arrays and flow need the same height and width, got {} and {}".format(prefix, (h, w), tuple(self.shape)))
+        near, far, _, c, _ = dev.pair_host_arrays(near, far, layout, self.shape, prefix, nat.REFINE_MAX_C, one_item=True)
         near_mask = None if near_mask is None else dev.mask_array_arg(near_mask, self.shape, prefix, "near_mask")
         far_mask = None if far_mask is None else dev.mask_array_arg(far_mask, self.shape, prefix, "far_mask")
         valid = None if valid is None else dev.mask_array_arg(valid, self.shape, prefix, "valid")
@@ -537,19 +512,9 @@ class Flow(object):
         DeviceFlow.inverse_search's; the pyramid is estimate_flow.  One upload, three launches, one download."""
         prefix = "Error searching flow: "
         settings = dev.inverse_search_args(patch, stride, iterations, normalise, floor)
-        near, far = dev.photometric_host_array(near, layout, "near", prefix), dev.photometric_host_array(far, layout, "far", prefix)
-        if near.shape != far.shape:
-            raise ValueError("{}the arrays need the same shape, got {} and {}".format(prefix, near.shape, far.shape))
-        if near.dtype != far.dtype:
-            raise TypeError("{}the arrays need the same dtype, got {} and {}".format(prefix, near.dtype, far.dtype))
-        n, c, h, w, batched = dev.tensor_args(dev.tensor_logical_shape(near.shape, layout), layout, near.dtype.name)
-        dev.inverse_search_channels(c)
-        if n != 1:
-            raise ValueError("{}one flow takes one item, got {}".format(prefix, n))
-        if (h, w) != tuple(self.shape):
-            raise ValueError("{}arrays and flow need the same height and width, got {} and {}".format(prefix, (h, w), tuple(self.shape)))
-        if min(h, w) < settings[0]:
-            raise ValueError("{}a {} x {} flow holds no patch of {}".format(prefix, h, w, settings[0]))
+        near, far, _, c, _ = dev.pair_host_arrays(near, far, layout, self.shape, prefix, nat.ISEARCH_MAX_C, one_item=True)
+        if min(self.shape) < settings[0]:
+            raise ValueError("{}a {} x {} flow holds no patch of {}".format(prefix, self.shape[0], self.shape[1], settings[0]))
         vecs, mask, pv, ps, grid = dev.inverse_search_host(near, far, layout, 1, c, self._vecs, self._mask,
                                                            1 if self._ref == 's' else -1, *settings,
                                                            want_patches=bool(return_patches), quant=quant)

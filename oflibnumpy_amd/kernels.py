@@ -592,6 +592,40 @@ def splat_host(src, layout, n, c, vecs, mask, mode, alpha, min_weight, frac_bits
     return dst, valid.view(np.bool_), weight, None if counters is None else (int(counters[0]), int(counters[1]))
 
 
+# ------------------------------------------------------------------------------ K21 ... K24: what the image-pair families share
+def _pair_head(near, far, dtype, layout, n, c, shape):
+    """the arguments every native entry of K21 ... K24 begins with; near, far: pointers"""
+    return near, far, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, shape[0], shape[1]
+
+
+def _pair_error_launch(entry, near, far, dtype, layout, n, c, shape, flow, fmask, flow_shared, sign, settings, threshold,
+                       near_mask, far_mask, want_err, want_covered, want_counts, quant, stream):
+    """K21's and K22's device entries differ in their `settings` alone: the outputs allocated and the call made once"""
+    px = n * shape[0] * shape[1]
+    err = DeviceBuffer(px * 4) if want_err else None
+    covered = DeviceBuffer(px) if want_covered else None
+    within = DeviceBuffer(px) if threshold is not None else None
+    counts = DeviceBuffer.zeros(n * 8, stream) if want_counts else None
+    nat.check(entry(*_pair_head(near.ptr, far.ptr, dtype, layout, n, c, shape), flow.ptr, fmask.ptr, 1 if flow_shared else 0, sign,
+                    _ptr(near_mask), _ptr(far_mask), *settings, np.float32(0) if threshold is None else threshold,
+                    _ptr(err), _ptr(covered), _ptr(within), _ptr(counts), quant, stream))
+    return err, covered, within, counts
+
+
+def _pair_error_host(entry, near, far, layout, n, c, vecs, mask, sign, settings, threshold, near_mask, far_mask, quant):
+    """the same for their host entries: the result arrays made, the call, and the uint8 maps viewed as bool"""
+    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(mask)
+    h, w = vecs.shape[:2]
+    err, covered = np.empty((n, h, w), np.float32), np.empty((n, h, w), np.uint8)
+    within = np.empty((n, h, w), np.uint8) if threshold is not None else None
+    nat.check(entry(*_pair_head(near.ctypes.data, far.ctypes.data, near.dtype.name, layout, n, c, (h, w)), vecs.ctypes.data,
+                    m.ctypes.data, 1, sign, _host_ptr(near_mask), _host_ptr(far_mask), *settings,
+                    np.float32(0) if threshold is None else threshold, err.ctypes.data, covered.ctypes.data, _host_ptr(within),
+                    None, quant))
+    res = (err, covered.view(np.bool_))
+    return res + (within.view(np.bool_),) if within is not None else res
+
+
 # ------------------------------------------------------------------------------ K21: photometric error of a warp
 def photometric_launch(near, far, dtype, layout, n, c, shape, flow, fmask, flow_shared, sign, metric, eps, threshold=None,
                        near_mask=None, far_mask=None, want_err=True, want_covered=True, want_counts=False,
@@ -601,16 +635,8 @@ def photometric_launch(near, far, dtype, layout, n, c, shape, flow, fmask, flow_
     [H][W] each when flow_shared, else n back to back.  metric, eps, threshold: from args.photometric_args (threshold None:
     no `within`).  -> (err or None, covered or None, within or None, counts or None): float32, uint8 and uint8 [n][H][W]
     and the zeroed-then-added uint32 [n][2] = {covered, within} words, all still in HBM."""
-    px = n * shape[0] * shape[1]
-    err = DeviceBuffer(px * 4) if want_err else None
-    covered = DeviceBuffer(px) if want_covered else None
-    within = DeviceBuffer(px) if threshold is not None else None
-    counts = DeviceBuffer.zeros(n * 8, stream) if want_counts else None
-    nat.check(_lib().ofl_photometric_dev(near.ptr, far.ptr, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, shape[0], shape[1],
-                                         flow.ptr, fmask.ptr, 1 if flow_shared else 0, sign, _ptr(near_mask), _ptr(far_mask),
-                                         metric, eps, np.float32(0) if threshold is None else threshold,
-                                         _ptr(err), _ptr(covered), _ptr(within), _ptr(counts), quant, stream))
-    return err, covered, within, counts
+    return _pair_error_launch(_lib().ofl_photometric_dev, near, far, dtype, layout, n, c, shape, flow, fmask, flow_shared, sign,
+                              (metric, eps), threshold, near_mask, far_mask, want_err, want_covered, want_counts, quant, stream)
 
 
 def photometric_host(near, far, layout, n, c, vecs, mask, sign, metric, eps, threshold=None, near_mask=None, far_mask=None,
@@ -618,16 +644,8 @@ def photometric_host(near, far, layout, n, c, vecs, mask, sign, metric, eps, thr
     """K21 for host arrays through ofl_photometric (upload, one launch, download): near, far contiguous float32 or float16
     arrays of one dtype in the memory order of `layout`, ONE field (vecs (H, W, 2), mask) and one of each mask (uint8
     (H, W) or None) for all `n` items -> (err float32, covered bool[, within bool]), each (n, H, W)."""
-    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(mask)
-    h, w = vecs.shape[:2]
-    err, covered = np.empty((n, h, w), np.float32), np.empty((n, h, w), np.uint8)
-    within = np.empty((n, h, w), np.uint8) if threshold is not None else None
-    nat.check(_lib().ofl_photometric(near.ctypes.data, far.ctypes.data, _TENSOR_EL[near.dtype.name], _TENSOR_LAYOUT[layout],
-                                     n, c, h, w, vecs.ctypes.data, m.ctypes.data, 1, sign, _host_ptr(near_mask),
-                                     _host_ptr(far_mask), metric, eps, np.float32(0) if threshold is None else threshold,
-                                     err.ctypes.data, covered.ctypes.data, _host_ptr(within), None, quant))
-    res = (err, covered.view(np.bool_))
-    return res + (within.view(np.bool_),) if within is not None else res
+    return _pair_error_host(_lib().ofl_photometric, near, far, layout, n, c, vecs, mask, sign, (metric, eps), threshold,
+                            near_mask, far_mask, quant)
 
 
 # ------------------------------------------------------------------------------ K22: census distance of a warp over a window
@@ -639,32 +657,17 @@ def census_launch(near, far, dtype, layout, n, c, shape, flow, fmask, flow_share
     threshold: from args.census_args (threshold None: no `within`).  -> (err or None, covered or None, within or None,
     counts or None): float32, uint8 and uint8 [n][H][W] and the zeroed-then-added uint32 [n][2] = {covered, within} words,
     all still in HBM."""
-    px = n * shape[0] * shape[1]
-    err = DeviceBuffer(px * 4) if want_err else None
-    covered = DeviceBuffer(px) if want_covered else None
-    within = DeviceBuffer(px) if threshold is not None else None
-    counts = DeviceBuffer.zeros(n * 8, stream) if want_counts else None
-    nat.check(_lib().ofl_census_dev(near.ptr, far.ptr, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, shape[0], shape[1],
-                                    flow.ptr, fmask.ptr, 1 if flow_shared else 0, sign, _ptr(near_mask), _ptr(far_mask),
-                                    window, mode, p0, p1, min_count, np.float32(0) if threshold is None else threshold,
-                                    _ptr(err), _ptr(covered), _ptr(within), _ptr(counts), quant, stream))
-    return err, covered, within, counts
+    return _pair_error_launch(_lib().ofl_census_dev, near, far, dtype, layout, n, c, shape, flow, fmask, flow_shared, sign,
+                              (window, mode, p0, p1, min_count), threshold, near_mask, far_mask, want_err, want_covered,
+                              want_counts, quant, stream)
 
 
 def census_host(near, far, layout, n, c, vecs, mask, sign, window, mode, p0, p1, min_count, threshold=None, near_mask=None,
                 far_mask=None, quant=nat.QUANT_OPENCV):
     """K22 for host arrays through ofl_census (upload, one launch, download): arrays, field and masks as in
     photometric_host -> (err float32, covered bool[, within bool]), each (n, H, W)."""
-    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(mask)
-    h, w = vecs.shape[:2]
-    err, covered = np.empty((n, h, w), np.float32), np.empty((n, h, w), np.uint8)
-    within = np.empty((n, h, w), np.uint8) if threshold is not None else None
-    nat.check(_lib().ofl_census(near.ctypes.data, far.ctypes.data, _TENSOR_EL[near.dtype.name], _TENSOR_LAYOUT[layout],
-                                n, c, h, w, vecs.ctypes.data, m.ctypes.data, 1, sign, _host_ptr(near_mask), _host_ptr(far_mask),
-                                window, mode, p0, p1, min_count, np.float32(0) if threshold is None else threshold,
-                                err.ctypes.data, covered.ctypes.data, _host_ptr(within), None, quant))
-    res = (err, covered.view(np.bool_))
-    return res + (within.view(np.bool_),) if within is not None else res
+    return _pair_error_host(_lib().ofl_census, near, far, layout, n, c, vecs, mask, sign, (window, mode, p0, p1, min_count),
+                            threshold, near_mask, far_mask, quant)
 
 
 # ------------------------------------------------------------------------------ K23: variational refinement of a field
@@ -679,7 +682,7 @@ def refine_launch(near, far, dtype, layout, n, c, shape, flow, fmask, sign, alph
     work = DeviceBuffer(nbytes)
     out = DeviceBuffer(n * h * w * 8)
     data = DeviceBuffer(n * h * w) if want_data else None
-    nat.check(lib.ofl_refine_dev(near.ptr, far.ptr, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, h, w, flow.ptr, fmask.ptr, sign,
+    nat.check(lib.ofl_refine_dev(*_pair_head(near.ptr, far.ptr, dtype, layout, n, c, shape), flow.ptr, fmask.ptr, sign,
                                  _ptr(near_mask), _ptr(far_mask), _ptr(valid), alpha, delta, zeta, eps, fixed_point, sor, omega,
                                  work.ptr, nbytes, out.ptr, _ptr(data), quant, stream))
     return out, data
@@ -694,8 +697,8 @@ def refine_host(near, far, layout, n, c, vecs, mask, sign, alpha, delta, zeta, e
     h, w = vecs.shape[-3:-1]
     out = np.empty((n, h, w, 2), np.float32)
     data = np.empty((n, h, w), np.uint8) if want_data else None
-    nat.check(_lib().ofl_refine(near.ctypes.data, far.ctypes.data, _TENSOR_EL[near.dtype.name], _TENSOR_LAYOUT[layout],
-                                n, c, h, w, vecs.ctypes.data, m.ctypes.data, sign, _host_ptr(near_mask), _host_ptr(far_mask),
+    nat.check(_lib().ofl_refine(*_pair_head(near.ctypes.data, far.ctypes.data, near.dtype.name, layout, n, c, (h, w)),
+                                vecs.ctypes.data, m.ctypes.data, sign, _host_ptr(near_mask), _host_ptr(far_mask),
                                 _host_ptr(valid), alpha, delta, zeta, eps, fixed_point, sor, omega,
                                 out.ctypes.data, _host_ptr(data), quant))
     return out, None if data is None else data.view(np.bool_)
@@ -716,7 +719,7 @@ def inverse_search_launch(near, far, dtype, layout, n, c, shape, flow, fmask, si
     out, mask = DeviceBuffer(n * h * w * 8), DeviceBuffer(n * h * w)
     pv = DeviceBuffer(n * ny * nx * 8) if want_patches else None
     ps = DeviceBuffer(n * ny * nx * 4) if want_patches else None
-    nat.check(lib.ofl_inverse_search_dev(near.ptr, far.ptr, _TENSOR_EL[dtype], _TENSOR_LAYOUT[layout], n, c, h, w, _ptr(flow),
+    nat.check(lib.ofl_inverse_search_dev(*_pair_head(near.ptr, far.ptr, dtype, layout, n, c, shape), _ptr(flow),
                                          _ptr(fmask), sign, patch, stride, iterations, 1 if normalise else 0, floor,
                                          work.ptr, nbytes, out.ptr, mask.ptr, _ptr(pv), _ptr(ps), quant, stream))
     return out, mask, pv, ps, (ny, nx)
@@ -733,7 +736,7 @@ def inverse_search_host(near, far, layout, n, c, vecs, mask, sign, patch, stride
     out, om = np.empty((n, h, w, 2), np.float32), np.empty((n, h, w), np.uint8)
     pv = np.empty((n, ny, nx, 2), np.float32) if want_patches else None
     ps = np.empty((n, ny, nx), np.float32) if want_patches else None
-    nat.check(_lib().ofl_inverse_search(near.ctypes.data, far.ctypes.data, _TENSOR_EL[near.dtype.name], _TENSOR_LAYOUT[layout],
-                                        n, c, h, w, vecs.ctypes.data, m.ctypes.data, sign, patch, stride, iterations,
+    nat.check(_lib().ofl_inverse_search(*_pair_head(near.ctypes.data, far.ctypes.data, near.dtype.name, layout, n, c, (h, w)),
+                                        vecs.ctypes.data, m.ctypes.data, sign, patch, stride, iterations,
                                         1 if normalise else 0, floor, out.ctypes.data, om.ctypes.data, _host_ptr(pv), _host_ptr(ps), quant))
     return out, om.view(np.bool_), pv, ps, (ny, nx)
