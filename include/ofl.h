@@ -1322,6 +1322,53 @@ int ofl_inverse_search(const void *near, const void *far, int elem, int layout, 
                        const float *flow, const uint8_t *fmask, int sign, int patch, int stride, int iterations,
                        int normalise, float floor, float *out, uint8_t *out_mask, float *patch_vecs, float *patch_ssd, int quant);
 
+/* ------------------------------------------------------------------ K25: a sequence of fields accumulated into one
+ * Chains the consecutive flows of a video into one long-range field: what a host loop of L - 1 Flow.combine_with(mode=3)
+ * calls (flow_class.py:1412-1422) computes, in ONE launch, with the accumulated vector in registers, no intermediate
+ * field and no read-back.  A sequence is L fields of one shape and ONE reference, field k mapping frame k to frame k + 1;
+ * sign = +1 for 's', which walks k = 0, 1, ..., L - 1, and -1 for 't', which walks k = L - 1, ..., 0.  Per pixel (x, y), with
+ * k0 the first field of the walk, every operation float32 and rounded once:
+ *     acc = f_k0[y][x];  m = mask_k0[y][x]
+ *     for every later k of the walk:
+ *         tap = the bilinear tap of (x, y) + sign * acc                 (map_coord / make_tap, `quant` as in K1 / K2)
+ *         s   = f_k's four taps blended (0 outside the frame);  am = mask_k's four taps blended as 0.0f / 1.0f
+ *         m   = m & (am == 1.0f)
+ *         acc = (acc.u + s.u, acc.v + s.v)
+ * This is ofl_compose3_dev with fb = acc and fa = f_k, folded over the sequence, bit for bit, vectors and masks:
+ *     's':  F <- F.combine_with(f_k, 3)  for k = 1 ... L - 1
+ *     't':  G <- f_k.combine_with(G, 3)  for k = L - 2 ... 0
+ * For 't' this right fold is the only association that is a per-pixel walk.  The left fold, ((f_0 (+) f_1) (+) f_2) ...,
+ * interpolates the accumulated field and is NOT what this entry computes.  There is NO zero-flow short cut in either `quant`
+ * mode (as in K13: the reference's early exits are a host decision) and no early exit that changes a value.  The non-finite
+ * rules above (K1 / K2 / K12 / K13) hold: a non-finite accumulated vector samples nothing, the pixel is invalid from that
+ * step on.  L = 1 copies the field.
+ *     flows   float32 [S][L][H][W][2], masks uint8 [S][L][H][W]: S sequences of L fields each, back to back
+ *     out     float32 [S][H][W][2],    mout  uint8 [S][H][W]: required
+ *     part_vecs float32 [S][L][H][W][2] and part_masks uint8 [S][L][H][W], both or neither (NULL): the accumulated field
+ *             after each step, stored at the batch index of the field taken last -- for 's' entry k is the composition of
+ *             fields 0 ... k and entry L - 1 the result, for 't' entry k is the composition of fields k ... L - 1 and entry
+ *             0 the result; the entry at k0 is that field itself
+ *     lost_at int32 [S][H][W] or NULL: the batch index k of the field at which the pixel's mask first became 0 -- k0 for a
+ *             pixel whose own mask in the first-walked field is unset --, -1 for a pixel still valid at the end
+ * An output that is NULL is not written.  H and W in [1, 32766], L >= 1, S in [1, 65535] (the grid's z).  flows, out and
+ * part_vecs must be 8-byte, lost_at 4-byte aligned; the outputs must not overlap the inputs or each other.
+ * One launch: one lane per pixel, L - 1 dependent gathers, every tap its own guarded 8-byte and 1-byte load; no LDS, no
+ * atomics, no workspace, 64-bit offsets across fields.  Bytes per pixel: reads 9 L; writes 9, + 9 L with the partial
+ * results, + 4 with lost_at -- where the chain of L - 1 ofl_compose3_dev launches reads 18 (L - 1) and writes 9 (L - 1).
+ * A bad argument -- a NULL flows / masks / out / mout, sizes, L or S out of range, sign not +-1, an unknown quant, one
+ * partial buffer without the other, an overlap, a misaligned pointer -- returns OFL_E_INVALID with a message before any
+ * launch.  The _dev entry is asynchronous; the host entry takes host pointers, uploads, launches once, downloads and
+ * synchronises.
+ * Not built: a tiled / LDS path for the first, most coherent steps, modes 1 and 2, sequences of mixed reference, the left
+ * fold for 't', re-anchoring or filling lost pixels inside the call (ofl_fill_dev does that afterwards), packed masks, a
+ * backward pass.
+ */
+int ofl_compose_sequence_dev(const float *flows, const uint8_t *masks, int sign, int H, int W, int L, int S,
+                             float *out, uint8_t *mout, float *part_vecs, uint8_t *part_masks, int32_t *lost_at,
+                             int quant, void *stream);
+int ofl_compose_sequence(const float *flows, const uint8_t *masks, int sign, int H, int W, int L, int S,
+                         float *out, uint8_t *mout, float *part_vecs, uint8_t *part_masks, int32_t *lost_at, int quant);
+
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`
  * to all ranks over xGMI, and -- for one huge field warped with ref 's' in slab mode (above) -- one all-gather of the

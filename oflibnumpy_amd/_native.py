@@ -188,6 +188,8 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _ci, _vp]),
     "ofl_inverse_search": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cf,
                                  _vp, _vp, _vp, _vp, _ci]),
+    "ofl_compose_sequence_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp]),
+    "ofl_compose_sequence": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

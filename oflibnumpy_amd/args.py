@@ -271,6 +271,28 @@ def consistency_args(alpha=None, beta=None):
     return out[0], out[1]
 
 
+# -- a sequence of fields accumulated into one (K25)
+SEQUENCE_PREFIX = "Error combining flow sequence: "
+
+
+def sequence_args(n, length=None, quant=0, return_partials=False, return_lost_at=False):
+    """Validation of the settings of a sequence accumulation over `n` fields, on the host before any device work
+    -> (length, n_seq, quant, return_partials, return_lost_at).  length: None for one sequence of all n fields, else an int
+    in 1 ... n that divides n; quant: 0 (the 1/32-px snap) or 1 (exact).  A bool or a non-integer where an integer is due,
+    or a non-bool flag, is a TypeError; a value out of range a ValueError."""
+    length = n if length is None else length
+    for name, value in (("length", length), ("quant", quant)):
+        if not _is_integer(value):
+            raise TypeError("{}{} needs to be an integer, got {}".format(SEQUENCE_PREFIX, name.capitalize(), type(value).__name__))
+    if length < 1 or n % length:
+        raise ValueError("{}Length needs to be a positive divisor of the number of flows {}, got {}".format(SEQUENCE_PREFIX, n, length))
+    if quant not in (0, 1):
+        raise ValueError("{}Quant needs to be 0 (QUANT_OPENCV) or 1 (QUANT_EXACT), got {}".format(SEQUENCE_PREFIX, quant))
+    return_partials = optional_bool(return_partials, False, SEQUENCE_PREFIX + "Return_partials needs to be a boolean")
+    return_lost_at = optional_bool(return_lost_at, False, SEQUENCE_PREFIX + "Return_lost_at needs to be a boolean")
+    return int(length), n // int(length), int(quant), return_partials, return_lost_at
+
+
 # -- what the image-pair families K21 ... K24 share: their number settings, the channel limit and the two host arrays
 def _float32_rounded(value, name, prefix, none_ok=True):
     """a number -> float32, +-inf where float32 cannot hold it; a bool or a non-number is a TypeError (none_ok: the caller

@@ -191,6 +191,30 @@ class DeviceFlowBatch:
         b = DeviceFlowBatch.wrap(self.n, self.shape, self.ref, out, mask)
         return (b, pv, ps, grid) if return_patches else b
 
+    def combine_sequence(self, length=None, quant=nat.QUANT_OPENCV, return_partials=False, return_lost_at=False):
+        """The batch as a SEQUENCE -- field k maps frame k to frame k + 1 -- accumulated into one long-range field in ONE
+        launch of K25 (ofl_compose_sequence_dev): per pixel a walk through the fields with the accumulated vector in
+        registers, mode 3 of combine_with folded over the sequence, bit for bit,
+            ref 's':  F <- F.combine_with(f_k, 3)  for k = 1 ... n - 1
+            ref 't':  G <- f_k.combine_with(G, 3)  for k = n - 2 ... 0
+        without the zero-flow early exits (as in consistency).  For 't' this right fold is the only association that is a
+        per-pixel walk; the left fold, ((f_0 (+) f_1) (+) f_2) ..., interpolates the accumulated field and is NOT what this
+        computes.  length: None -- the whole batch is one sequence, the result a DeviceFlow -- or a divisor of n: n / length
+        sequences of `length` consecutive fields each, the result an unpacked DeviceFlowBatch of n / length fields.
+        return_partials appends an unpacked DeviceFlowBatch of n fields, the accumulated field after each step at the index of
+        the field taken last ('s': entry k composes fields 0 ... k of its sequence; 't': entry k composes fields k ...
+        length - 1); return_lost_at an int32 DeviceBuffer [n / length][H][W], the index within its sequence of the field at
+        which the pixel's mask first became 0, -1 where it is still set at the end.  A packed batch is read through its byte
+        masks.  Nothing synchronises."""
+        whole = length is None
+        length, n_seq, quant, return_partials, return_lost_at = dev.sequence_args(self.n, length, quant, return_partials, return_lost_at)
+        out, mout, pv, pm, lost = dev.sequence_launch(self.vecs, self.mask, 1 if self.ref == 's' else -1, self.shape, length, n_seq,
+                                                      want_partials=return_partials, want_lost_at=return_lost_at, quant=quant)
+        res = dev.DeviceFlow(out, mout, self.shape, self.ref) if whole else DeviceFlowBatch.wrap(n_seq, self.shape, self.ref, out, mout)
+        extra = ((DeviceFlowBatch.wrap(self.n, self.shape, self.ref, pv, pm),) if return_partials else ()) + \
+                ((lost,) if return_lost_at else ())
+        return (res,) + extra if extra else res
+
     def error(self, gt, thresholds=None, outlier=None, speed_edges=None, use_est_mask=True, return_map=False, return_outliers=False):
         """self[i].error(gt[i], ...) for every i in ONE launch of K14 (DeviceFlow.error): `gt` a batch of the same length,
         shape and reference.  -> a DeviceFlowError whose read() gives a list of n FlowErrorStats (the one read-back, 96 bytes

@@ -34,7 +34,8 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rul
                    consistency_args, error_args, fill_args, median_args, upsample_args, upsample_weights_array, corr_args,
                    corr_host_array, optional_bool, mask_array_arg, match_args, match_host_array, splat_args, splat_host_array,
                    splat_importance_array, photometric_args, photometric_host_array, census_args, refine_args,
-                   inverse_search_args, inverse_search_channels, estimate_levels, pair_channels, pair_host_arrays)
+                   inverse_search_args, inverse_search_channels, estimate_levels, pair_channels, pair_host_arrays,
+                   sequence_args, SEQUENCE_PREFIX)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
                       compose3_bits_launch, mask_bits_bytes, mask_pack, mask_unpack, visualise_range_launch, FitField,
                       flow_from_matrix_launch, _valid_mask, _mask_buffer, _mask_and, resize_host, grid_minus, sample_points,
@@ -43,7 +44,8 @@ from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stat
                       FlowErrorStats, fill_launch, fill_host, median_launch, median_host, upsample_launch,
                       upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host, match_launch, match_host, splat_launch, splat_host,
                       photometric_launch, photometric_host, census_launch, census_host,
-                      refine_launch, refine_host, tensor_halve_launch, inverse_search_launch, inverse_search_host)
+                      refine_launch, refine_host, tensor_halve_launch, inverse_search_launch, inverse_search_host,
+                      sequence_launch, sequence_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
                       SLAB_ERR_LIST, slab_list_bytes, comm_allgather, scatter_slab_stars, scatter_slab_finish, _slab_timeout,
                       scatter_slab, scatter_host, scatter_query, scatter_query_resident)

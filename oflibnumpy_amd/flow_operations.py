@@ -12,7 +12,7 @@ nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
            'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow',
            'upsample_flow_convex', 'correlation_lookup', 'global_match', 'splat_flow', 'photometric_error', 'census_error',
-           'refine_flow', 'inverse_search_flow', 'estimate_flow', 'halve_tensor']
+           'refine_flow', 'inverse_search_flow', 'estimate_flow', 'halve_tensor', 'combine_flow_sequence']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -241,6 +241,56 @@ def estimate_flow(img1: nd, img2: nd, ref: str = 't', levels: int = None, patch:
                             patch, stride, iterations, refine, refine_args, init)
     vecs, mask = out.to_host()
     return Flow(vecs, ref, mask)
+
+
+def combine_flow_sequence(flows, ref: str = None, masks: nd = None, quant: int = 0, return_partials: bool = False,
+                          return_lost_at: bool = False):
+    """The consecutive flows of a sequence -- flow k maps frame k to frame k + 1 -- accumulated into ONE long-range Flow
+    (DeviceFlowBatch.combine_sequence: K25, one upload, one launch, one download): mode 3 of combine_with folded over the
+    sequence without its zero-flow early exits,
+        ref 's':  F <- F.combine_with(flow_k, 3)  for k = 1 ... n - 1
+        ref 't':  G <- flow_k.combine_with(G, 3)  for k = n - 2 ... 0
+    For 't' this right fold is the only association that is a per-pixel walk; the left fold, ((f_0 (+) f_1) (+) f_2) ...,
+    interpolates the accumulated field and is NOT what this computes.  flows: a list of Flow objects of one shape and
+    reference, or an (n, H, W, 2) array with the reference `ref` and optional (n, H, W) `masks` (None: all valid).
+    -> a Flow; return_partials appends a list of n Flows, the accumulated flow after each step at the index of the flow
+    taken last ('s': entry k composes flows 0 ... k; 't': entry k composes flows k ... n - 1); return_lost_at an int32
+    (H, W) array, the index of the flow at which the pixel's mask first became False, -1 where it is True at the end.
+    Not a function of the reference, whose users write the loop of combine_with calls."""
+    from . import device as dev
+    prefix = dev.SEQUENCE_PREFIX
+    if isinstance(flows, np.ndarray):
+        if flows.ndim != 4 or flows.shape[3] != 2 or flows.shape[0] == 0:
+            raise ValueError("{}Flows need to be a numpy array of shape (n, H, W, 2), n > 0, got {}".format(prefix, flows.shape))
+        if masks is not None:
+            if not isinstance(masks, np.ndarray):
+                raise TypeError("{}Masks need to be a numpy array or None".format(prefix))
+            if masks.shape != flows.shape[:3]:
+                raise ValueError("{}Masks need to have shape {}, got {}".format(prefix, flows.shape[:3], masks.shape))
+        flows = [Flow(flows[k], ref, None if masks is None else masks[k]) for k in range(flows.shape[0])]
+    elif isinstance(flows, (list, tuple)):
+        if not flows:
+            raise ValueError("{}Flows need to hold at least one flow".format(prefix))
+        if not all(isinstance(f, Flow) for f in flows):
+            raise TypeError("{}Flows need to be a list of Flow objects or a numpy array".format(prefix))
+        if masks is not None:
+            raise ValueError("{}Masks go with a numpy array of flows; Flow objects carry their own".format(prefix))
+        if any(f.shape != flows[0].shape for f in flows):
+            raise ValueError("{}Flow fields need to have the same shape".format(prefix))
+        if any(f.ref != flows[0].ref for f in flows):
+            raise ValueError("{}Flow fields need to have the same reference".format(prefix))
+    else:
+        raise TypeError("{}Flows need to be a list of Flow objects or a numpy array".format(prefix))
+    _, _, quant, return_partials, return_lost_at = dev.sequence_args(len(flows), None, quant, return_partials, return_lost_at)
+    ref = flows[0].ref
+    out, mout, pv, pm, lost = dev.sequence_host(np.stack([f.vecs for f in flows]), np.stack([f.mask for f in flows]),
+                                                1 if ref == 's' else -1, return_partials, return_lost_at, quant)
+    res = (Flow(out, ref, mout),)
+    if return_partials:
+        res += ([Flow(pv[k], ref, pm[k]) for k in range(len(flows))],)
+    if return_lost_at:
+        res += (lost,)
+    return res if len(res) > 1 else res[0]
 
 
 def halve_tensor(arr: nd, layout: str = 'chw') -> nd:

@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching, K20 splatting, K21 photometric error, K22 census distance, K23 variational refinement and K24 dense inverse search.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching, K20 splatting, K21 photometric error, K22 census distance, K23 variational refinement, K24 dense inverse search and K25 sequence accumulation.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -740,3 +740,35 @@ def inverse_search_host(near, far, layout, n, c, vecs, mask, sign, patch, stride
                                         vecs.ctypes.data, m.ctypes.data, sign, patch, stride, iterations,
                                         1 if normalise else 0, floor, out.ctypes.data, om.ctypes.data, _host_ptr(pv), _host_ptr(ps), quant))
     return out, om.view(np.bool_), pv, ps, (ny, nx)
+
+
+# ------------------------------------------------------------------------------ K25: a sequence of fields accumulated into one
+def sequence_launch(vecs, mask, sign, shape, length, n_seq=1, want_partials=False, want_lost_at=False, quant=nat.QUANT_OPENCV,
+                    stream=None):
+    """K25 (ofl_compose_sequence_dev) on `n_seq` sequences of `length` fields each, stored back to back; asynchronous, one
+    launch.  -> (out_vecs, out_mask, part_vecs or None, part_masks or None, lost_at or None): float32 [n_seq][H][W][2] and
+    uint8 [n_seq][H][W], the partial results float32 [n_seq][length][H][W][2] and uint8 [n_seq][length][H][W], and int32
+    [n_seq][H][W], all still in HBM."""
+    px = n_seq * shape[0] * shape[1]
+    out, mout = DeviceBuffer(px * 8), DeviceBuffer(px)
+    pv = DeviceBuffer(px * length * 8) if want_partials else None
+    pm = DeviceBuffer(px * length) if want_partials else None
+    lost = DeviceBuffer(px * 4) if want_lost_at else None
+    nat.check(_lib().ofl_compose_sequence_dev(vecs.ptr, mask.ptr, sign, shape[0], shape[1], length, n_seq, out.ptr, mout.ptr,
+                                              _ptr(pv), _ptr(pm), _ptr(lost), quant, stream))
+    return out, mout, pv, pm, lost
+
+
+def sequence_host(vecs, masks, sign, want_partials=False, want_lost_at=False, quant=nat.QUANT_OPENCV):
+    """K25 for host arrays through ofl_compose_sequence (upload, one launch, download): vecs (L, H, W, 2), masks (L, H, W),
+    ONE sequence -> (vecs float32 (H, W, 2), mask bool (H, W), part_vecs float32 (L, H, W, 2) or None, part_masks bool
+    (L, H, W) or None, lost_at int32 (H, W) or None)."""
+    vecs, m = np.ascontiguousarray(vecs, np.float32), mask_bytes(masks)
+    length, h, w = vecs.shape[:3]
+    out, mout = np.empty((h, w, 2), np.float32), np.empty((h, w), np.uint8)
+    pv = np.empty((length, h, w, 2), np.float32) if want_partials else None
+    pm = np.empty((length, h, w), np.uint8) if want_partials else None
+    lost = np.empty((h, w), np.int32) if want_lost_at else None
+    nat.check(_lib().ofl_compose_sequence(vecs.ctypes.data, m.ctypes.data, sign, h, w, length, 1, out.ctypes.data,
+                                          mout.ctypes.data, _host_ptr(pv), _host_ptr(pm), _host_ptr(lost), quant))
+    return out, mout.view(np.bool_), pv, None if pm is None else pm.view(np.bool_), lost
