@@ -1122,7 +1122,7 @@ int ofl_splat(const void *src, int elem, int layout, int N, int C, int H, int W,
  * entry takes host pointers (counts_host: host uint32[N][2] or NULL), uploads, launches, downloads and synchronises.
  * Bytes per pixel: reads 2 C elements (near streamed, far gathered) + 8 (flow) + 1 to 3 (masks); writes 4 + 1 + 1, where
  * K12 plus an elementwise pass writes and re-reads C elements more.
- * Not built: the window metrics SSIM and gradient constancy (a second pass; the census distance is K22, below), a reduction
+ * Not built: the window metric gradient constancy (the census distance is K22, below, SSIM is K26), a reduction
  * of the map to a mean or percentiles, a backward pass, mixed element types or layouts, integer tensors on the device,
  * padding offsets.
  */
@@ -1169,7 +1169,7 @@ int ofl_photometric(const void *near, const void *far, int elem, int layout, int
  * Alignment, 64-bit offsets, aliasing and the two entries (asynchronous _dev, host-staged) as in K21.  A bad argument -- those
  * of K21, C > 4, another window or mode, min_count outside [1, K * K - 1], delta negative, noise or knee not positive, any
  * of them or tau (when within is given) not finite -- returns OFL_E_INVALID with a message before any launch.
- * Not built: C > 4 and a per-channel census, luma weights (pass a reduced plane), SSIM and gradient constancy, windows above
+ * Not built: C > 4 and a per-channel census, luma weights (pass a reduced plane), gradient constancy (SSIM is K26), windows above
  * 7 or not square, a reduction of the map, a backward pass, mixed element types or layouts, integer tensors on the device.
  */
 enum { OFL_CENSUS_HARD = 0, OFL_CENSUS_SOFT = 1 };
@@ -1368,6 +1368,62 @@ int ofl_compose_sequence_dev(const float *flows, const uint8_t *masks, int sign,
                              int quant, void *stream);
 int ofl_compose_sequence(const float *flows, const uint8_t *masks, int sign, int H, int W, int L, int S,
                          float *out, uint8_t *mout, float *part_vecs, uint8_t *part_masks, int32_t *lost_at, int quant);
+
+/* ------------------------------------------------------------------ K26: structural similarity of a warp over a window
+ * K21 compares raw values and K22 their order.  The third standard term compares the local mean, variance and covariance of
+ * the intensities in a weighted K x K window around the pixel, in `near` and in the warped `far`: Wang et al.'s SSIM -- with
+ * an 11 x 11 Gaussian window the number quoted for the quality of a warp where there is no ground truth -- and, with a
+ * uniform window, the avg_pool2d form in the photometric loss of UnFlow / DDFlow / ARFlow / UFlow / SMURF.  The output is the
+ * DISSIMILARITY (1 - SSIM) / 2 in [0, 1]; SSIM itself is 1 - 2 err.  One fused launch: the warped image is never written.
+ *     near, far, elem, layout, N, C, H, W, flow, fmask, flow_shared, sign, near_mask, far_mask, quant: K22's (C in [1, 4])
+ *     window    K in {3, 5, 7, 11}, r = K / 2
+ *     taps      a HOST pointer to K float32 values, in both entries: the 1-D window g[0 ... K-1], read during the call and
+ *               passed to the kernel by value; every tap finite and > 0.  The 2-D window is g[dx + r] * g[dy + r]
+ *     c1, c2    float32, finite and > 0: Wang's (k1 L)^2 and (k2 L)^2
+ *     min_count in [1, K * K]: the members a window needs -- the centre IS a member of its own window, unlike K22
+ *     tau       as in K21
+ * Per item n and pixel q, every operation float32 and rounded once (no FMA; the divisions correctly rounded):
+ *     tap(q), w_c(q), am(q), cov1(q), A(q), B(q)        K22's, unchanged
+ *     member(q) = q inside the frame & cov1(q)
+ *     for every row dy = -r ... r and dx = -r ... r of the window of p (the centre included), q = p + (dx, dy):
+ *         ga = g[dx+r] * A(q);   gb = g[dx+r] * B(q)
+ *         the six terms  g[dx+r],  ga,  gb,  ga * A(q),  gb * B(q),  ga * B(q)
+ *         each term is REPLACED by +0.0f where !member(q)            (a select, not a product: a NaN there does not leak)
+ *         R^k_dy = the row sum of term k, ascending dx, from +0.0f                          k = 0 ... 5
+ *     S^k = g[-r+r] * R^k_(-r) + ... + g[r+r] * R^k_r, one product and one addition a row, ascending dy, from +0.0f
+ *     (Wt, Sa, Sb, Saa, Sbb, Sab) = S^0 ... S^5;   n = the number of members (an integer)
+ *     mu_a = Sa / Wt;  mu_b = Sb / Wt
+ *     va  = Saa / Wt - mu_a * mu_a;   vb = Sbb / Wt - mu_b * mu_b;   vab = Sab / Wt - mu_a * mu_b
+ *     num = (2 * (mu_a * mu_b) + c1) * (2 * vab + c2)
+ *     den = ((mu_a * mu_a + mu_b * mu_b) + c1) * ((va + vb) + c2)
+ *     s = num / den;   e = (1 - s) * 0.5;   e = e < 0 ? 0 : (e > 1 ? 1 : e)          (a NaN stays a NaN)
+ *     covered(p) = cov1(p) & (n >= min_count);  err = covered ? e : 0.0f;  within = covered & (e <= tau)
+ * These are population moments -- Wang et al. with a Gaussian window, the avg_pool2d form with a uniform one --, and the
+ * intensity is the channel mean, as in K22 ... K24.  The definition is separable on purpose: the six row sums of a tile row
+ * do not depend on the centre, so the centres a thread owns share them, and a window of ones gives Wt == n exactly.  The raw
+ * second moments are on purpose too: centring on the centre pixel would cut the cancellation in Saa / Wt - mu_a^2 but end
+ * the sharing; in float32 they cost 1e-5 to 1e-4 of e against float64 at intensities 0 ... 255 (tests/ssim_ref.py derives the
+ * bound and restates all of this in NumPy).  There is NO zero-flow short cut.
+ *     err, covered, within, counts: K21's ([N][H][W]; one of err / within required; counts uint32[N][2] ADDED to, at most one
+ *     integer atomic add per workgroup and counter; no other atomics, no workspace).
+ * Alignment, 64-bit offsets, aliasing and the two entries (asynchronous _dev, host-staged) as in K21.  A bad argument -- those
+ * of K21, C > 4, another window, a NULL taps, a tap, c1 or c2 not finite or not positive, min_count outside [1, K * K], tau
+ * (when within is given) negative or not finite -- returns OFL_E_INVALID with a message before any launch.
+ * Not built: C > 4 and a per-channel SSIM, luma weights (pass a reduced plane), sample (N - 1) moments, other or non-square
+ * windows, MS-SSIM, the three components as outputs, gradient constancy, a reduction of the map, PSNR, a backward pass,
+ * mixed element types or layouts, integer tensors on the device.
+ */
+enum { OFL_SSIM_MAX_C = 4 };
+int ofl_ssim_dev(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                 const float *flow, const uint8_t *fmask, int flow_shared, int sign,
+                 const uint8_t *near_mask, const uint8_t *far_mask,
+                 int window, const float *taps, float c1, float c2, int min_count, float tau,
+                 float *err, uint8_t *covered, uint8_t *within, uint32_t *counts, int quant, void *stream);
+int ofl_ssim(const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+             const float *flow, const uint8_t *fmask, int flow_shared, int sign,
+             const uint8_t *near_mask, const uint8_t *far_mask,
+             int window, const float *taps, float c1, float c2, int min_count, float tau,
+             float *err, uint8_t *covered, uint8_t *within, uint32_t *counts_host, int quant);
 
 /* ------------------------------------------------------------------ C1: the exchange steps (RCCL)
  * Two exchange steps exist in the sharded workload: one broadcast of a shared source image / flow from rank `root`

@@ -33,6 +33,7 @@ CENSUS_HARD, CENSUS_SOFT = 0, 1
 CENSUS_MAX_C = 4
 REFINE_MAX_C, REFINE_MAX_ITER = 4, 32
 ISEARCH_MAX_C, ISEARCH_MAX_ITER = 4, 32
+SSIM_MAX_C = 4
 
 
 class MeshCert(ctypes.Structure):
@@ -190,6 +191,10 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _vp, _ci]),
     "ofl_compose_sequence_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp]),
     "ofl_compose_sequence": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci]),
+    "ofl_ssim_dev": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _vp, _cf, _cf, _ci, _cf,
+                           _vp, _vp, _vp, _vp, _ci, _vp]),
+    "ofl_ssim": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _vp, _cf, _cf, _ci, _cf,
+                       _vp, _vp, _vp, _vp, _ci]),
     "ofl_comm_unique_id": (_ci, [_vp]),
     "ofl_comm_init": (_ci, [_vp, _ci, _ci]),
     "ofl_comm_broadcast": (_ci, [_vp, _cs, _ci, _vp]),

@@ -436,6 +436,58 @@ def census_channels(c):
     return pair_channels(c, nat.CENSUS_MAX_C, "Error computing census distance: ")
 
 
+# -- structural similarity of a warp over a window (K26)
+SSIM_WINDOWS = (3, 5, 7, 11)
+SSIM_WEIGHTS = ('gaussian', 'uniform')
+SSIM_SIGMA = 1.5                  # Wang et al.'s Gaussian window
+
+
+def ssim_args(window=11, weights='gaussian', sigma=None, data_range=255.0, k1=0.01, k2=0.03, min_count=None, threshold=None):
+    """Validation of the settings of a structural similarity (K26) on the host before any device work -> (window, taps, c1,
+    c2, min_count, threshold): taps the float32 array of the 1-D window, c1 = (k1 data_range)^2 and c2 = (k2 data_range)^2
+    computed in float64 and rounded to float32, threshold as float32 or None.  window: 3, 5, 7 or 11; weights: 'uniform'
+    (every tap 1.0; `sigma` must stay None) or 'gaussian' (exp(-x^2 / (2 sigma^2)) in float64, divided by its sum, rounded
+    to float32; `sigma` > 0, None: 1.5); data_range, k1, k2 > 0; min_count: the valid pixels a window needs, the centre
+    among them, 1 ... window^2, None: all of them; threshold: None for no `within` output, else the bound err <= threshold.
+    A bool or a value of the wrong type is a TypeError, a value out of range or not finite (as given, or once rounded to
+    float32) a ValueError."""
+    prefix = "Error computing structural similarity: "
+    _integer_setting(window, "window", prefix)
+    if window not in SSIM_WINDOWS:
+        raise ValueError("{}window must be 3, 5, 7 or 11, got {}".format(prefix, window))
+    if not isinstance(weights, str):
+        raise TypeError("{}weights must be a string, got {}".format(prefix, type(weights).__name__))
+    if weights not in SSIM_WEIGHTS:
+        raise ValueError("{}weights must be 'gaussian' or 'uniform', got {!r}".format(prefix, weights))
+    if sigma is not None and weights != 'gaussian':
+        raise ValueError("{}sigma belongs to weights 'gaussian' and must be None with weights '{}'".format(prefix, weights))
+    window = int(window)
+    if weights == 'uniform':
+        taps = np.ones(window, np.float32)
+    else:
+        _float32_setting(SSIM_SIGMA if sigma is None else sigma, "sigma", prefix, positive=True)
+        x = np.arange(window, dtype=np.float64) - window // 2
+        g = np.exp(-(x * x) / (2.0 * float(SSIM_SIGMA if sigma is None else sigma) ** 2))
+        taps = (g / g.sum()).astype(np.float32)
+        if not (np.isfinite(taps).all() and (taps > 0).all()):
+            raise ValueError("{}sigma must leave every tap of window {} positive in float32, got {}".format(prefix, window, sigma))
+    for name, value in (("data_range", data_range), ("k1", k1), ("k2", k2)):
+        _float32_setting(value, name, prefix, positive=True, none_ok=False)
+    with np.errstate(over='ignore', under='ignore'):
+        c1, c2 = np.float32((float(k1) * float(data_range)) ** 2), np.float32((float(k2) * float(data_range)) ** 2)
+    for name, value in (("k1 * data_range", c1), ("k2 * data_range", c2)):
+        if not (np.isfinite(value) and value > 0):
+            raise ValueError("{}({})^2 must be finite and positive in float32, got {}".format(prefix, name, value))
+    threshold = None if threshold is None else _float32_setting(threshold, "threshold", prefix)
+    full = window * window
+    if min_count is None:
+        min_count = full
+    _integer_setting(min_count, "min_count", prefix, none_ok=True)
+    if not 1 <= min_count <= full:
+        raise ValueError("{}min_count must be in [1, {}] for window {}, got {}".format(prefix, full, window, min_count))
+    return window, taps, c1, c2, int(min_count), threshold
+
+
 # -- variational refinement of a field on two images (K23)
 REFINE_DEFAULTS = dict(alpha=20.0, delta=5.0, zeta=0.1, eps=0.1, fixed_point=5, sor=5, omega=1.6)
 

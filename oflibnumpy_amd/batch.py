@@ -166,6 +166,19 @@ class DeviceFlowBatch:
                                           self.ref, near, far, near_mask, far_mask, return_counts, quant, batch=self.n)
         return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
 
+    def ssim(self, near, far, window=11, weights='gaussian', sigma=None, data_range=255.0, k1=0.01, k2=0.03, min_count=None,
+             threshold=None, near_mask=None, far_mask=None, return_counts=False, quant=nat.QUANT_OPENCV):
+        """self[i].ssim(item i of `near`, item i of `far`, ...) for every i in ONE launch of K26 (DeviceFlow.ssim):
+        near, far DeviceTensors (n, C, H, W) of one layout and dtype with 1 to 4 channels, near_mask, far_mask uint8
+        DeviceBuffers [n][H][W] (per item) or None.  -> (error float32, covered uint8) as DeviceBuffers [n][H][W], error
+        the dissimilarity (1 - SSIM) / 2; `threshold` appends within (uint8), return_counts an (n, 2) uint32 array of
+        (covered, within) pixels per item -- the only option that synchronises.  A packed batch is read through its byte
+        masks."""
+        res, counts, _ = dev.error_map_op(dev.ssim_launch, dev.ssim_args(window, weights, sigma, data_range, k1, k2, min_count, threshold),
+                                          nat.SSIM_MAX_C, "Error computing structural similarity: ", self.vecs, self.mask, self.shape,
+                                          self.ref, near, far, near_mask, far_mask, return_counts, quant, batch=self.n)
+        return res + (counts.to_host((self.n, 2), np.uint32),) if return_counts else res
+
     def refine(self, near, far, alpha=None, delta=None, zeta=None, eps=None, fixed_point=None, sor=None, omega=None,
                near_mask=None, far_mask=None, valid=None, return_data=False, quant=nat.QUANT_OPENCV):
         """self[i].refine(item i of `near`, item i of `far`, ...) for every i in the SAME launches of K23

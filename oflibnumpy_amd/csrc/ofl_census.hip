@@ -33,7 +33,7 @@
 // counts: K21's scheme (ballot + popcount, at most one integer atomicAdd per workgroup and counter); no other atomics, no
 // workspace, 64-bit element offsets.  36 instantiations: 3 element types x 2 quant x 3 windows x 2 modes.
 //
-// OUT OF SCOPE: C > 4 and a per-channel census, luma weights, SSIM and gradient constancy, windows above 7 or not square, a
+// OUT OF SCOPE: C > 4 and a per-channel census, luma weights, gradient constancy (SSIM is K26), windows above 7 or not square, a
 // reduction of the map, a backward pass, mixed element types or layouts, integer tensors.
 #include "ofl_common.h"
 #include "ofl_elem.h"

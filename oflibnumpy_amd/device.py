@@ -33,7 +33,7 @@ from .args import (DEFAULT_THRESHOLD, _DT_CODE, _TRACK_DT, _PAD_MODES, remap_rul
                    resize_scales, resized_shape, tensor_dtype, tensor_args, tensor_mem_shape, tensor_logical_shape,
                    consistency_args, error_args, fill_args, median_args, upsample_args, upsample_weights_array, corr_args,
                    corr_host_array, optional_bool, mask_array_arg, match_args, match_host_array, splat_args, splat_host_array,
-                   splat_importance_array, photometric_args, photometric_host_array, census_args, refine_args,
+                   splat_importance_array, photometric_args, photometric_host_array, census_args, ssim_args, refine_args,
                    inverse_search_args, inverse_search_channels, estimate_levels, pair_channels, pair_host_arrays,
                    sequence_args, SEQUENCE_PREFIX)
 from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stats_word_launch, compose3_launch,
@@ -43,7 +43,7 @@ from .kernels import (gather_bilinear_batch, gather_valid_only, flow_stats, stat
                       tensor_permute_launch, consistency_launch, consistency_host, error_launch, error_host, ERROR_RECORD,
                       FlowErrorStats, fill_launch, fill_host, median_launch, median_host, upsample_launch,
                       upsample_host, avgpool2_launch, corr_lookup_launch, corr_lookup_host, match_launch, match_host, splat_launch, splat_host,
-                      photometric_launch, photometric_host, census_launch, census_host,
+                      photometric_launch, photometric_host, census_launch, census_host, ssim_launch, ssim_host,
                       refine_launch, refine_host, tensor_halve_launch, inverse_search_launch, inverse_search_host,
                       sequence_launch, sequence_host)
 from .scatter import (_workspace, walk_check, scatter_linear, scatter_linear_f64, scatter_rows, SLAB_LIST_HEAD, SLAB_RECORD,
@@ -431,8 +431,8 @@ def photometric_tensors(near, far, field_shape, batch=None, prefix="Error comput
 # family's args.*_args returned.  They return the buffers of the launch wrapper; the two classes shape their own results.
 def error_map_op(launch, settings, max_c, prefix, vecs, mask, shape, ref, near, far, near_mask, far_mask, return_counts, quant,
                  batch=None):
-    """photometric (launch photometric_launch, max_c None) and census (census_launch, 4) -> ((err, covered[, within]), the
-    counts buffer or None, the number of items)"""
+    """photometric (launch photometric_launch, max_c None), census (census_launch, 4) and ssim (ssim_launch, 4) -> ((err,
+    covered[, within]), the counts buffer or None, the number of items)"""
     near, far = photometric_tensors(near, far, shape, batch, prefix, max_c)
     n_bytes = (batch or 1) * shape[0] * shape[1]
     near_mask = mask_buffer_arg(near_mask, n_bytes, prefix, "near_mask")
@@ -784,7 +784,7 @@ class DeviceFlow:
         -> (error, covered): a float32 and a uint8 DeviceBuffer [N][H][W]; `threshold` appends within = covered &
         (error <= threshold) as uint8, return_counts appends [(n_covered, n_within)] * N as Python ints -- the only option
         that synchronises.  `error` is what splat(mode='softmax', importance=error, alpha=-20.0) takes, without a copy.
-        Not built: the window metrics SSIM and gradient constancy (the census distance is `census`), a mean or percentiles
+        Not built: the window metric gradient constancy (the census distance is `census`, SSIM is `ssim`), a mean or percentiles
         of the map, a backward pass, mixed dtypes or layouts, integer tensors, padding offsets.  The inputs are not modified."""
         res, counts, n = error_map_op(photometric_launch, photometric_args(metric, eps, threshold), None,
                                       "Error computing photometric error: ", self.vecs, self.mask, self.shape, self.ref,
@@ -806,10 +806,35 @@ class DeviceFlow:
         without a zero-flow short cut; works for 's' and 't' fields alike.
         -> (error, covered): a float32 and a uint8 DeviceBuffer [N][H][W]; `threshold` appends within = covered &
         (error <= threshold) as uint8, return_counts appends [(n_covered, n_within)] * N as Python ints -- the only option
-        that synchronises.  Not built: more than 4 channels, a per-channel census, luma weights, SSIM, gradient constancy,
+        that synchronises.  Not built: more than 4 channels, a per-channel census, luma weights, gradient constancy,
         other windows, a mean of the map, a backward pass.  The inputs are not modified."""
         res, counts, n = error_map_op(census_launch, census_args(window, mode, delta, noise, knee, min_count, threshold),
                                       nat.CENSUS_MAX_C, "Error computing census distance: ", self.vecs, self.mask, self.shape,
+                                      self.ref, near, far, near_mask, far_mask, return_counts, quant)
+        return res + ([(int(a), int(b)) for a, b in counts.to_host((n, 2), np.uint32)],) if return_counts else res
+
+    def ssim(self, near, far, window=11, weights='gaussian', sigma=None, data_range=255.0, k1=0.01, k2=0.03, min_count=None,
+             threshold=None, near_mask=None, far_mask=None, return_counts=False, quant=nat.QUANT_OPENCV):
+        """The structural dissimilarity of this field in ONE launch of K26 (include/ofl.h): the local means, variances and
+        the covariance of the intensities -- the channel means A of `near` and B of `far` sampled where this field points
+        -- in a weighted window x window neighbourhood of the pixel (3, 5, 7 or 11), compared as Wang et al.'s SSIM:
+            SSIM  = (2 mu_a mu_b + c1) (2 cov_ab + c2) / ((mu_a^2 + mu_b^2 + c1) (var_a + var_b + c2))
+            error = clamp((1 - SSIM) / 2, 0, 1)          so SSIM = 1 - 2 error
+        with c1 = (k1 data_range)^2, c2 = (k2 data_range)^2 and population moments.  weights: 'gaussian' (`sigma` None: 1.5;
+        the defaults are Wang's 11 x 11 window for intensities 0 ... 255) or 'uniform' (the avg_pool2d form of the SSIM term
+        in unsupervised flow; `sigma` stays None).  The window holds the pixels that are inside the frame and covered as
+        photometric defines it, the centre among them, and is renormalised to them; a pixel is covered when photometric
+        covers it and its window has at least min_count such pixels (None: all window^2, the usual border mask).  Every
+        operation is float32; the raw second moments cost 1e-5 to 1e-4 of the error against float64 at intensities 0 ... 255.
+        near, far, near_mask, far_mask, quant: as in photometric, with 1 to 4 channels.  Not a function of the reference and
+        without a zero-flow short cut; works for 's' and 't' fields alike.
+        -> (error, covered): a float32 and a uint8 DeviceBuffer [N][H][W]; `threshold` appends within = covered &
+        (error <= threshold) as uint8, return_counts appends [(n_covered, n_within)] * N as Python ints -- the only option
+        that synchronises.  `error` feeds splat(importance=) as photometric's does.  Not built: more than 4 channels, a
+        per-channel SSIM, luma weights, sample (N - 1) moments, other windows, MS-SSIM, the three components, gradient
+        constancy, a mean of the map, PSNR, a backward pass.  The inputs are not modified."""
+        res, counts, n = error_map_op(ssim_launch, ssim_args(window, weights, sigma, data_range, k1, k2, min_count, threshold),
+                                      nat.SSIM_MAX_C, "Error computing structural similarity: ", self.vecs, self.mask, self.shape,
                                       self.ref, near, far, near_mask, far_mask, return_counts, quant)
         return res + ([(int(a), int(b)) for a, b in counts.to_host((n, 2), np.uint32)],) if return_counts else res
 

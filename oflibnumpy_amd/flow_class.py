@@ -474,6 +474,29 @@ class Flow(object):
                               near_mask=near_mask, far_mask=far_mask, quant=quant)
         return res if batched else tuple(r[0] for r in res)
 
+    def ssim(self, near: np.ndarray, far: np.ndarray, window: int = 11, weights: str = 'gaussian', sigma: float = None,
+             data_range: float = 255.0, k1: float = 0.01, k2: float = 0.03, min_count: int = None, threshold: float = None,
+             near_mask: np.ndarray = None, far_mask: np.ndarray = None, layout: str = 'hwc',
+             quant: int = 0) -> Tuple[np.ndarray, ...]:
+        """The structural dissimilarity (1 - SSIM) / 2 of this flow, in [0, 1]: Wang et al.'s SSIM of the intensities
+        (channel means) in a weighted window x window neighbourhood (3, 5, 7 or 11) of each pixel of `near`, the image of
+        the flow's own frame, against the same in `far`, that of the other frame, sampled where the flow points -- weights
+        'gaussian' (`sigma` None: 1.5; the defaults are Wang's 11 x 11 window for intensities 0 ... 255) or 'uniform' (the
+        avg_pool2d form of unsupervised flow); c1 = (k1 data_range)^2, c2 = (k2 data_range)^2.  near, far: arrays as in
+        photometric with 1 to 4 channels, uint8 images included (converted to float32, exact).  min_count: the valid pixels
+        a window needs, the centre among them, None: all window^2.  -> (error float32, covered bool), each (H, W) -- or
+        (N, H, W) --, plus within = covered & (error <= threshold) as bool with `threshold`; SSIM itself is 1 - 2 error and
+        its mean error[covered].mean().  Not a function of the reference; the definition is DeviceFlow.ssim's.  One upload,
+        one launch, one download."""
+        prefix = "Error computing structural similarity: "
+        settings = dev.ssim_args(window, weights, sigma, data_range, k1, k2, min_count, threshold)
+        near, far, n, c, batched = dev.pair_host_arrays(near, far, layout, self.shape, prefix, nat.SSIM_MAX_C)
+        near_mask = None if near_mask is None else dev.mask_array_arg(near_mask, self.shape, prefix, "near_mask")
+        far_mask = None if far_mask is None else dev.mask_array_arg(far_mask, self.shape, prefix, "far_mask")
+        res = dev.ssim_host(near, far, layout, n, c, self._vecs, self._mask, 1 if self._ref == 's' else -1, *settings,
+                            near_mask=near_mask, far_mask=far_mask, quant=quant)
+        return res if batched else tuple(r[0] for r in res)
+
     def refine(self, near: np.ndarray, far: np.ndarray, alpha: float = None, delta: float = None, zeta: float = None,
                eps: float = None, fixed_point: int = None, sor: int = None, omega: float = None,
                near_mask: np.ndarray = None, far_mask: np.ndarray = None, valid: np.ndarray = None, return_data: bool = False,

@@ -12,7 +12,7 @@ nd = np.ndarray
 __all__ = ['combine_flows', 'switch_flow_ref', 'invert_flow', 'valid_target', 'valid_source', 'get_flow_padding',
            'get_flow_matrix', 'visualise_flow', 'flow_consistency', 'flow_error', 'fill_flow', 'median_flow',
            'upsample_flow_convex', 'correlation_lookup', 'global_match', 'splat_flow', 'photometric_error', 'census_error',
-           'refine_flow', 'inverse_search_flow', 'estimate_flow', 'halve_tensor', 'combine_flow_sequence']
+           'ssim_error', 'refine_flow', 'inverse_search_flow', 'estimate_flow', 'halve_tensor', 'combine_flow_sequence']
 
 
 def combine_flows(input_1: Union[Flow, nd], input_2: Union[Flow, nd], mode: int, ref: str = None,
@@ -182,6 +182,19 @@ def census_error(flow: nd, near: nd, far: nd, ref: str = None, mask: nd = None, 
     return Flow(flow, ref, mask).census(near, far, window=window, mode=mode, delta=delta, noise=noise, knee=knee,
                                         min_count=min_count, threshold=threshold, near_mask=near_mask, far_mask=far_mask,
                                         layout=layout)
+
+
+def ssim_error(flow: nd, near: nd, far: nd, ref: str = None, mask: nd = None, window: int = 11, weights: str = 'gaussian',
+               sigma: float = None, data_range: float = 255.0, k1: float = 0.01, k2: float = 0.03, min_count: int = None,
+               threshold: float = None, near_mask: nd = None, far_mask: nd = None, layout: str = 'hwc') -> tuple:
+    """(error, covered) -- a float32 map and a bool array, plus the bool array `within` with `threshold` -- of the structural
+    dissimilarity (1 - SSIM) / 2 of the flow array `flow` (H, W, 2) with reference `ref` and mask `mask` (None: all valid):
+    Wang et al.'s SSIM in a weighted window around each pixel of `near`, the image of the flow's own frame, against `far`,
+    sampled where the flow points -- Flow.ssim: weights 'gaussian' or 'uniform', window 3, 5, 7 or 11; arrays (H, W),
+    (H, W, C) or, with layout='chw', (C, H, W), 1 to 4 channels."""
+    return Flow(flow, ref, mask).ssim(near, far, window=window, weights=weights, sigma=sigma, data_range=data_range, k1=k1,
+                                      k2=k2, min_count=min_count, threshold=threshold, near_mask=near_mask, far_mask=far_mask,
+                                      layout=layout)
 
 
 def refine_flow(flow: nd, near: nd, far: nd, ref: str = None, mask: nd = None, alpha: float = None, delta: float = None,

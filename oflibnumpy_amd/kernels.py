@@ -1,5 +1,5 @@
 """Thin launch wrappers of the library's kernel families on buffers that are already in HBM: K1 gather, K2 compose, K4
-statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching, K20 splatting, K21 photometric error, K22 census distance, K23 variational refinement, K24 dense inverse search and K25 sequence accumulation.  Each wrapper allocates what the entry needs,
+statistics, K7 visualise, K8 matrix fit, K9 build / resize, K10 tracking, K12 tensor warps, K13 consistency, K14 flow error, K15 fill, K16 median filter, K17 convex upsampling, K18 correlation lookup, K19 global matching, K20 splatting, K21 photometric error, K22 census distance, K23 variational refinement, K24 dense inverse search, K25 sequence accumulation and K26 structural similarity.  Each wrapper allocates what the entry needs,
 passes pointers and returns buffers; the scatter kernel K3 and its multi-rank protocol live in scatter.py, the exchange
 with other frameworks (K11) in interop.py.  The wrappers that hand back a DeviceImage (gather_bilinear, gather_rows,
 visualise_launch) stay next to that class in device.py.
@@ -600,7 +600,7 @@ def _pair_head(near, far, dtype, layout, n, c, shape):
 
 def _pair_error_launch(entry, near, far, dtype, layout, n, c, shape, flow, fmask, flow_shared, sign, settings, threshold,
                        near_mask, far_mask, want_err, want_covered, want_counts, quant, stream):
-    """K21's and K22's device entries differ in their `settings` alone: the outputs allocated and the call made once"""
+    """K21's, K22's and K26's device entries differ in their `settings` alone: the outputs allocated and the call made once"""
     px = n * shape[0] * shape[1]
     err = DeviceBuffer(px * 4) if want_err else None
     covered = DeviceBuffer(px) if want_covered else None
@@ -667,6 +667,30 @@ def census_host(near, far, layout, n, c, vecs, mask, sign, window, mode, p0, p1,
     """K22 for host arrays through ofl_census (upload, one launch, download): arrays, field and masks as in
     photometric_host -> (err float32, covered bool[, within bool]), each (n, H, W)."""
     return _pair_error_host(_lib().ofl_census, near, far, layout, n, c, vecs, mask, sign, (window, mode, p0, p1, min_count),
+                            threshold, near_mask, far_mask, quant)
+
+
+# ------------------------------------------------------------------------------ K26: structural similarity of a warp over a window
+def ssim_launch(near, far, dtype, layout, n, c, shape, flow, fmask, flow_shared, sign, window, taps, c1, c2, min_count,
+                threshold=None, near_mask=None, far_mask=None, want_err=True, want_covered=True, want_counts=False,
+                quant=nat.QUANT_OPENCV, stream=None):
+    """K26 (ofl_ssim_dev) on `n` items of `c` channels (1 to 4) in `layout` ('chw' / 'hwc') of `dtype`; buffers and the
+    shared or per-item field and masks as in photometric_launch; asynchronous, one launch.  window, taps, c1, c2, min_count,
+    threshold: from args.ssim_args (taps: the float32 array of the 1-D window, read by the entry during the call; threshold
+    None: no `within`).  -> (err or None, covered or None, within or None, counts or None): float32, uint8 and uint8
+    [n][H][W] and the zeroed-then-added uint32 [n][2] = {covered, within} words, all still in HBM."""
+    taps = np.ascontiguousarray(taps, np.float32)               # alive until the entry has returned
+    return _pair_error_launch(_lib().ofl_ssim_dev, near, far, dtype, layout, n, c, shape, flow, fmask, flow_shared, sign,
+                              (window, taps.ctypes.data, c1, c2, min_count), threshold, near_mask, far_mask, want_err, want_covered,
+                              want_counts, quant, stream)
+
+
+def ssim_host(near, far, layout, n, c, vecs, mask, sign, window, taps, c1, c2, min_count, threshold=None, near_mask=None,
+              far_mask=None, quant=nat.QUANT_OPENCV):
+    """K26 for host arrays through ofl_ssim (upload, one launch, download): arrays, field and masks as in
+    photometric_host -> (err float32, covered bool[, within bool]), each (n, H, W)."""
+    taps = np.ascontiguousarray(taps, np.float32)
+    return _pair_error_host(_lib().ofl_ssim, near, far, layout, n, c, vecs, mask, sign, (window, taps.ctypes.data, c1, c2, min_count),
                             threshold, near_mask, far_mask, quant)
 
 
