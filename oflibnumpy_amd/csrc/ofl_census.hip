@@ -30,14 +30,14 @@
 //            its four centres.  Hard mode counts its terms in an integer and converts once: every partial sum of the stated
 //            order is an integer of at most 48, exact in float32, so the bits are the same, and s(a) != s(b) is four
 //            compares and mask logic.
-// counts: K21's scheme (ballot + popcount, at most one integer atomicAdd per workgroup and counter); no other atomics, no
-// workspace, 64-bit element offsets.  36 instantiations: 3 element types x 2 quant x 3 windows x 2 modes.
+// Epilogue: window_finish (ofl_photo_dev.h, shared with K26) -- covered, the stores of error_store and the counts in K21's
+// scheme (ballot + popcount, at most one integer atomicAdd per workgroup and counter); no other atomics, no workspace, 64-bit
+// element offsets.  36 instantiations: 3 element types x 2 quant x 3 windows x 2 modes.
 //
 // OUT OF SCOPE: C > 4 and a per-channel census, luma weights, gradient constancy (SSIM is K26), windows above 7 or not square, a
 // reduction of the map, a backward pass, mixed element types or layouts, integer tensors.
 #include "ofl_common.h"
 #include "ofl_elem.h"
-#include "ofl_host_stage.h"
 #include "ofl_photo_dev.h"
 
 #pragma clang fp contract(off)
@@ -83,9 +83,7 @@ void census_kernel(const CArgs a)
     __shared__ float   s_a[NE], s_b[NE];
     __shared__ uint8_t s_m[NE];
 
-    const int H = a.H, W = a.W;
     const int n = blockIdx.z, x0 = blockIdx.x * kTX, y0 = blockIdx.y * kTY;
-    const size_t hw = (size_t)H * W;
 
     stage_warped_tile<E, QUANT, R, kTX, kTY>(a, n, x0, y0, s_a, s_b, s_m);           // ofl_photo_dev.h
     __syncthreads();
@@ -133,59 +131,36 @@ void census_kernel(const CArgs a)
             }
         }
     }
-    if constexpr (MODE == OFL_CENSUS_HARD) {
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) S[j] = (float)diff[j];
-    }
 
-    uint32_t n_cov = 0, n_wi = 0;
-    const int x = x0 + lane;
+    float e[kRows];                                                                 // hard: the count, converted once
 #pragma unroll
-    for (int j = 0; j < kRows; ++j) {
-        const int y = y0 + top + j;
-        const bool act = x < W && y < H;
-        const bool cov = act && cm[j] && cnt[j] >= a.min_count;
-        const float e = __fdiv_rn(S[j], (float)cnt[j]);
-        const bool wi = a.within != nullptr && cov && e <= a.tau;
-        if (act) {
-            const size_t o = (size_t)n * hw + (size_t)y * W + x;
-            if (a.err) a.err[o] = cov ? e : 0.0f;
-            if (a.covered) a.covered[o] = cov ? 1 : 0;
-            if (a.within) a.within[o] = wi ? 1 : 0;
-        }
-        n_cov += (uint32_t)__popcll(__ballot(cov));
-        n_wi += (uint32_t)__popcll(__ballot(wi));
-    }
-    if (a.counts) photo_count(a.counts, n, n_cov, n_wi);
+    for (int j = 0; j < kRows; ++j) e[j] = __fdiv_rn(MODE == OFL_CENSUS_HARD ? (float)diff[j] : S[j], (float)cnt[j]);
+    window_finish(a, n, x0, y0, cm, cnt, e);                                        // ofl_photo_dev.h
 }
 
 int check_census_args(const char *who, const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
                       const void *flow, const void *fmask, int sign, int window, int mode, float p0, float p1, int min_count,
                       float tau, const void *err, const void *within, int quant)
 {
-    if (!near || !far || !flow || !fmask) return fail(OFL_E_INVALID, "%s: NULL pointer (near, far, flow and fmask are required)", who);
-    OFL_TRY(check_pair_args(who, elem, layout, N, C, OFL_CENSUS_MAX_C, H, W, sign, quant));
+    OFL_TRY(check_error_map_inputs(who, near, far, flow, fmask, elem, layout, N, C, OFL_CENSUS_MAX_C, H, W, sign, quant));
     if (window != 3 && window != 5 && window != 7) return fail(OFL_E_INVALID, "%s: window must be 3, 5 or 7, got %d", who, window);
     if (mode == OFL_CENSUS_HARD) {
-        if (!(p0 >= 0.0f) || !__builtin_isfinite(p0)) return fail(OFL_E_INVALID, "%s: delta must be finite and not negative (got %g)", who, (double)p0);
+        if (!finite_not_negative(p0)) return fail(OFL_E_INVALID, "%s: delta must be finite and not negative (got %g)", who, (double)p0);
     } else if (mode == OFL_CENSUS_SOFT) {
-        if (!(p0 > 0.0f) || !__builtin_isfinite(p0)) return fail(OFL_E_INVALID, "%s: noise must be finite and positive (got %g)", who, (double)p0);
-        if (!(p1 > 0.0f) || !__builtin_isfinite(p1)) return fail(OFL_E_INVALID, "%s: knee must be finite and positive (got %g)", who, (double)p1);
+        if (!finite_positive(p0)) return fail(OFL_E_INVALID, "%s: noise must be finite and positive (got %g)", who, (double)p0);
+        if (!finite_positive(p1)) return fail(OFL_E_INVALID, "%s: knee must be finite and positive (got %g)", who, (double)p1);
     } else {
         return fail(OFL_E_INVALID, "%s: bad mode %d", who, mode);
     }
     if (min_count < 1 || min_count > window * window - 1)
         return fail(OFL_E_INVALID, "%s: min_count must be in [1, %d], got %d", who, window * window - 1, min_count);
-    if (!err && !within) return fail(OFL_E_INVALID, "%s: one of err and within is required", who);
-    if (within && (!(tau >= 0.0f) || !__builtin_isfinite(tau)))
-        return fail(OFL_E_INVALID, "%s: tau must be finite and not negative (got %g)", who, (double)tau);
-    return OFL_OK;
+    return check_error_map_outputs(who, err, within, tau);
 }
 
 template <int E, int QUANT, int K>
 void launch_census(const CArgs &a, int mode, hipStream_t s)
 {
-    const dim3 grid((unsigned)((a.W + kTX - 1) / kTX), (unsigned)((a.H + kTY - 1) / kTY), (unsigned)a.N);
+    const dim3 grid = window_grid(a.N, a.H, a.W);
     if (mode == OFL_CENSUS_HARD) hipLaunchKernelGGL((census_kernel<E, QUANT, K, OFL_CENSUS_HARD>), grid, dim3(256), 0, s, a);
     else                         hipLaunchKernelGGL((census_kernel<E, QUANT, K, OFL_CENSUS_SOFT>), grid, dim3(256), 0, s, a);
 }
@@ -203,14 +178,11 @@ int ofl_census_dev(const void *near, const void *far, int elem, int layout, int 
     OFL_TRY(need_device());
     OFL_TRY(check_census_args("ofl_census", near, far, elem, layout, N, C, H, W, flow, fmask, sign, window, mode, p0, p1, min_count, tau,
                               err, within, quant));
-    OFL_TRY(check_pair_alignment("ofl_census", near, far, elem));
-    if (!host_aligned(flow, 8)) return fail(OFL_E_INVALID, "ofl_census: flow must be 8-byte aligned");
-    if (!host_aligned(err, 4) || !host_aligned(counts, 4)) return fail(OFL_E_INVALID, "ofl_census: err and counts must be 4-byte aligned");
     CArgs a;
-    pair_fill(a, near, far, layout, N, C, H, W, flow, fmask, flow_shared != 0, sign, near_mask, far_mask);
-    a.err = err; a.covered = covered; a.within = within; a.counts = counts;
+    OFL_TRY(error_map_fill("ofl_census", a, near, far, elem, layout, N, C, H, W, flow, fmask, flow_shared != 0, sign, near_mask, far_mask,
+                           err, covered, within, counts, tau));
     a.min_count = min_count;
-    a.p0 = p0; a.p1 = p1; a.tau = tau;
+    a.p0 = p0; a.p1 = p1;
     hipStream_t s = stream_of(stream);
     with_elem(elem, [&](auto E) { with_quant(quant, [&](auto Q) {
         switch (window) {
@@ -232,19 +204,8 @@ int ofl_census(const void *near, const void *far, int elem, int layout, int N, i
     OFL_TRY(need_device());
     OFL_TRY(check_census_args("ofl_census", near, far, elem, layout, N, C, H, W, flow, fmask, sign, window, mode, p0, p1, min_count, tau,
                               err, within, quant));
-    const size_t hw = (size_t)H * W, n = (size_t)N * hw, nf = flow_shared ? hw : n;
-    const size_t bytes = n * C * (elem == OFL_EL_F32 ? 4 : 2);
-    HostStage st("ofl_census");
-    auto dn = st.in(near, bytes), df = st.in(far, bytes);
-    auto dfl = st.in(flow, nf * 2);
-    auto dfm = st.in(fmask, nf), dnm = st.in(near_mask, nf), dam = st.in(far_mask, nf);
-    auto de = st.out(err, n);
-    auto dc = st.out(covered, n), dw = st.out(within, n);
-    auto cnt = st.out(counts_host, (size_t)N * 2, true);          // the launch adds to the counts
-    OFL_TRY(st.upload());
-    OFL_TRY(ofl_census_dev(dn, df, elem, layout, N, C, H, W, dfl, dfm, flow_shared, sign, dnm, dam, window, mode, p0, p1, min_count, tau,
-                           de, dc, dw, cnt, quant, st.stream()));
-    return st.download();
+    return error_map_host("ofl_census", ofl_census_dev, near, far, elem, layout, N, C, H, W, flow, fmask, flow_shared, sign, near_mask, far_mask,
+                          err, covered, within, counts_host, quant, window, mode, p0, p1, min_count, tau);
 }
 
 }  // extern "C"

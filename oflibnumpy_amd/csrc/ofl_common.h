@@ -28,6 +28,10 @@ inline hipStream_t stream_of(void *s) { return s ? (hipStream_t)s : rt().stream;
 // `p` on an `a`-byte boundary (a power of two); a NULL pointer, an absent optional argument, counts as aligned
 inline bool host_aligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 
+// the two tests of a float32 setting: finite and >= 0, finite and > 0 (a NaN fails both)
+inline bool finite_not_negative(float v) { return v >= 0.0f && __builtin_isfinite(v); }
+inline bool finite_positive(float v)     { return v > 0.0f && __builtin_isfinite(v); }
+
 // [p, p + n) and [q, q + m) share a byte; an absent (NULL) range shares none
 inline bool overlap(const void *p, size_t n, const void *q, size_t m)
 {

@@ -211,7 +211,7 @@ int check_isearch_args(const char *who, const void *near, const void *far, int e
     OFL_TRY(check_isearch_dims(who, N, H, W, patch, stride));
     if (iterations < 1 || iterations > OFL_ISEARCH_MAX_ITER)
         return fail(OFL_E_INVALID, "%s: iterations must be in [1, %d], got %d", who, OFL_ISEARCH_MAX_ITER, iterations);
-    if (!(__builtin_isfinite(floor) && floor > 0.0f)) return fail(OFL_E_INVALID, "%s: floor must be finite and positive (got %g)", who, (double)floor);
+    if (!finite_positive(floor)) return fail(OFL_E_INVALID, "%s: floor must be finite and positive (got %g)", who, (double)floor);
     return OFL_OK;
 }
 

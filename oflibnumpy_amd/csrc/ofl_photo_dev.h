@@ -1,12 +1,15 @@
-// ofl_photo_dev.h -- what the image-pair families K21 (ofl_photometric.hip), K22 (ofl_census.hip), K23 (ofl_refine.hip) and K24
-// (ofl_inverse_search.hip) share.  Host: PairArgs, the kernel arguments that describe the two tensors and the field, with the
-// checks of the arguments behind them (check_pair_args, check_pair_alignment) and pair_fill, which sets them.  Device: the
-// frame test of a tap, the `covered` rule of a pixel, finite32, the channel mean of a pixel (K24), the warp of a tile plus halo
-// into LDS (K22, K23) with the tile it is instantiated on, and the per-item counts of a workgroup.  A family keeps its own
-// NULL-pointer line, the checks of its settings, outputs and workspace, and the launches (DESIGN "Image-pair families").
+// ofl_photo_dev.h -- what the image-pair families K21 (ofl_photometric.hip), K22 (ofl_census.hip), K23 (ofl_refine.hip), K24
+// (ofl_inverse_search.hip) and K26 (ofl_ssim.hip) share.  Host: PairArgs, the kernel arguments that describe the two tensors and
+// the field, with their checks (check_pair_args, check_pair_alignment) and pair_fill, which sets them; for the error-map entries
+// K21, K22 and K26 -- err, covered, within, counts and a tau -- the two halves of their checks, error_map_fill (the `_dev` form)
+// and error_map_host (the host form).  Device: the frame test of a tap, the `covered` rule of a pixel, finite32, the channel
+// mean of a pixel (K24), the warp of a tile plus halo into LDS (K22, K23, K26) with its tile and window_grid, the counts of a
+// workgroup, error_store (the stores of one pixel) and window_finish (the epilogue of K22 and K26).  A family keeps the checks
+// of its settings and workspace and its launches (DESIGN "Image-pair families").
 #pragma once
 #include "ofl_common.h"
 #include "ofl_elem.h"
+#include "ofl_host_stage.h"
 
 namespace ofl {
 
@@ -62,6 +65,60 @@ inline void pair_fill(Args &a, const void *near, const void *far, int layout, in
     a.s_ch = layout == OFL_TENSOR_NCHW ? (size_t)H * W : 1;
 }
 
+// ----------------------------------------------------------------------------- host side: the error-map entries K21, K22, K26
+// their checks come in one order: check_error_map_inputs -- the required pointers, then the shared arguments --, the family's
+// own settings, check_error_map_outputs -- err / within, then tau
+inline int check_error_map_inputs(const char *who, const void *near, const void *far, const void *flow, const void *fmask,
+                                  int elem, int layout, int N, int C, int max_c, int H, int W, int sign, int quant)
+{
+    if (!near || !far || !flow || !fmask) return fail(OFL_E_INVALID, "%s: NULL pointer (near, far, flow and fmask are required)", who);
+    return check_pair_args(who, elem, layout, N, C, max_c, H, W, sign, quant);
+}
+
+inline int check_error_map_outputs(const char *who, const void *err, const void *within, float tau)
+{
+    if (!err && !within) return fail(OFL_E_INVALID, "%s: one of err and within is required", who);
+    if (within && !finite_not_negative(tau)) return fail(OFL_E_INVALID, "%s: tau must be finite and not negative (got %g)", who, (double)tau);
+    return OFL_OK;
+}
+
+// the `_dev` form, arguments checked: the device pointers on their boundaries -- near and far by element, the float2 field,
+// the 4-byte outputs --, then pair_fill and, next to it, the outputs and tau of PArgs, CArgs and SArgs
+template <class Args>
+inline int error_map_fill(const char *who, Args &a, const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                          const float *flow, const uint8_t *fmask, bool flow_shared, int sign, const uint8_t *near_mask,
+                          const uint8_t *far_mask, float *err, uint8_t *covered, uint8_t *within, uint32_t *counts, float tau)
+{
+    OFL_TRY(check_pair_alignment(who, near, far, elem));
+    if (!host_aligned(flow, 8)) return fail(OFL_E_INVALID, "%s: flow must be 8-byte aligned", who);
+    if (!host_aligned(err, 4) || !host_aligned(counts, 4)) return fail(OFL_E_INVALID, "%s: err and counts must be 4-byte aligned", who);
+    pair_fill(a, near, far, layout, N, C, H, W, flow, fmask, flow_shared, sign, near_mask, far_mask);
+    a.err = err; a.covered = covered; a.within = within; a.counts = counts; a.tau = tau;
+    return OFL_OK;
+}
+
+// the host form of an error-map entry, arguments checked: upload, `dev`, the family's `_dev` entry, on the copies (NULL where
+// the host pointer was) with the family's `settings` in their place, tau last among them, download
+template <class Dev, class... Settings>
+inline int error_map_host(const char *who, Dev dev, const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
+                          const float *flow, const uint8_t *fmask, int flow_shared, int sign, const uint8_t *near_mask,
+                          const uint8_t *far_mask, float *err, uint8_t *covered, uint8_t *within, uint32_t *counts_host, int quant,
+                          Settings... settings)
+{
+    const size_t hw = (size_t)H * W, n = (size_t)N * hw, nf = flow_shared ? hw : n;
+    const size_t bytes = n * C * (elem == OFL_EL_F32 ? 4 : 2);
+    HostStage st(who);
+    auto dn = st.in(near, bytes), df = st.in(far, bytes);
+    auto dfl = st.in(flow, nf * 2);
+    auto dfm = st.in(fmask, nf), dnm = st.in(near_mask, nf), dam = st.in(far_mask, nf);
+    auto de = st.out(err, n);
+    auto dc = st.out(covered, n), dw = st.out(within, n);
+    auto cnt = st.out(counts_host, (size_t)N * 2, true);          // the launch adds to the counts
+    OFL_TRY(st.upload());
+    OFL_TRY(dev(dn, df, elem, layout, N, C, H, W, dfl, dfm, flow_shared, sign, dnm, dam, settings..., de, dc, dw, cnt, quant, st.stream()));
+    return st.download();
+}
+
 // ----------------------------------------------------------------------------- device side
 __device__ __forceinline__ bool finite32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
@@ -115,6 +172,9 @@ __device__ __forceinline__ float channel_mean(const void *tensor, size_t base, s
 // Args: PairArgs, a struct derived from it or one with the same members, with C in 1 ... 4.  K22 and K23 instantiate it on the tile below.
 constexpr int kTX = 64, kTY = 16;       // the tile
 constexpr int kRows = 4;                // rows of a column one thread owns after the staging: 4 waves x 4 rows
+
+// the grid of a kernel instantiated on that tile: one workgroup a tile, the items along z
+inline dim3 window_grid(int N, int H, int W) { return dim3((unsigned)((W + kTX - 1) / kTX), (unsigned)((H + kTY - 1) / kTY), (unsigned)N); }
 
 template <int E, int QUANT, int R, int TX, int TY, class Args>
 __device__ __forceinline__ void stage_warped_tile(const Args &a, int n, int x0, int y0, float *s_a, float *s_b, uint8_t *s_m)
@@ -183,6 +243,40 @@ __device__ __forceinline__ void photo_count(uint32_t *counts, int n, uint32_t n_
         if (c0) atomicAdd(counts + 2 * (size_t)n, c0);
         if (c1) atomicAdd(counts + 2 * (size_t)n + 1, c1);
     }
+}
+
+// the three optional stores of ONE pixel of an error map (Args: PArgs, CArgs, SArgs) at element `at`: err = covered ? e : 0.0f,
+// covered, within = covered & (e <= tau) -- false for a NaN -- -> within, for the counts
+template <class Args>
+__device__ __forceinline__ bool error_store(const Args &a, size_t at, float e, bool cov)
+{
+    const bool wi = a.within != nullptr && cov && e <= a.tau;
+    if (a.err) a.err[at] = cov ? e : 0.0f;
+    if (a.covered) a.covered[at] = cov ? 1 : 0;
+    if (a.within) a.within[at] = wi ? 1 : 0;
+    return wi;
+}
+
+// the epilogue of a window kernel (K22, K26), called by every thread: it owns the kRows rows from y0 + kRows * wave of column
+// x0 + lane of item n; per row cm, the centre's member flag, cnt, the members of its window, and e, computed covered or not.
+// covered = inside the frame & cm & (cnt >= min_count); error_store; the wave's two ballots a row; photo_count.
+template <class Args>
+__device__ __forceinline__ void window_finish(const Args &a, int n, int x0, int y0, const bool (&cm)[kRows], const int (&cnt)[kRows],
+                                              const float (&e)[kRows])
+{
+    const int top = kRows * (threadIdx.x >> 6), x = x0 + (threadIdx.x & 63);
+    const size_t hw = (size_t)a.H * a.W;
+    uint32_t n_cov = 0, n_wi = 0;
+#pragma unroll
+    for (int j = 0; j < kRows; ++j) {
+        const int y = y0 + top + j;
+        const bool act = x < a.W && y < a.H;
+        const bool cov = act && cm[j] && cnt[j] >= a.min_count;
+        const bool wi = act && error_store(a, (size_t)n * hw + (size_t)y * a.W + x, e[j], cov);      // no store outside the frame
+        n_cov += (uint32_t)__popcll(__ballot(cov));
+        n_wi += (uint32_t)__popcll(__ballot(wi));
+    }
+    if (a.counts) photo_count(a.counts, n, n_cov, n_wi);
 }
 
 }  // namespace ofl

@@ -36,13 +36,12 @@
 // atomicAdd per counter (integer adds: their order cannot change the result); these are the only atomics.  Every element
 // offset is 64-bit.  No workspace.  A variant with two pixels per lane was not built: no figure, no variant.
 //
-// PairArgs with its checks, tap_frame, photo_covered and photo_count are shared with K22 ... K24 (ofl_photo_dev.h).
+// Shared (ofl_photo_dev.h): PairArgs with its checks, tap_frame, photo_covered, photo_count; with K22 and K26 the entries' frame and error_store.
 //
 // OUT OF SCOPE: window metrics (SSIM, gradient constancy; the census distance is K22, ofl_census.hip), a reduction of the
 // map, a backward pass, mixed element types or layouts, integer tensors, padding offsets.
 #include "ofl_common.h"
 #include "ofl_elem.h"
-#include "ofl_host_stage.h"
 #include "ofl_photo_dev.h"
 
 #pragma clang fp contract(off)
@@ -80,10 +79,7 @@ __device__ __forceinline__ void photo_finish(const PArgs &a, size_t at, float S,
 {
     float e = __fmul_rn(S, a.inv_c);
     if (a.metric == OFL_PHOTO_L2) e = sqrtf(e);
-    wi = a.within != nullptr && cov && e <= a.tau;
-    if (a.err) a.err[at] = cov ? e : 0.0f;
-    if (a.covered) a.covered[at] = cov ? 1 : 0;
-    if (a.within) a.within[at] = wi ? 1 : 0;
+    wi = error_store(a, at, e, cov);                     // ofl_photo_dev.h
 }
 
 // ---------------------------------------------------------------------------------------------- planar
@@ -245,14 +241,10 @@ int check_photometric_args(const char *who, const void *near, const void *far, i
                            const void *flow, const void *fmask, int sign, int metric, float eps, float tau,
                            const void *err, const void *within, int quant)
 {
-    if (!near || !far || !flow || !fmask) return fail(OFL_E_INVALID, "%s: NULL pointer (near, far, flow and fmask are required)", who);
-    OFL_TRY(check_pair_args(who, elem, layout, N, C, 65535, H, W, sign, quant));
+    OFL_TRY(check_error_map_inputs(who, near, far, flow, fmask, elem, layout, N, C, 65535, H, W, sign, quant));
     if (metric != OFL_PHOTO_L1 && metric != OFL_PHOTO_L2 && metric != OFL_PHOTO_CHARBONNIER) return fail(OFL_E_INVALID, "%s: bad metric %d", who, metric);
-    if (!(eps >= 0.0f) || !__builtin_isfinite(eps)) return fail(OFL_E_INVALID, "%s: eps must be finite and not negative (got %g)", who, (double)eps);
-    if (!err && !within) return fail(OFL_E_INVALID, "%s: one of err and within is required", who);
-    if (within && (!(tau >= 0.0f) || !__builtin_isfinite(tau)))
-        return fail(OFL_E_INVALID, "%s: tau must be finite and not negative (got %g)", who, (double)tau);
-    return OFL_OK;
+    if (!finite_not_negative(eps)) return fail(OFL_E_INVALID, "%s: eps must be finite and not negative (got %g)", who, (double)eps);
+    return check_error_map_outputs(who, err, within, tau);
 }
 
 template <int E, int QUANT>
@@ -293,15 +285,11 @@ int ofl_photometric_dev(const void *near, const void *far, int elem, int layout,
 {
     OFL_TRY(need_device());
     OFL_TRY(check_photometric_args("ofl_photometric", near, far, elem, layout, N, C, H, W, flow, fmask, sign, metric, eps, tau, err, within, quant));
-    OFL_TRY(check_pair_alignment("ofl_photometric", near, far, elem));
-    if (!host_aligned(flow, 8)) return fail(OFL_E_INVALID, "ofl_photometric: flow must be 8-byte aligned");
-    if (!host_aligned(err, 4) || !host_aligned(counts, 4)) return fail(OFL_E_INVALID, "ofl_photometric: err and counts must be 4-byte aligned");
     PArgs a;
-    pair_fill(a, near, far, layout, N, C, H, W, flow, fmask, flow_shared != 0, sign, near_mask, far_mask);
-    a.err = err; a.covered = covered; a.within = within; a.counts = counts;
+    OFL_TRY(error_map_fill("ofl_photometric", a, near, far, elem, layout, N, C, H, W, flow, fmask, flow_shared != 0, sign, near_mask, far_mask,
+                           err, covered, within, counts, tau));
     a.metric = metric;
     a.eps2 = eps * eps;                                  // float32, rounded once (-ffp-contract=off)
-    a.tau = tau;
     hipStream_t s = stream_of(stream);
     with_elem(elem, [&](auto E) { with_quant(quant, [&](auto Q) { launch_photometric<E.value, Q.value>(a, layout, s); }); });
     OFL_HIP(hipGetLastError());
@@ -316,19 +304,8 @@ int ofl_photometric(const void *near, const void *far, int elem, int layout, int
 {
     OFL_TRY(need_device());
     OFL_TRY(check_photometric_args("ofl_photometric", near, far, elem, layout, N, C, H, W, flow, fmask, sign, metric, eps, tau, err, within, quant));
-    const size_t hw = (size_t)H * W, n = (size_t)N * hw, nf = flow_shared ? hw : n;
-    const size_t bytes = n * C * (elem == OFL_EL_F32 ? 4 : 2);
-    HostStage st("ofl_photometric");
-    auto dn = st.in(near, bytes), df = st.in(far, bytes);
-    auto dfl = st.in(flow, nf * 2);
-    auto dfm = st.in(fmask, nf), dnm = st.in(near_mask, nf), dam = st.in(far_mask, nf);
-    auto de = st.out(err, n);
-    auto dc = st.out(covered, n), dw = st.out(within, n);
-    auto cnt = st.out(counts_host, (size_t)N * 2, true);          // the launch adds to the counts
-    OFL_TRY(st.upload());
-    OFL_TRY(ofl_photometric_dev(dn, df, elem, layout, N, C, H, W, dfl, dfm, flow_shared, sign, dnm, dam, metric, eps, tau,
-                                de, dc, dw, cnt, quant, st.stream()));
-    return st.download();
+    return error_map_host("ofl_photometric", ofl_photometric_dev, near, far, elem, layout, N, C, H, W, flow, fmask, flow_shared, sign, near_mask, far_mask,
+                          err, covered, within, counts_host, quant, metric, eps, tau);
 }
 
 }  // extern "C"

@@ -202,19 +202,17 @@ void refine_finish_kernel(const RArgs a)
     reinterpret_cast<float2 *>(a.out)[p] = f;
 }
 
-bool finite_in(float v, float lo, bool open_lo) { return __builtin_isfinite(v) && (open_lo ? v > lo : v >= lo); }
-
 int check_refine_args(const char *who, const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
                       const void *flow, const void *fmask, int sign, float alpha, float delta, float zeta, float eps,
                       int fixed_point, int sor, float omega, const void *out, int quant)
 {
     if (!near || !far || !flow || !fmask || !out) return fail(OFL_E_INVALID, "%s: NULL pointer (near, far, flow, fmask and out are required)", who);
     OFL_TRY(check_pair_args(who, elem, layout, N, C, OFL_REFINE_MAX_C, H, W, sign, quant));
-    if (!finite_in(alpha, 0.0f, false)) return fail(OFL_E_INVALID, "%s: alpha must be finite and not negative (got %g)", who, (double)alpha);
-    if (!finite_in(delta, 0.0f, false)) return fail(OFL_E_INVALID, "%s: delta must be finite and not negative (got %g)", who, (double)delta);
-    if (!finite_in(zeta, 0.0f, true)) return fail(OFL_E_INVALID, "%s: zeta must be finite and positive (got %g)", who, (double)zeta);
-    if (!finite_in(eps, 0.0f, true)) return fail(OFL_E_INVALID, "%s: eps must be finite and positive (got %g)", who, (double)eps);
-    if (!finite_in(zeta * zeta, 0.0f, true) || !finite_in(eps * eps, 0.0f, true))
+    if (!finite_not_negative(alpha)) return fail(OFL_E_INVALID, "%s: alpha must be finite and not negative (got %g)", who, (double)alpha);
+    if (!finite_not_negative(delta)) return fail(OFL_E_INVALID, "%s: delta must be finite and not negative (got %g)", who, (double)delta);
+    if (!finite_positive(zeta)) return fail(OFL_E_INVALID, "%s: zeta must be finite and positive (got %g)", who, (double)zeta);
+    if (!finite_positive(eps)) return fail(OFL_E_INVALID, "%s: eps must be finite and positive (got %g)", who, (double)eps);
+    if (!finite_positive(zeta * zeta) || !finite_positive(eps * eps))
         return fail(OFL_E_INVALID, "%s: zeta^2 and eps^2 must be finite and positive in float32", who);
     if (fixed_point < 1 || fixed_point > OFL_REFINE_MAX_ITER) return fail(OFL_E_INVALID, "%s: fixed_point must be in [1, %d], got %d", who, OFL_REFINE_MAX_ITER, fixed_point);
     if (sor < 1 || sor > OFL_REFINE_MAX_ITER) return fail(OFL_E_INVALID, "%s: sor must be in [1, %d], got %d", who, OFL_REFINE_MAX_ITER, sor);
@@ -271,7 +269,7 @@ int ofl_refine_dev(const void *near, const void *far, int elem, int layout, int 
     a.alpha = alpha; a.delta = delta; a.zeta2 = zeta * zeta; a.eps2 = eps * eps; a.omega = omega;
 
     hipStream_t s = stream_of(stream);
-    const dim3 tiles((unsigned)((W + kTX - 1) / kTX), (unsigned)((H + kTY - 1) / kTY), (unsigned)N);
+    const dim3 tiles = window_grid(N, H, W);
     with_elem(elem, [&](auto E) { with_quant(quant, [&](auto Q) {
         hipLaunchKernelGGL((refine_setup_kernel<E.value, Q.value>), tiles, dim3(256), 0, s, a);
     }); });

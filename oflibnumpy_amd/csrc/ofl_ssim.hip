@@ -32,15 +32,15 @@
 //            SIMD with spilled scalars.  Every register array is indexed by unrolled constants only; the taps are passed
 //            by value, the column's tap at a constant offset of the kernel arguments and the row's tap g[i - j] by a
 //            wave-uniform index -- a scalar load, no register array --, so nothing goes to scratch.
-// counts: K21's scheme (ballot + popcount, at most one integer atomicAdd per workgroup and counter); no other atomics, no
-// workspace, 64-bit element offsets.  24 instantiations: 3 element types x 2 quant x 4 windows.
+// Epilogue: window_finish (ofl_photo_dev.h, shared with K22) -- covered, the stores of error_store and the counts in K21's
+// scheme (ballot + popcount, at most one integer atomicAdd per workgroup and counter); no other atomics, no workspace, 64-bit
+// element offsets.  24 instantiations: 3 element types x 2 quant x 4 windows.
 //
 // OUT OF SCOPE: C > 4 and a per-channel SSIM, luma weights, sample (N - 1) moments, windows that are not square or of another
 // size, MS-SSIM, the three components as outputs, gradient constancy, a reduction of the map, PSNR, a backward pass, mixed
 // element types or layouts, integer tensors.
 #include "ofl_common.h"
 #include "ofl_elem.h"
-#include "ofl_host_stage.h"
 #include "ofl_photo_dev.h"
 
 #pragma clang fp contract(off)
@@ -86,9 +86,7 @@ void ssim_kernel(const SArgs a)
     __shared__ float   s_a[NE], s_b[NE];
     __shared__ uint8_t s_m[NE];
 
-    const int H = a.H, W = a.W;
     const int n = blockIdx.z, x0 = blockIdx.x * kTX, y0 = blockIdx.y * kTY;
-    const size_t hw = (size_t)H * W;
 
     stage_warped_tile<E, QUANT, R, kTX, kTY>(a, n, x0, y0, s_a, s_b, s_m);           // ofl_photo_dev.h
     __syncthreads();
@@ -129,55 +127,34 @@ void ssim_kernel(const SArgs a)
         }
     }
 
-    uint32_t n_cov = 0, n_wi = 0;
-    const int x = x0 + lane;
+    bool  cm[kRows];
+    float e[kRows];
 #pragma unroll
-    for (int j = 0; j < kRows; ++j) {
-        const int y = y0 + top + j;
-        const bool act = x < W && y < H;
-        const bool cov = act && s_m[(top + R + j) * TW + lane + R] != 0 && cnt[j] >= a.min_count;
-        const float e = ssim_error(S[j], a.c1, a.c2);
-        const bool wi = a.within != nullptr && cov && e <= a.tau;
-        if (act) {
-            const size_t o = (size_t)n * hw + (size_t)y * W + x;
-            if (a.err) a.err[o] = cov ? e : 0.0f;
-            if (a.covered) a.covered[o] = cov ? 1 : 0;
-            if (a.within) a.within[o] = wi ? 1 : 0;
-        }
-        n_cov += (uint32_t)__popcll(__ballot(cov));
-        n_wi += (uint32_t)__popcll(__ballot(wi));
-    }
-    if (a.counts) photo_count(a.counts, n, n_cov, n_wi);
+    for (int j = 0; j < kRows; ++j) { cm[j] = s_m[(top + R + j) * TW + lane + R] != 0; e[j] = ssim_error(S[j], a.c1, a.c2); }
+    window_finish(a, n, x0, y0, cm, cnt, e);                                        // ofl_photo_dev.h
 }
-
-bool positive_finite(float v) { return v > 0.0f && __builtin_isfinite(v); }
 
 int check_ssim_args(const char *who, const void *near, const void *far, int elem, int layout, int N, int C, int H, int W,
                     const void *flow, const void *fmask, int sign, int window, const float *taps, float c1, float c2,
                     int min_count, float tau, const void *err, const void *within, int quant)
 {
-    if (!near || !far || !flow || !fmask) return fail(OFL_E_INVALID, "%s: NULL pointer (near, far, flow and fmask are required)", who);
-    OFL_TRY(check_pair_args(who, elem, layout, N, C, OFL_SSIM_MAX_C, H, W, sign, quant));
+    OFL_TRY(check_error_map_inputs(who, near, far, flow, fmask, elem, layout, N, C, OFL_SSIM_MAX_C, H, W, sign, quant));
     if (window != 3 && window != 5 && window != 7 && window != 11)
         return fail(OFL_E_INVALID, "%s: window must be 3, 5, 7 or 11, got %d", who, window);
     if (!taps) return fail(OFL_E_INVALID, "%s: taps must not be NULL (a host pointer to %d float32 values)", who, window);
     for (int i = 0; i < window; ++i)
-        if (!positive_finite(taps[i])) return fail(OFL_E_INVALID, "%s: taps[%d] must be finite and positive (got %g)", who, i, (double)taps[i]);
-    if (!positive_finite(c1)) return fail(OFL_E_INVALID, "%s: c1 must be finite and positive (got %g)", who, (double)c1);
-    if (!positive_finite(c2)) return fail(OFL_E_INVALID, "%s: c2 must be finite and positive (got %g)", who, (double)c2);
+        if (!finite_positive(taps[i])) return fail(OFL_E_INVALID, "%s: taps[%d] must be finite and positive (got %g)", who, i, (double)taps[i]);
+    if (!finite_positive(c1)) return fail(OFL_E_INVALID, "%s: c1 must be finite and positive (got %g)", who, (double)c1);
+    if (!finite_positive(c2)) return fail(OFL_E_INVALID, "%s: c2 must be finite and positive (got %g)", who, (double)c2);
     if (min_count < 1 || min_count > window * window)
         return fail(OFL_E_INVALID, "%s: min_count must be in [1, %d], got %d", who, window * window, min_count);
-    if (!err && !within) return fail(OFL_E_INVALID, "%s: one of err and within is required", who);
-    if (within && (!(tau >= 0.0f) || !__builtin_isfinite(tau)))
-        return fail(OFL_E_INVALID, "%s: tau must be finite and not negative (got %g)", who, (double)tau);
-    return OFL_OK;
+    return check_error_map_outputs(who, err, within, tau);
 }
 
 template <int E, int QUANT, int K>
 void launch_ssim(const SArgs &a, hipStream_t s)
 {
-    const dim3 grid((unsigned)((a.W + kTX - 1) / kTX), (unsigned)((a.H + kTY - 1) / kTY), (unsigned)a.N);
-    hipLaunchKernelGGL((ssim_kernel<E, QUANT, K>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((ssim_kernel<E, QUANT, K>), window_grid(a.N, a.H, a.W), dim3(256), 0, s, a);
 }
 
 }  // namespace
@@ -193,14 +170,11 @@ int ofl_ssim_dev(const void *near, const void *far, int elem, int layout, int N,
     OFL_TRY(need_device());
     OFL_TRY(check_ssim_args("ofl_ssim", near, far, elem, layout, N, C, H, W, flow, fmask, sign, window, taps, c1, c2, min_count, tau,
                             err, within, quant));
-    OFL_TRY(check_pair_alignment("ofl_ssim", near, far, elem));
-    if (!host_aligned(flow, 8)) return fail(OFL_E_INVALID, "ofl_ssim: flow must be 8-byte aligned");
-    if (!host_aligned(err, 4) || !host_aligned(counts, 4)) return fail(OFL_E_INVALID, "ofl_ssim: err and counts must be 4-byte aligned");
     SArgs a;
-    pair_fill(a, near, far, layout, N, C, H, W, flow, fmask, flow_shared != 0, sign, near_mask, far_mask);
-    a.err = err; a.covered = covered; a.within = within; a.counts = counts;
+    OFL_TRY(error_map_fill("ofl_ssim", a, near, far, elem, layout, N, C, H, W, flow, fmask, flow_shared != 0, sign, near_mask, far_mask,
+                           err, covered, within, counts, tau));
     a.min_count = min_count;
-    a.c1 = c1; a.c2 = c2; a.tau = tau;
+    a.c1 = c1; a.c2 = c2;
     for (int i = 0; i < kMaxTaps; ++i) a.g[i] = i < window ? taps[i] : 0.0f;        // read here: the caller may free them on return
     hipStream_t s = stream_of(stream);
     with_elem(elem, [&](auto E) { with_quant(quant, [&](auto Q) {
@@ -224,19 +198,8 @@ int ofl_ssim(const void *near, const void *far, int elem, int layout, int N, int
     OFL_TRY(need_device());
     OFL_TRY(check_ssim_args("ofl_ssim", near, far, elem, layout, N, C, H, W, flow, fmask, sign, window, taps, c1, c2, min_count, tau,
                             err, within, quant));
-    const size_t hw = (size_t)H * W, n = (size_t)N * hw, nf = flow_shared ? hw : n;
-    const size_t bytes = n * C * (elem == OFL_EL_F32 ? 4 : 2);
-    HostStage st("ofl_ssim");
-    auto dn = st.in(near, bytes), df = st.in(far, bytes);
-    auto dfl = st.in(flow, nf * 2);
-    auto dfm = st.in(fmask, nf), dnm = st.in(near_mask, nf), dam = st.in(far_mask, nf);
-    auto de = st.out(err, n);
-    auto dc = st.out(covered, n), dw = st.out(within, n);
-    auto cnt = st.out(counts_host, (size_t)N * 2, true);          // the launch adds to the counts
-    OFL_TRY(st.upload());
-    OFL_TRY(ofl_ssim_dev(dn, df, elem, layout, N, C, H, W, dfl, dfm, flow_shared, sign, dnm, dam, window, taps, c1, c2, min_count, tau,
-                         de, dc, dw, cnt, quant, st.stream()));
-    return st.download();
+    return error_map_host("ofl_ssim", ofl_ssim_dev, near, far, elem, layout, N, C, H, W, flow, fmask, flow_shared, sign, near_mask, far_mask,
+                          err, covered, within, counts_host, quant, window, taps, c1, c2, min_count, tau);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-"""The argument checks the image-pair families K21 ... K24 share, at the eight native entries: ofl_photometric, ofl_census,
-ofl_refine, ofl_inverse_search and their _dev forms.  One argument of the shared set is invalid at a time, every call
+"""The argument checks the image-pair families K21 ... K24 and K26 share, at the ten native entries: ofl_photometric, ofl_census,
+ofl_ssim, ofl_refine, ofl_inverse_search and their _dev forms.  One argument of the shared set is invalid at a time, every call
 fails validation -- no kernel is launched -- and the return code and the exact ofl_last_error text are pinned."""
 import numpy as np
 import pytest
@@ -12,8 +12,9 @@ pytestmark = pytest.mark.gpu
 F32, U8 = np.float32, np.uint8
 H = W = 8
 PX = H * W
-MAX_C = {'photometric': 65535, 'census': 4, 'refine': 4, 'inverse_search': 4}
+MAX_C = {'photometric': 65535, 'census': 4, 'ssim': 4, 'refine': 4, 'inverse_search': 4}
 FAMILIES = sorted(MAX_C)
+TAPS = np.ones(3, F32)                          # K26's window, a host array in both forms
 
 # the shared arguments of a good call: 8 x 8, three channels of float32
 GOOD = dict(elem=nat.EL_F32, layout=nat.TENSOR_NCHW, N=1, C=3, H=H, W=W, sign=1, quant=nat.QUANT_OPENCV)
@@ -61,6 +62,9 @@ def _call(family, m, near=None, **change):
         return fn(*head, 1, a['sign'], None, None, nat.PHOTO_L1, F32(0), F32(0), m.out, m.o1, None, None, a['quant'], *m.tail)
     if family == 'census':
         return fn(*head, 1, a['sign'], None, None, 3, nat.CENSUS_HARD, F32(0), F32(0), 8, F32(0), m.out, m.o1, None, None,
+                  a['quant'], *m.tail)
+    if family == 'ssim':
+        return fn(*head, 1, a['sign'], None, None, 3, TAPS.ctypes.data, F32(1), F32(1), 9, F32(0), m.out, m.o1, None, None,
                   a['quant'], *m.tail)
     if family == 'refine':
         return fn(*head, a['sign'], None, None, None, F32(20), F32(5), F32(0.1), F32(0.1), 1, 1, F32(1.6), *work, m.out, m.o1,

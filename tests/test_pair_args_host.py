@@ -1,6 +1,6 @@
-"""The argument surface the image-pair families K21 ... K24 share, without a GPU: the messages of the host path of
-Flow.photometric / census / refine / inverse_search that are raised before any native call, and those of the number checks
-of the four args.*_args functions.  Every expected string is written out."""
+"""The argument surface the image-pair families K21 ... K24 and K26 share, without a GPU: the messages of the host path of
+Flow.photometric / census / ssim / refine / inverse_search that are raised before any native call, and those of the number
+checks of the args.*_args functions of K21 ... K24 (K26's: test_ssim_host.py).  Every expected string is written out."""
 import re
 
 import numpy as np
@@ -13,7 +13,8 @@ F32 = np.float32
 H, W = 6, 9
 
 PREFIX = {'photometric': "Error computing photometric error: ", 'census': "Error computing census distance: ",
-          'refine': "Error refining flow: ", 'inverse_search': "Error searching flow: "}
+          'ssim': "Error computing structural similarity: ", 'refine': "Error refining flow: ",
+          'inverse_search': "Error searching flow: "}
 METHODS = sorted(PREFIX)
 
 
@@ -48,7 +49,7 @@ def test_shared_host_path_messages(method):
         _call(method, _img(3, W, H), _img(3, W, H), layout='chw')
 
 
-@pytest.mark.parametrize("method", ['census', 'refine', 'inverse_search'])
+@pytest.mark.parametrize("method", ['census', 'ssim', 'refine', 'inverse_search'])
 def test_channel_limit_message(method):
     with _raises(ValueError, PREFIX[method] + "the tensors need 1 to 4 channels (grey, two-plane, RGB, RGBA), got 5"):
         _call(method, _img(H, W, 5), _img(H, W, 5))
@@ -64,7 +65,7 @@ def test_one_item_message(method):
         _call(method, _img(2, H, 8, 3), _img(2, H, 8, 3))                     # before the height / width check
 
 
-@pytest.mark.parametrize("method", ['photometric', 'census', 'refine'])
+@pytest.mark.parametrize("method", ['photometric', 'census', 'ssim', 'refine'])
 def test_mask_messages(method):
     p = PREFIX[method]
     with _raises(ValueError, p + "near_mask needs to have the shape of the flow, got (9, 6) and (6, 9)"):
